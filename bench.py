@@ -24,7 +24,10 @@ the measured time with checks x cycles-per-check from the diagnostics build
 (profiles/pipe_model_latest.json).  The 16 B x S*C*N figure is reported under
 `work_equivalent`, labelled as what it is.
 
-Legs in the same JSON line (rank 0 at N = 1; single scenarios are replicas, they do not shard):
+A plain run sets up, warms up, times the K steps of the headline workload, writes its outputs
+(--dump-outputs) and prints the result line.  Everything below runs only with --full.
+
+Legs in the same JSON line with --full (rank 0 at N = 1; single scenarios are replicas, they do not shard):
   config1   BASELINE configs[0]: the fleet.kdl dry-run fixtures, microseconds per plan on the GPU
             path and on the single-threaded C oracle, and the "Rust not available" statement
   config2   BASELINE configs[1]: 1 x 10k services x 1k servers (cpu/mem/ports)
@@ -36,7 +39,14 @@ Legs in the same JSON line (rank 0 at N = 1; single scenarios are replicas, they
   cpu_single_thread  the single-threaded C oracle on the same inputs as configs 2, 3 and 5
                      (A1 legacy order, levels, FFD), each GPU result checked bit for bit
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+--dump-outputs DIR writes what the last timed step handed back (rank 0) as DIR/<name>.npy, float32 or
+float64 holding the integers exactly: `best` (winning scenario id), `plan_assign` / `plan_reason` (the
+winner's plan as handed off), `cost_rejected` / `cost_nodes_used` / `cost_scenario` (the fields of every
+scenario's packed cost, SPEC.md 2.4) and `assign_sample` / `reason_sample` (a fixed, seeded sample of this
+rank's S x C per-scenario plans, positions in `sample_index`).  The inputs depend on the arguments only,
+so two builds can be compared file for file.
 
 --gpus N without an external launcher starts N worker processes itself (before
 any GPU call in this parent), one per GPU, over torch.distributed (RCCL).
@@ -72,13 +82,18 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scenarios", type=int, default=S4, help="total what-if scenarios (config 4: 4096)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the config 1 / 2 / 3 / 5 legs, the stage-2 sweep and the CPU baselines "
+                         "(off by default: a plain run times the headline workload only)")
     ap.add_argument("--config3-steps", type=int, default=3)
-    ap.add_argument("--no-legs", action="store_true", help="skip the config 2 / 3 / 5 legs")
-    ap.add_argument("--no-stage2", action="store_true")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the config 1 / 2 / 3 / 5 legs")
+    ap.add_argument("--no-stage2", action="store_true", help="with --full: skip the stage-2 sweep")
     ap.add_argument("--cpu-budget-s", type=float, default=12.0, help="CPU baseline sample budget (wall s)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads for the CPU baseline (default: every usable core, within the cgroup quota)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--dry-launch", action="store_true",
                     help="test hook: each rank prints its rank/world env as JSON and exits (no GPU call)")
     return ap.parse_args()
@@ -548,6 +563,41 @@ def stage2_leg(planner, dev, steps, S=512):
     return out
 
 
+DUMP_SAMPLE = 1 << 20  # per-scenario plan entries kept by --dump-outputs (the full S x C is ~1 GB)
+
+
+def dump_outputs(path, winner, plan, db, C):
+    """--dump-outputs: what the last timed step handed back, as <path>/<name>.npy.  u32 / u64 fields go
+    to float64 and bytes to float32 (both exact); ~22 MB in all.  The per-scenario plans are sampled
+    at DUMP_SAMPLE positions drawn once from a fixed seed (every position when there are fewer)."""
+    import numpy as np
+    import torch
+
+    from fleetflow_amd import shard
+    os.makedirs(path, exist_ok=True)
+    assign, reason = shard.unpack_plan(plan, C)
+    cost = winner["costs"].cpu().numpy().view(np.uint64)
+    total = db.assign.numel()
+    if total > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(SEED4).choice(total, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(total, dtype=np.int64)
+    idx_t = torch.from_numpy(idx).to(db.assign.device)
+    arrays = {
+        "best": np.array([winner["best"]], np.float64),
+        "plan_assign": assign.cpu().numpy().view(np.uint32).astype(np.float64),
+        "plan_reason": reason.cpu().numpy().astype(np.float32),
+        "cost_rejected": (cost >> np.uint64(40)).astype(np.float64),
+        "cost_nodes_used": ((cost >> np.uint64(16)) & np.uint64(0xFFFFFF)).astype(np.float64),
+        "cost_scenario": (cost & np.uint64(0xFFFF)).astype(np.float64),
+        "sample_index": idx.astype(np.float64),
+        "assign_sample": db.assign[idx_t].cpu().numpy().view(np.uint32).astype(np.float64),
+        "reason_sample": db.reason[idx_t].cpu().numpy().astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def worker(args):
     if args.dry_launch:
         print(json.dumps({k: os.environ.get(k) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR",
@@ -590,6 +640,7 @@ def worker(args):
         planner.dev_argmin_cost(costs, best)
         b = int(best.item())  # every rank holds the same winner
         winner["best"] = b
+        winner["costs"] = costs
         winner["owner"] = shard.hand_off_plan(b, db.assign, db.reason, C, rank, world, S_total, plan)
 
     barrier = (lambda: dist.barrier()) if world > 1 else (lambda: None)
@@ -616,6 +667,8 @@ def worker(args):
     if world > 1:
         dist.all_reduce(kt, op=dist.ReduceOp.MAX)
     kernel_ms, sort_avg_ms = float(kt[0].item()), float(kt[1].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, winner, plan, db, C)
 
     out = None
     if rank == 0:
@@ -643,8 +696,8 @@ def worker(args):
             "breakdown_ms": {"ffd_kernel": kernel_ms, "sort": sort_avg_ms},
             "best_scenario": winner["best"], "best_owner_rank": winner["owner"],
         }
-    # the config-3 leg and the CPU baseline only at N = 1 (single-scenario replicas do not shard)
-    if world == 1 and rank == 0:
+    # --full: the other legs and the CPU baselines, only at N = 1 (single-scenario replicas do not shard)
+    if args.full and world == 1 and rank == 0:
         del db, pristine
         torch.cuda.empty_cache()
         gpu = {}  # plans of the single-scenario legs, for the oracle check

@@ -23,7 +23,7 @@ for s in $steps; do
         > ${log}_tests.log 2>&1 || { echo "tests step failed"; tail -40 ${log}_tests.log; exit 1; }
       tail -3 ${log}_tests.log ;;
     bench)
-      timeout -k 10 400 python -u bench.py > ${log}_bench.json 2> ${log}_bench.err \
+      timeout -k 10 400 python -u bench.py --full > ${log}_bench.json 2> ${log}_bench.err \
         || { echo "bench failed"; tail -30 ${log}_bench.err; exit 1; }
       cat ${log}_bench.json ;;
     scale)

@@ -9,7 +9,7 @@ tag=${1:?tag}
 mkdir -p gpurun_out
 for rep in 1 2; do
   for v in "" _place_imo _place_iilp _feas_imo _feas_iilp; do
-    FLEETPLACE_LIB=$root/fleetflow_amd/libfleetplace$v.so timeout -k 10 200 python -u bench.py --no-legs --no-cpu-baseline \
+    FLEETPLACE_LIB=$root/fleetflow_amd/libfleetplace$v.so timeout -k 10 200 python -u bench.py --full --no-legs --no-cpu-baseline \
       --steps 5 > gpurun_out/${tag}_bench${v}_${rep}.json 2> gpurun_out/${tag}_bench${v}_${rep}.err || { echo "bench $v failed"; tail gpurun_out/${tag}_bench${v}_${rep}.err; exit 1; }
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], 'rep', sys.argv[3], 'step', round(d['ms_per_step'],3), d['breakdown_ms'], 'stage2', round(d['stage2']['kernel_ms'],3))" gpurun_out/${tag}_bench${v}_${rep}.json "lib$v" $rep
   done
