@@ -525,6 +525,93 @@ extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const 
     return batch_host(c, &b);
 }
 
+// Scored placement (SPEC.md 2.6): fp_place_batch's staging with the per-scenario strategy and
+// preferred-label words and the optional node counts.  The strategies are host memory here, so a
+// value that is no fp_strategy is refused before anything is staged.
+static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
+                             uint32_t *node_count) {
+    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
+    const size_t SC = S * C, SN = S * N;
+    if (S && !strategy) return FP_EINVAL;
+    for (size_t s = 0; s < S; ++s)
+        if (strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
+    if (S && C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign ||
+                   !b->reason))
+        return FP_EINVAL;
+    if (S && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used ||
+                   !b->schedulable))
+        return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1) + SN * (4 * 5 + 1) + S * (8 + 4 + 4) + 20 * 256);
+    if (rc) return rc;
+    fp_stage_reset(c);
+    fp_batch d = *b;
+    d.cpu_m = stage_in(c, b->cpu_m, SC, &rc);
+    d.mem_mib = stage_in(c, b->mem_mib, SC, &rc);
+    d.req_labels = stage_in(c, b->req_labels, SC, &rc);
+    d.conflict = stage_in(c, b->conflict, SC, &rc);
+    d.level = b->level ? stage_in(c, b->level, SC, &rc) : nullptr;
+    d.cpu_free = stage_in(c, b->cpu_free, SN, &rc);
+    d.mem_free = stage_in(c, b->mem_free, SN, &rc);
+    d.labels = stage_in(c, b->labels, SN, &rc);
+    d.conflict_used = stage_in(c, b->conflict_used, SN, &rc);
+    d.schedulable = stage_in(c, b->schedulable, SN, &rc);
+    const uint32_t *dstrat = stage_in(c, strategy, S, &rc);
+    const uint32_t *dpref = stage_in(c, preferred, S, &rc);
+    uint32_t *dcount = stage_in(c, node_count, SN, &rc);
+    d.assign = stage_out<uint32_t>(c, SC, &rc);
+    d.reason = stage_out<uint8_t>(c, SC, &rc);
+    d.cost = stage_out<uint64_t>(c, S, &rc);
+    if (rc) return rc;
+    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount);
+    if (rc) return rc;
+    const OutCopy o[] = {{b->assign, d.assign, SC * 4},          {b->reason, d.reason, SC},
+                         {b->cost, d.cost, S * 8},                {b->cpu_free, d.cpu_free, SN * 4},
+                         {b->mem_free, d.mem_free, SN * 4},       {b->conflict_used, d.conflict_used, SN * 4},
+                         {node_count, dcount, SN * 4}};
+    return copy_back_all(c, o, 7);
+}
+
+extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                     const uint32_t *preferred_labels, uint32_t *node_count) {
+    if (!c || !b) return FP_EINVAL;
+    return batch_policy_host(c, b, strategy, preferred_labels, node_count);
+}
+
+extern "C" int fp_place_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                               uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                               uint32_t *assign_out, uint8_t *reason_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    fp_batch b;
+    memset(&b, 0, sizeof(b));
+    b.n_scen = 1;
+    b.n_containers = cs->n;
+    b.n_nodes = ns->n;
+    b.cpu_m = cs->cpu_m;
+    b.mem_mib = cs->mem_mib;
+    b.req_labels = cs->req_labels;
+    b.conflict = cs->conflict;
+    b.level = level;
+    b.cpu_free = ns->cpu_free;
+    b.mem_free = ns->mem_free;
+    b.labels = ns->labels;
+    b.conflict_used = ns->conflict_used;
+    b.schedulable = ns->schedulable;
+    b.assign = assign_out;
+    b.reason = reason_out;
+    return batch_policy_host(c, &b, &strategy, &preferred_labels, node_count);
+}
+
+extern "C" int fp_dev_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                         const uint32_t *preferred_labels, uint32_t *node_count) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count));
+}
+
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,
                               uint32_t *first_out, uint32_t *count_out, uint64_t *bitmap_out) {
     if (!c || !cs || !ns) return FP_EINVAL;

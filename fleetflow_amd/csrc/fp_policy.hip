@@ -1,0 +1,384 @@
+// fp_policy.hip -- scored placement (SPEC.md 2.6): spread / pack / fill-lowest placers and soft
+// preferred labels, batched over what-if scenarios.  One workgroup owns one scenario.
+//
+// First fit (fp_place.hip, fp_pipe.hip) prunes and pipelines on monotonicity.  A scored rule picks the
+// feasible node with the smallest key, on state that changes after every placement, so every container
+// needs an argmin over every node: a different kernel.
+//
+// Per fp_dev_place_batch_policy call (asynchronous, nothing is read back):
+//   1. k_policy_check : one word, set when any scenario's strategy is not an fp_strategy value; every
+//                       later kernel of the call returns on it before writing (all-or-nothing), and
+//                       FP_EINVAL goes into the context's error word
+//   2. k_policy_keys  : key (~cpu << 32 | ~mem), value = the index in the scenario; a stable rocprim
+//                       radix sort over 64 bits (segmented per scenario for S > 1) gives the FFD order
+//                       (cpu desc, mem desc, index asc) -- the recipe of fp_place.hip step 3b
+//   3. k_policy<BLK,K>: the placer.  The scenario's node state lives in registers for the whole
+//                       kernel: thread t of a BLK-thread block owns nodes t + BLK * j, j < K, five
+//                       words each (cpu_free, mem_free, conflict_used, count, labels) plus the static
+//                       preferred-label miss count, a per-thread schedulable mask and a "touched" mask.
+//                       The node arrays are only ever indexed by the unrolled j (a runtime index would
+//                       send them to scratch); the winner's update is an unrolled `if (j == J)`.
+//
+// Per container: each thread takes the min key of its K nodes (an infeasible node is all-ones), the wave
+// takes its min across lanes, lane 0 writes it to the wave's LDS slot, ONE barrier, every thread takes
+// the min of the per-wave slots, the owner of the winning node updates its registers and thread 0
+// stores assign / reason at the container's original index.
+//
+// One barrier per container suffices because the slots are double-buffered by the parity of the
+// reductions run so far.  Reduction r writes buffer r & 1 before barrier B_r and reads it after.  The
+// next writer of that buffer is reduction r + 2, and a wave gets there only past B_(r+1), which opens
+// only when every wave has arrived at it -- and a wave arrives at B_(r+1) after it has consumed its
+// reads of reduction r (the keys of reduction r + 1 depend on the winner of r).  So no write can
+// overtake a read of the same buffer (WAR), and B_r orders every write before every read (RAW).  The
+// parity counts reductions, not containers: a CYCLE container runs none, and two reductions with only a
+// skipped container between them must still use different buffers.
+//
+// The container record (cpu, mem, req, conf, original index, CYCLE flag) is uniform across the block.
+// Each wave gathers 64 records at a time into registers (lane l holds record i0 + l, loaded a chunk
+// ahead) and broadcasts container u with v_readlane, so the record arrives in scalar registers and no
+// lane ever issues a per-container load.
+//
+// No device-wide synchronisation, no spin waits, no links: the kernel cannot deadlock and has no guard.
+// N <= FP_POLICY_MAX_NODES (1024 threads x 8 nodes): past one workgroup the argmin per dependent
+// container would need a grid-wide synchronisation per placement.
+#include "fp_internal.h"
+#include <type_traits>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+
+namespace {
+
+constexpr uint64_t KEY_NONE = ~0ull;
+constexpr uint32_t KEY_NODE_BITS = 26;  // key = pref_miss << 58 | primary << 26 | node
+
+__global__ __launch_bounds__(256) void k_policy_check(const uint32_t *__restrict__ strategy, uint32_t S,
+                                                      uint32_t *__restrict__ bad, uint32_t *__restrict__ err) {
+    bool b = false;
+    for (uint32_t s = threadIdx.x; s < S; s += blockDim.x) b |= strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST;
+    const bool any = __syncthreads_or(b);
+    if (threadIdx.x == 0) {
+        *bad = any ? 1u : 0u;
+        if (any) atomicMax(err, (uint32_t)(-FP_EINVAL));
+    }
+}
+
+__global__ void k_policy_fill_cost(uint32_t S, uint32_t scen_base, const uint32_t *__restrict__ bad,
+                                   uint64_t *__restrict__ cost) {
+    if (*bad) return;
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < S) cost[s] = fpd::pack_cost(0, 0, scen_base + s);
+}
+
+__global__ __launch_bounds__(256) void k_policy_keys(const uint32_t *__restrict__ cpu, const uint32_t *__restrict__ mem,
+                                                     size_t n, uint32_t C, uint64_t *__restrict__ keys,
+                                                     uint32_t *__restrict__ vals) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        keys[i] = ((uint64_t)~cpu[i] << 32) | (uint32_t)~mem[i];
+        vals[i] = (uint32_t)i % C;  // n = S * C < 2^32
+    }
+}
+
+__global__ void k_policy_offsets(uint32_t S, uint32_t C, uint32_t *__restrict__ off) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= S) off[i] = i * C;
+}
+
+struct PolicyArgs {
+    uint32_t C, N, scen_base;
+    const uint32_t *order;                        // [S][C] FFD order (index in the scenario)
+    const uint32_t *cpu, *mem, *req, *conf;       // [S][C]
+    const uint32_t *level;                        // [S][C] or null
+    uint32_t *cpu_free, *mem_free, *conflict_used;  // [S][N] in/out
+    const uint32_t *labels;                       // [S][N]
+    const uint8_t *schedulable;                   // [S][N]
+    uint32_t *node_count;                         // [S][N] in/out or null
+    const uint32_t *strategy, *preferred;         // [S]; preferred nullable
+    uint32_t *assign;                             // [S][C]
+    uint8_t *reason;                              // [S][C]
+    uint64_t *cost;                               // [S] or null
+    const uint32_t *bad;                          // k_policy_check's word
+};
+
+__device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+// wave-uniform value of lane `l` (l uniform): the record broadcast
+__device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t l) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
+}
+
+// Cross-lane min of the 64-bit keys on the VALU (DPP), not through the LDS crossbar: with 16 waves a
+// block, 12 ds_bpermute a wave and container kept the LDS pipe busier than the key evaluation.
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+    return ((uint64_t)hi << 32) | lo;
+}
+// the min over each row of 16 lanes, in every lane of the row (all 64 lanes active).  min is idempotent,
+// so the mirrors serve as butterflies: quads, then the two quads of a half row, then the two halves
+__device__ __forceinline__ uint64_t row_min64(uint64_t v) {
+    v = min64(v, dpp64<0xB1>(v));   // quad_perm [1, 0, 3, 2]
+    v = min64(v, dpp64<0x4E>(v));   // quad_perm [2, 3, 0, 1]
+    v = min64(v, dpp64<0x141>(v));  // row_half_mirror
+    v = min64(v, dpp64<0x140>(v));  // row_mirror
+    return v;
+}
+__device__ __forceinline__ uint64_t lane64(uint64_t v, int l) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+}
+// the min over the wave, uniform: the four row mins meet in scalar registers
+__device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
+    v = row_min64(v);
+    return min64(min64(lane64(v, 0), lane64(v, 16)), min64(lane64(v, 32), lane64(v, 48)));
+}
+
+template <int BLK, int K>
+__global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
+    static_assert(BLK % 64 == 0 && (BLK & (BLK - 1)) == 0, "block of whole waves, power of two");
+    constexpr uint32_t NW = BLK / 64;
+    if (*a.bad) return;  // an invalid strategy somewhere in the batch: nothing is written
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    const uint32_t s = blockIdx.x, C = a.C, N = a.N;
+    const size_t cb = (size_t)s * C, nb = (size_t)s * N;
+    const uint32_t strat = a.strategy[s];
+    const uint32_t pref = a.preferred ? a.preferred[s] : 0u;
+
+    // ---- the scenario's node state, in registers ----
+    uint32_t cf[K], mf[K], cu[K], cnt[K], lab[K], pmh[K];  // pmh = pref_miss << 26: the key's high word
+    uint32_t sched = 0, touched = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const uint32_t n = t + (uint32_t)BLK * j;
+        const bool in = n < N;
+        cf[j] = in ? a.cpu_free[nb + n] : 0u;
+        mf[j] = in ? a.mem_free[nb + n] : 0u;
+        cu[j] = in ? a.conflict_used[nb + n] : 0u;
+        lab[j] = in ? a.labels[nb + n] : 0u;
+        cnt[j] = in && a.node_count ? a.node_count[nb + n] : 0u;
+        if (in && a.schedulable[nb + n]) sched |= 1u << j;
+        pmh[j] = (uint32_t)__popc(pref & ~lab[j]) << (58 - 32);
+    }
+
+    __shared__ uint64_t slot[2][NW];
+    uint32_t par = 0, rejected = 0;  // rejected is the same in every thread
+
+    // ---- container records, 64 per chunk, one chunk ahead ----
+    const uint32_t *ord = a.order + cb;
+    auto ld_ord = [&](uint32_t i) -> uint32_t { return i < C ? ord[i] : 0u; };
+    uint32_t r_cpu, r_mem, r_req, r_conf, r_idx;  // r_idx = FP_NONE: a CYCLE container
+    auto gather = [&](uint32_t i, uint32_t o) {
+        const bool in = i < C;
+        r_cpu = in ? a.cpu[cb + o] : 0u;
+        r_mem = in ? a.mem[cb + o] : 0u;
+        r_req = in ? a.req[cb + o] : 0u;
+        r_conf = in ? a.conf[cb + o] : 0u;
+        r_idx = in && a.level && a.level[cb + o] == FP_NONE ? FP_NONE : o;
+        if (in && r_idx == FP_NONE && w == 0) {  // CYCLE: reported here, skipped below
+            a.assign[cb + o] = FP_NONE;
+            a.reason[cb + o] = (uint8_t)FP_REASON_CYCLE;
+        }
+    };
+    gather(lane, ld_ord(lane));
+    uint32_t o_next = ld_ord(64u + lane);
+
+    for (uint32_t i0 = 0; i0 < C; i0 += 64u) {
+        const uint32_t c_cpu = r_cpu, c_mem = r_mem, c_req = r_req, c_conf = r_conf, c_idx = r_idx;
+        if (i0 + 64u < C) {  // the next chunk's records and the order of the one after it
+            gather(i0 + 64u + lane, o_next);
+            o_next = ld_ord(i0 + 128u + lane);
+        }
+        const uint32_t nu = C - i0 < 64u ? C - i0 : 64u;
+        for (uint32_t u = 0; u < nu; ++u) {
+            const uint32_t idx = bcast(c_idx, u);
+            if (idx == FP_NONE) { ++rejected; continue; }  // CYCLE (uniform)
+            const uint32_t cpu = bcast(c_cpu, u), mem = bcast(c_mem, u), req = bcast(c_req, u), conf = bcast(c_conf, u);
+
+            // ---- this thread's min key ----
+            uint64_t best = KEY_NONE;
+            auto local_min = [&](auto strat_c) {
+                constexpr uint32_t ST = decltype(strat_c)::value;
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    // a slot row past N holds no node (uniform): N = 5000 evaluates 5 of K = 8 rows.
+                    // The kernel is bound by VALU issue (4 waves a SIMD, ~18 instructions a node)
+                    if (K > 1 && (uint32_t)BLK * j >= N) break;
+                    const bool ok = ((sched >> j) & 1u) && fpd::fits(cpu, mem, req, conf, cf[j], mf[j], lab[j], cu[j]);
+                    const uint32_t prim = ST == FP_STRATEGY_SPREAD        ? cnt[j]
+                                          : ST == FP_STRATEGY_PACK        ? cf[j] - cpu
+                                          : ST == FP_STRATEGY_FILL_LOWEST ? ~cf[j]
+                                                                          : 0u;
+                    const uint32_t hi = pmh[j] | (prim >> (32 - KEY_NODE_BITS));
+                    const uint32_t lo = (prim << KEY_NODE_BITS) | (t + (uint32_t)BLK * j);
+                    const uint64_t key = ((uint64_t)hi << 32) | lo;
+                    best = min64(best, ok ? key : KEY_NONE);
+                }
+            };
+            switch (strat) {  // uniform
+            case FP_STRATEGY_SPREAD: local_min(std::integral_constant<uint32_t, FP_STRATEGY_SPREAD>{}); break;
+            case FP_STRATEGY_PACK: local_min(std::integral_constant<uint32_t, FP_STRATEGY_PACK>{}); break;
+            case FP_STRATEGY_FILL_LOWEST: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FILL_LOWEST>{}); break;
+            default: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FIRST_FIT>{}); break;
+            }
+
+            // ---- wave min, then block min over the per-wave slots ----
+            best = wave_min64(best);
+            if (NW > 1) {
+                static_assert(NW == 1 || NW == 16, "one slot per lane of a 16-lane row");
+                if (lane == 0) slot[par][w] = best;
+                __syncthreads();
+                best = row_min64(slot[par][lane & (NW - 1)]);  // every row of 16 lanes holds all 16 slots
+                par ^= 1u;
+            }
+
+            // ---- the winner ----
+            const bool placed = best != KEY_NONE;
+            const uint32_t n = (uint32_t)best & ((1u << KEY_NODE_BITS) - 1u);
+            if (placed && (n & (uint32_t)(BLK - 1)) == t) {
+                const uint32_t J = n / (uint32_t)BLK;
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    if ((uint32_t)j == J) {
+                        cf[j] -= cpu;
+                        mf[j] -= mem;
+                        cu[j] |= conf;
+                        cnt[j] += 1u;
+                        touched |= 1u << j;
+                    }
+                }
+            }
+            if (!placed) ++rejected;
+            if (t == 0) {
+                a.assign[cb + idx] = placed ? n : FP_NONE;
+                a.reason[cb + idx] = (uint8_t)(placed ? FP_REASON_OK : FP_REASON_NOFIT);
+            }
+        }
+    }
+
+    // ---- final node state, cost ----
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const uint32_t n = t + (uint32_t)BLK * j;
+        if (n < N && ((touched >> j) & 1u)) {
+            a.cpu_free[nb + n] = cf[j];
+            a.mem_free[nb + n] = mf[j];
+            a.conflict_used[nb + n] = cu[j];
+            if (a.node_count) a.node_count[nb + n] = cnt[j];
+        }
+    }
+    if (a.cost) {
+        uint32_t used = (uint32_t)__popc(touched);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) used += (uint32_t)__shfl_xor((int)used, o);
+        if (NW > 1) {
+            __shared__ uint32_t usedw[NW];
+            if (lane == 0) usedw[w] = used;
+            __syncthreads();
+            used = 0;
+#pragma unroll
+            for (uint32_t ww = 0; ww < NW; ++ww) used += usedw[ww];
+        }
+        if (t == 0) a.cost[s] = fpd::pack_cost(rejected, used, a.scen_base + s);
+    }
+}
+
+static inline unsigned grid_for(size_t n, unsigned block) {
+    size_t g = (n + block - 1) / block;
+    if (g > 65535u * 4) g = 65535u * 4;
+    return (unsigned)(g ? g : 1);
+}
+
+// the sorts' scratch bytes for S scenarios of C containers
+int policy_sort_tmp(hipStream_t st, uint32_t S, size_t SC, size_t *bytes) {
+    size_t t = 0;
+    if (S == 1) {
+        FP_HIP(rocprim::radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                         (uint32_t *)nullptr, SC, 0, 64, st));
+    } else {
+        FP_HIP(rocprim::segmented_radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr,
+                                                   (uint32_t *)nullptr, (uint32_t *)nullptr, (unsigned)SC, S,
+                                                   (uint32_t *)nullptr, (uint32_t *)nullptr, 0, 64, st));
+    }
+    *bytes = t;
+    return FP_OK;
+}
+
+}  // namespace
+
+int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
+                                   uint32_t *node_count) {
+    const uint32_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
+    // this call resets the arena the last first-fit call's range words live in (fp_ctx_place_path)
+    c->last_rng = nullptr;
+    if (S == 0) return FP_OK;
+    if (!strategy) return FP_EINVAL;
+    if ((uint64_t)b->scen_base + S > 65536ull) return FP_EOVERFLOW;  // SPEC.md 2.4: 16-bit scenario id
+    if (N > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
+    const size_t SC = (size_t)S * C;
+    if (SC > 0xFFFFFFFFull) return FP_EOVERFLOW;  // rocprim segmented sort takes u32 sizes
+    if (C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign || !b->reason)) return FP_EINVAL;
+    if (C && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable)) return FP_EINVAL;
+    hipStream_t st = c->stream;
+
+    size_t sort_tmp = 0;
+    if (C)
+        if (int rc = policy_sort_tmp(st, S, SC, &sort_tmp)) return rc;
+    const size_t need = SC * (8 * 2 + 4 * 2) + ((size_t)S + 1) * 4 + sort_tmp + 16 + 8 * 256;
+    if (int rc = fp_ws_reserve(c, need)) return rc;
+    fp_ws_reset(c);
+    uint32_t *bad = (uint32_t *)fp_ws_take(c, 4);
+    if (!bad) return FP_ENOMEM;
+    k_policy_check<<<1, 256, 0, st>>>(strategy, S, bad, c->d_err);
+    FP_HIP(hipGetLastError());
+    if (C == 0) {  // nothing to place: every scenario costs (0 rejected, 0 nodes used)
+        if (b->cost) {
+            k_policy_fill_cost<<<(S + 255) / 256, 256, 0, st>>>(S, b->scen_base, bad, b->cost);
+            FP_HIP(hipGetLastError());
+        }
+        return FP_OK;
+    }
+    uint64_t *keys_in = (uint64_t *)fp_ws_take(c, SC * 8);
+    uint64_t *keys_out = (uint64_t *)fp_ws_take(c, SC * 8);
+    uint32_t *vals_in = (uint32_t *)fp_ws_take(c, SC * 4);
+    uint32_t *vals_out = (uint32_t *)fp_ws_take(c, SC * 4);
+    uint32_t *offs = (uint32_t *)fp_ws_take(c, ((size_t)S + 1) * 4);
+    void *tmp = fp_ws_take(c, sort_tmp + 16);
+    if (!keys_in || !keys_out || !vals_in || !vals_out || !offs || !tmp) return FP_ENOMEM;
+
+    // ---- FFD order ----
+    hipEvent_t ev;
+    fp_prof_begin(c, FP_K_SORT, &ev);
+    k_policy_keys<<<grid_for(SC, 256), 256, 0, st>>>(b->cpu_m, b->mem_mib, SC, C, keys_in, vals_in);
+    FP_HIP(hipGetLastError());
+    if (S == 1) {
+        FP_HIP(rocprim::radix_sort_pairs(tmp, sort_tmp, keys_in, keys_out, vals_in, vals_out, SC, 0, 64, st));
+    } else {
+        k_policy_offsets<<<(S + 1 + 255) / 256, 256, 0, st>>>(S, C, offs);
+        FP_HIP(hipGetLastError());
+        FP_HIP(rocprim::segmented_radix_sort_pairs(tmp, sort_tmp, keys_in, keys_out, vals_in, vals_out, (unsigned)SC, S,
+                                                   offs, offs + 1, 0, 64, st));
+    }
+    fp_prof_end(c, FP_K_SORT, ev);
+
+    // ---- placement ----
+    PolicyArgs a;
+    a.C = C; a.N = N; a.scen_base = b->scen_base;
+    a.order = vals_out;
+    a.cpu = b->cpu_m; a.mem = b->mem_mib; a.req = b->req_labels; a.conf = b->conflict;
+    a.level = b->level;
+    a.cpu_free = b->cpu_free; a.mem_free = b->mem_free; a.conflict_used = b->conflict_used;
+    a.labels = b->labels; a.schedulable = b->schedulable;
+    a.node_count = node_count;
+    a.strategy = strategy; a.preferred = preferred;
+    a.assign = b->assign; a.reason = b->reason; a.cost = b->cost;
+    a.bad = bad;
+    fp_prof_begin(c, FP_K_PLACE, &ev);
+    if (N <= 64) k_policy<64, 1><<<S, 64, 0, st>>>(a);
+    else if (N <= 1024) k_policy<1024, 1><<<S, 1024, 0, st>>>(a);
+    else if (N <= 2048) k_policy<1024, 2><<<S, 1024, 0, st>>>(a);
+    else if (N <= 4096) k_policy<1024, 4><<<S, 1024, 0, st>>>(a);
+    else k_policy<1024, 8><<<S, 1024, 0, st>>>(a);
+    FP_HIP(hipGetLastError());
+    fp_prof_end(c, FP_K_PLACE, ev);
+    return FP_OK;
+}

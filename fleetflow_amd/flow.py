@@ -84,14 +84,40 @@ class Service:
         self.environment.update(other.environment)
 
 
+POLICY_STRATEGIES = ("spread_across_pool", "pack_into_dedicated", "fill_lowest")
+
+
+@dataclass
+class PlacementPolicy:
+    """The tenant PlacementPolicy subset the planner reads (controlplane model.rs:56-95): one of the
+    three strategy constants (None = first fit) and the soft ``preferred_labels`` map.
+    SpreadConstraint, fallback_policy and resource_quota are not read."""
+    strategy: str | None = None
+    preferred_labels: dict[str, str] = field(default_factory=dict)
+
+    def __post_init__(self):
+        if self.strategy is not None and self.strategy not in POLICY_STRATEGIES:
+            raise ValueError(f"unknown placement strategy '{self.strategy}' (expected {'|'.join(POLICY_STRATEGIES)})")
+
+    @property
+    def preferred(self) -> list[str]:
+        """The preferred labels as the ``key=value`` strings of ``LabelDict``."""
+        return [f"{k}={v}" for k, v in sorted(self.preferred_labels.items())]
+
+    @property
+    def active(self) -> bool:
+        return self.strategy is not None or bool(self.preferred_labels)
+
+
 @dataclass
 class Stage:
-    """fleetflow_core::Stage (model/stage.rs:48-64)."""
+    """fleetflow_core::Stage (model/stage.rs:48-64), plus the SPEC.md 4 ``placement`` node."""
     services: list[str] = field(default_factory=list)
     servers: list[str] = field(default_factory=list)
     variables: dict[str, str] = field(default_factory=dict)
     registry: str | None = None
     backend: str = "docker"
+    placement: PlacementPolicy | None = None
 
 
 @dataclass
@@ -229,6 +255,9 @@ class Plan:
     # stage 2 on the stage's pristine server table: service -> (feasible servers, first feasible
     # slug or None); count 0 is an exact NOFIT before placement (SPEC.md 2.3 monotonicity)
     candidates: dict[str, tuple[int, str | None]] = field(default_factory=dict)
+    # the placement strategy the assignment was made under (SPEC.md 2.6); None = first fit
+    strategy: str | None = None
+    preferred: list[str] = field(default_factory=list)
 
 
 def _server_nodes(flow: Flow, servers: list[str]):
@@ -238,12 +267,18 @@ def _server_nodes(flow: Flow, servers: list[str]):
     return out
 
 
-def _stage_tables(names: list[str], flow: Flow, nodes: list[Server]):
+def _stage_labels(names: list[str], flow: Flow, nodes: list[Server], preferred=()) -> LabelDict:
+    """The stage's label dictionary: required, server and (soft) preferred labels."""
+    svcs = [flow.services.get(n, Service()) for n in names]
+    return LabelDict([lab for s in svcs for lab in s.labels] + [lab for nd in nodes for lab in nd.labels]
+                     + list(preferred))
+
+
+def _stage_tables(names: list[str], flow: Flow, nodes: list[Server], preferred=()):
     """The stage's services (vertex order) and servers as the SoA tables of the C ABI: label,
     host-port and anti-affinity bit dictionaries (SPEC.md 4)."""
     svcs = [flow.services.get(n, Service()) for n in names]
-    all_labels = [lab for s in svcs for lab in s.labels] + [lab for nd in nodes for lab in nd.labels]
-    ld = LabelDict(all_labels)
+    ld = _stage_labels(names, flow, nodes, preferred)
     ports = sorted({hp for s in svcs for hp in s.host_ports})
     groups = sorted({s.anti_affinity for s in svcs if s.anti_affinity})
     if len(ports) > 16 or len(groups) > 16:
@@ -270,15 +305,23 @@ def _stage_tables(names: list[str], flow: Flow, nodes: list[Server]):
 
 
 def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
-               servers: list[Server] | None = None) -> Plan:
+               servers: list[Server] | None = None, policy: PlacementPolicy | None = None) -> Plan:
     """Full planner output for one stage (SPEC.md 2): the `fleet up --dry-run`
     plan (up.rs:57-136).  One fp_plan_stage call -- A1 order, A2 levels, and with servers the stage-2
     candidates and the FFD plan -- when every service name appears once in the stage; a stage
-    listing a name twice (positions != vertices) takes the per-output calls."""
+    listing a name twice (positions != vertices) takes the per-output calls.
+
+    ``policy`` (or, without one, the stage's parsed ``placement`` node) selects a placement strategy
+    and soft preferred labels (SPEC.md 2.6): levels, orders and candidates are computed as without
+    one, and the assignment comes from ``Planner.place_policy``.  No policy, or one that sets
+    nothing: exactly the path above."""
     p = planner or default_planner()
     stage = flow.stages[stage_name]
     services = list(stage.services)
     nodes = servers if servers is not None else _server_nodes(flow, stage.servers)
+    pol = policy if policy is not None else stage.placement
+    if pol is not None and not pol.active:
+        pol = None
     assignment, rejected, candidates = {}, {}, {}
     if not services:
         return Plan(stage_name, [], {}, [], assignment, rejected, candidates)
@@ -307,6 +350,14 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
             first, count, _ = p.feasibility(cont, ntab, bitmap=False)
             assign, reason, _ = p.place(cont, ntab, level=[lvl_v[n] for n in names])
             placed = (first, count, assign, reason, None)
+    if placed is not None and pol is not None:
+        # the scored placer on the same tables; the preferred labels share the stage's dictionary
+        lvl_v = dict(zip(services, levels))
+        cont, ntab = _stage_tables(names, flow, nodes, pol.preferred)
+        pmask = _stage_labels(names, flow, nodes, pol.preferred).mask(pol.preferred)
+        assign, reason, _, _ = p.place_policy(cont, ntab, pol.strategy if pol.strategy is not None else 0,
+                                              preferred=pmask, level=[lvl_v[n] for n in names])
+        placed = (placed[0], placed[1], assign, reason, None)
     if placed is not None:
         first, count, assign, reason, _ = placed
         candidates = {n: (int(count[v]), nodes[int(first[v])].slug if int(first[v]) != NONE else None)
@@ -316,7 +367,10 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
                 assignment[n] = nodes[assign[v]].slug
             else:
                 rejected[n] = "CYCLE" if reason[v] == 2 else "NOFIT"
-    return Plan(stage_name, order, dict(zip(services, levels)), level_order, assignment, rejected, candidates)
+    plan = Plan(stage_name, order, dict(zip(services, levels)), level_order, assignment, rejected, candidates)
+    if placed is not None and pol is not None:
+        plan.strategy, plan.preferred = pol.strategy, pol.preferred
+    return plan
 
 
 def resolve_target_server(flow: Flow, stage_name: str, planner: Planner | None = None) -> str | None:

@@ -18,7 +18,7 @@ import os
 import re
 
 from . import kdl
-from .flow import U32_MAX, Flow, Port, Server, Service, Stage, Volume
+from .flow import POLICY_STRATEGIES, U32_MAX, Flow, PlacementPolicy, Port, Server, Service, Stage, Volume
 from .kdl import as_int, as_str
 
 
@@ -165,7 +165,30 @@ def parse_stage(node) -> tuple[str, Stage, dict[str, Service]]:
             if raw.lower() not in ("docker", "quadlet", "compose"):
                 raise FlowError(f"unknown backend '{raw}' (expected docker|quadlet|compose)")
             st.backend = raw.lower()
+        # ---- SPEC.md 4: placement policy (the reference skips unknown stage children, stage.rs:87) ----
+        elif ch.name == "placement":
+            st.placement = parse_placement(ch, name)
     return name, st, overrides
+
+
+def parse_placement(node, stage_name: str) -> PlacementPolicy:
+    """``placement strategy="spread_across_pool" { prefer "region=tokyo" }``: the tenant
+    PlacementPolicy's strategy constant and soft preferred labels (controlplane model.rs:56-95)."""
+    strategy = None
+    if node.has("strategy"):
+        strategy = as_str(node.get("strategy"))
+        if strategy not in POLICY_STRATEGIES:
+            raise FlowError(f"stage {stage_name}: unknown placement strategy {node.get('strategy')!r} "
+                            f"(expected {'|'.join(POLICY_STRATEGIES)})")
+    preferred: dict[str, str] = {}
+    for ch in node.children or []:
+        if ch.name == "prefer":
+            for _, v in ch.entries:
+                if not isinstance(v, str) or "=" not in v:
+                    raise FlowError(f"stage {stage_name}: prefer takes \"key=value\" labels, got {v!r}")
+                k, val = v.split("=", 1)
+                preferred[k] = val
+    return PlacementPolicy(strategy, preferred)
 
 
 # ---- parser/cloud.rs:46-140 (+ SPEC.md 4 capacity/labels/scheduling) ------------------------

@@ -24,7 +24,7 @@ from .parser import FlowError
 
 def plan_to_json(plan: Plan, indent: int | None = None) -> str:
     """Serialise a plan; a cycle member's level is null (it was U32_MAX)."""
-    return json.dumps({
+    d = {
         "stage": plan.stage,
         "order": plan.order,
         "levels": {k: (None if v == U32_MAX else v) for k, v in plan.levels.items()},
@@ -32,14 +32,19 @@ def plan_to_json(plan: Plan, indent: int | None = None) -> str:
         "assign": plan.assignment,
         "rejected": plan.rejected,
         "candidates": {k: {"count": c, "first": f} for k, (c, f) in plan.candidates.items()},
-    }, ensure_ascii=False, indent=indent)
+    }
+    if plan.strategy is not None or plan.preferred:  # a plan made under a placement policy (SPEC.md 2.6)
+        d["placement"] = {"strategy": plan.strategy, "preferred": plan.preferred}
+    return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
 def plan_from_json(text: str) -> Plan:
     d = json.loads(text)
+    pol = d.get("placement") or {}
     return Plan(d["stage"], d["order"], {k: (U32_MAX if v is None else v) for k, v in d["levels"].items()},
                 d["level_order"], d["assign"], d["rejected"],
-                {k: (v["count"], v["first"]) for k, v in d.get("candidates", {}).items()})
+                {k: (v["count"], v["first"]) for k, v in d.get("candidates", {}).items()},
+                pol.get("strategy"), list(pol.get("preferred") or []))
 
 
 def get_network_name(project: str, stage: str) -> str:
@@ -85,11 +90,22 @@ def _service_block(flow: Flow, stage: str, name: str, container_suffix: str, pla
 _FOOTER = "[dry-run] 実際の操作は行われません。--dry-run を外して実行してください。"
 
 
+def _policy_lines(plan: Plan | None) -> list[str]:
+    """The placement strategy a plan was made under (SPEC.md 2.6); nothing without one."""
+    if plan is None or (plan.strategy is None and not plan.preferred):
+        return []
+    line = f"  配置戦略: {plan.strategy if plan.strategy is not None else 'first_fit'}"
+    if plan.preferred:
+        line += f" (優先ラベル: {', '.join(plan.preferred)})"
+    return [line]
+
+
 def format_up_dry_run(flow: Flow, stage_name: str, plan: Plan | None = None) -> str:
     """up.rs:57-136 (``print_dry_run_plan``) over ``stage.services``."""
     stage = flow.stages[stage_name]
     lines = [f"[dry-run] ステージ '{stage_name}' の起動計画:", "",
              f"  ネットワーク: {get_network_name(flow.name, stage_name)} (作成予定)"]
+    lines += _policy_lines(plan)
     for name in stage.services:
         lines += _service_block(flow, stage_name, name, "", plan)
     lines += ["", _FOOTER]
@@ -103,6 +119,7 @@ def format_deploy_dry_run(flow: Flow, stage_name: str, target_services: list[str
     (deploy.rs:475-485)."""
     lines = [f"[dry-run] ステージ '{stage_name}' のデプロイ計画:", "", f"  テナント: {tenant_line}", "",
              f"  ネットワーク: {get_network_name(flow.name, stage_name)} (作成予定)"]
+    lines += _policy_lines(plan)
     for name in target_services:
         lines += _service_block(flow, stage_name, name, " (停止・削除→再作成)", plan)
     lines += ["", _FOOTER]

@@ -30,6 +30,18 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def strategy_id(strategy) -> int:
+    """An fp_strategy value from an int or one of the control plane's policy strings
+    (``spread_across_pool``, ``pack_into_dedicated``, ``fill_lowest``).  An int is passed on as it is
+    (the library refuses values that are no fp_strategy); an unknown string is a ValueError."""
+    if isinstance(strategy, str):
+        if strategy not in _lib.POLICY_STRATEGIES:
+            raise ValueError(f"unknown placement strategy '{strategy}' (expected "
+                             + "|".join(_lib.POLICY_STRATEGIES) + ")")
+        return _lib.POLICY_STRATEGIES[strategy]
+    return int(strategy)
+
+
 class Planner:
     def __init__(self, device: int = 0):
         self._L = _lib.load()
@@ -260,6 +272,57 @@ class Planner:
         check(self._L.fp_place_batch(self._ctx, ct.byref(b)), "fp_place_batch")
         return assign, reason, cost, (cf, mf, lab, cu, sched)
 
+    def place_policy(self, cont, nodes, strategy, preferred=0, level=None, node_count=None):
+        """Scored placement (SPEC.md 2.6, fp_place_policy): ``strategy`` is an fp_strategy value or one
+        of the control plane's policy strings, ``preferred`` the soft preferred-label mask,
+        ``node_count`` the containers already on each node (None = zero).  Inputs are not mutated.
+        Returns (assign, reason, nodes_after, node_count_after); the last is None without node_count."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
+        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
+        C, N = cpu.size, cf.size
+        lv = _u32(level) if level is not None else None
+        nc = _u32(node_count).copy() if node_count is not None else None
+        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
+        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
+        self._need(lv is None or lv.size == C, "level must hold C entries")
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        assign = np.empty(C, np.uint32)
+        reason = np.empty(C, np.uint8)
+        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
+        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
+        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        check(self._L.fp_place_policy(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
+                                      int(preferred) & 0xFFFFFFFF, p32(nc), p32(assign),
+                                      reason.ctypes.data_as(_lib.u8p)), "fp_place_policy")
+        return assign, reason, (cf, mf, lab, cu, sched), nc
+
+    def place_batch_policy(self, S, C, N, cont, nodes, strategy, preferred=None, level=None, node_count=None,
+                           scen_base=0):
+        """place_batch under per-scenario strategies ([S] ints or policy strings), preferred-label masks
+        ([S] or None) and node counts ([S*N] or None).  Returns (assign, reason, cost, nodes_after,
+        node_count_after)."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
+        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
+        lv = _u32(level) if level is not None else None
+        st = _u32([strategy_id(x) for x in strategy])
+        pf = _u32(preferred) if preferred is not None else None
+        nc = _u32(node_count).copy() if node_count is not None else None
+        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
+        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
+        self._need(lv is None or lv.size == S * C, "level must hold S * C entries")
+        self._need(st.size == S and (pf is None or pf.size == S), "strategy and preferred must hold S entries")
+        self._need(nc is None or nc.size == S * N, "node_count must hold S * N entries")
+        assign = np.empty(S * C, np.uint32)
+        reason = np.empty(S * C, np.uint8)
+        cost = np.empty(S, np.uint64)
+        b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
+                    _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
+        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        check(self._L.fp_place_batch_policy(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc)), "fp_place_batch_policy")
+        return assign, reason, cost, (cf, mf, lab, cu, sched), nc
+
     def feasibility(self, cont, nodes, bitmap=True):
         cpu, mem, req, conf = (_u32(x) for x in cont)
         cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
@@ -282,6 +345,17 @@ class Planner:
 
     def dev_place_batch(self, db: "DevBatch"):
         self._dev(lambda: check(self._L.fp_dev_place_batch(self._ctx, ct.byref(db.struct())), "fp_dev_place_batch"))
+
+    def dev_place_batch_policy(self, db: "DevBatch", strategy_t, preferred_t=None, count_t=None):
+        """fp_dev_place_batch_policy: ``strategy_t`` [S] (int32 storage of fp_strategy values),
+        ``preferred_t`` [S] or None, ``count_t`` [S*N] in/out or None -- device tensors."""
+        self._need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
+        self._need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
+        self._need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._dev(lambda: check(self._L.fp_dev_place_batch_policy(self._ctx, ct.byref(db.struct()), p(strategy_t),
+                                                                  p(preferred_t), p(count_t)),
+                                "fp_dev_place_batch_policy"))
 
     def dev_argmin_cost(self, cost_t, out_t):
         self._dev(lambda: check(self._L.fp_dev_argmin_cost(self._ctx, cost_t.data_ptr(), cost_t.numel(),

@@ -19,7 +19,7 @@ that slug order. The conversion is SPEC.md 4:
 """
 from __future__ import annotations
 
-from .flow import U32_MAX, Server
+from .flow import POLICY_STRATEGIES, U32_MAX, PlacementPolicy, Server
 
 SCHEDULABLE, CORDON, DRAIN = "schedulable", "cordon", "drain"
 
@@ -89,6 +89,21 @@ def node_table(rows: list[dict]) -> list[Server]:
     """db.rs:741-750: live rows (``deleted_at`` None) in slug order."""
     live = [r for r in rows if r.get("deleted_at") is None]
     return [server_from_row(r) for r in sorted(live, key=lambda r: r["slug"])]
+
+
+def placement_policy(tenant_row: dict | None) -> PlacementPolicy | None:
+    """A tenant row's ``placement_policy`` (as JSON; model.rs:82-95) -> the planner's policy: its
+    ``strategy`` constant and soft ``preferred_labels`` map.  None when the row has no policy; a
+    strategy that is none of the three constants is a ValueError.  ``spread_constraint``,
+    ``fallback_policy`` and ``resource_quota`` are not read."""
+    pol = (tenant_row or {}).get("placement_policy")
+    if pol is None:
+        return None
+    strategy = pol.get("strategy")
+    if strategy is not None and strategy not in POLICY_STRATEGIES:
+        raise ValueError(f"unknown placement strategy {strategy!r} (expected {'|'.join(POLICY_STRATEGIES)})")
+    pref = pol.get("preferred_labels") or {}
+    return PlacementPolicy(strategy, {str(k): str(v) for k, v in pref.items()})
 
 
 def pool_required_labels(pool: dict | None) -> list[str]:

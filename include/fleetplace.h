@@ -14,6 +14,8 @@
  *                        crates/fleetflow-controlplane/src/handlers/deploy.rs:386-398
  *                        (N = 1, unconstrained capacity reproduces it exactly)
  *   fp_place_batch    <- new: what-if scenarios, one plan per scenario + packed cost
+ *   fp_place_policy   <- new: fp_place under the tenant PlacementPolicy's strategy and preferred labels
+ *                        crates/fleetflow-controlplane/src/model.rs:56-95 (schema nothing reads upstream)
  *   fp_feasibility    <- new: stage-2 containers x nodes feasibility/score sweep
  *   fp_dev_feasibility_batch <- new: the same sweep over many what-if scenarios
  *
@@ -192,6 +194,25 @@ int fp_levelize(fp_ctx *ctx, const fp_graph *g, uint32_t *level_out, uint32_t *o
 int fp_place(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32_t *level,
              uint32_t *assign_out, uint8_t *reason_out);
 int fp_place_batch(fp_ctx *ctx, const fp_batch *b);
+/* Scored placement (SPEC.md 2.6): containers in the FFD order of fp_place, same feasibility predicate
+ * and CYCLE gating; among the feasible nodes the container goes to the one with the smallest key
+ *   popcount(preferred_labels & ~labels[n]) << 58 | primary(n) << 26 | n
+ * with primary(n) = 0 (FIRST_FIT), node_count[n] (SPREAD, `spread_across_pool`), cpu_free[n] - cpu_m
+ * (PACK, `pack_into_dedicated`: best fit on CPU) or 0xFFFFFFFF - cpu_free[n] (FILL_LOWEST,
+ * `fill_lowest`: most free CPU first); the strategies of the control plane's PlacementPolicy
+ * (crates/fleetflow-controlplane/src/model.rs:56-95).  FIRST_FIT with preferred_labels = 0 is fp_place.
+ * node_count ([N], or [S][N] for a batch; nullable) holds the containers already on each node and is
+ * updated in place; NULL starts at zero and returns nothing.  The cost counts the nodes that received a
+ * container in this call.  At most FP_POLICY_MAX_NODES nodes per scenario (FP_EOVERFLOW); a strategy
+ * above FP_STRATEGY_FILL_LOWEST is FP_EINVAL. */
+enum fp_strategy { FP_STRATEGY_FIRST_FIT = 0, FP_STRATEGY_SPREAD = 1, FP_STRATEGY_PACK = 2, FP_STRATEGY_FILL_LOWEST = 3 };
+#define FP_POLICY_MAX_NODES 8192
+int fp_place_policy(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32_t *level,
+                    uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                    uint32_t *assign_out, uint8_t *reason_out);
+/* strategy, preferred_labels: [S] per scenario (preferred_labels nullable = 0) */
+int fp_place_batch_policy(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                          const uint32_t *preferred_labels, uint32_t *node_count);
 /* Stage 2: first feasible node (FP_NONE) and feasible-node count per container on
  * the given node state; bitmap_out (nullable, ceil(C/64) * N words) holds
  * bit (c, n) at word [(c/64) * N + n], bit c % 64. */
@@ -236,6 +257,11 @@ int fp_dev_feasibility(fp_ctx *ctx, const fp_containers *c, const fp_nodes *node
  * lowest feasible node (FP_NONE if none) and count_out[s*C + c] = the number of feasible
  * nodes.  n_scen <= 65535. */
 int fp_dev_feasibility_batch(fp_ctx *ctx, const fp_batch *b, uint32_t *first_out, uint32_t *count_out);
+/* As fp_place_batch_policy on device pointers (strategy, preferred_labels and node_count included).
+ * A strategy value that is no fp_strategy is found on the device: nothing is written and
+ * fp_ctx_sync() reports FP_EINVAL. */
+int fp_dev_place_batch_policy(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                              const uint32_t *preferred_labels, uint32_t *node_count);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

@@ -15,6 +15,11 @@ pub const FP_NONE: u32 = 0xFFFF_FFFF;
 pub const FP_REASON_OK: u8 = 0;
 pub const FP_REASON_NOFIT: u8 = 1;
 pub const FP_REASON_CYCLE: u8 = 2;
+pub const FP_STRATEGY_FIRST_FIT: u32 = 0;
+pub const FP_STRATEGY_SPREAD: u32 = 1;
+pub const FP_STRATEGY_PACK: u32 = 2;
+pub const FP_STRATEGY_FILL_LOWEST: u32 = 3;
+pub const FP_POLICY_MAX_NODES: u32 = 8192;
 pub const FP_K_PLACE: c_int = 0;
 pub const FP_K_SORT: c_int = 1;
 pub const FP_K_FEAS: c_int = 2;
@@ -136,6 +141,13 @@ unsafe extern "C" {
     pub fn fp_place(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
                     assign_out: *mut u32, reason_out: *mut u8) -> c_int;
     pub fn fp_place_batch(ctx: *mut fp_ctx, b: *const fp_batch) -> c_int;
+    pub fn fp_place_policy(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
+                           strategy: u32, preferred_labels: u32, node_count: *mut u32, assign_out: *mut u32,
+                           reason_out: *mut u8) -> c_int;
+    pub fn fp_place_batch_policy(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                 preferred_labels: *const u32, node_count: *mut u32) -> c_int;
+    pub fn fp_dev_place_batch_policy(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                     preferred_labels: *const u32, node_count: *mut u32) -> c_int;
     pub fn fp_feasibility(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, first_out: *mut u32,
                           count_out: *mut u32, bitmap_out: *mut u64) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,

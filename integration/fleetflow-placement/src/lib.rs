@@ -106,6 +106,34 @@ impl Planner {
         Ok((assign, reason))
     }
 
+    /// Scored placement (SPEC.md 2.6, fleetplace.h `fp_place_policy`): `strategy` is one of
+    /// `ffi::FP_STRATEGY_*`, `preferred_labels` the soft preferred-label mask, `node_count` the
+    /// containers already on each node (updated in place; None starts at zero).  `nodes` is
+    /// updated in place.  At most `ffi::FP_POLICY_MAX_NODES` nodes (FP_EOVERFLOW).
+    pub fn place_policy(&mut self, c: &Containers, nodes: &mut Nodes, level: Option<&[u32]>, strategy: u32,
+                        preferred_labels: u32, node_count: Option<&mut [u32]>)
+                        -> Result<(Vec<u32>, Vec<u8>), PlanError> {
+        let n = c.cpu_m.len();
+        let nn = nodes.cpu_free.len();
+        if !c.all_len(n) || !nodes.all_len(nn) || level.map_or(false, |l| l.len() != n)
+            || node_count.as_ref().map_or(false, |k| k.len() != nn) {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        let mut ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_mut_ptr(),
+                                     mem_free: nodes.mem_free.as_mut_ptr(), labels: nodes.labels.as_ptr(),
+                                     conflict_used: nodes.conflict_used.as_mut_ptr(),
+                                     schedulable: nodes.schedulable.as_ptr() };
+        let (mut assign, mut reason) = (vec![0u32; n], vec![0u8; n]);
+        let count_ptr = node_count.map_or(std::ptr::null_mut(), |k| k.as_mut_ptr());
+        check(unsafe {
+            ffi::fp_place_policy(self.ctx, &cs, &mut ns, level.map_or(std::ptr::null(), |l| l.as_ptr()),
+                                 strategy, preferred_labels, count_ptr, assign.as_mut_ptr(), reason.as_mut_ptr())
+        })?;
+        Ok((assign, reason))
+    }
+
     /// One stage's whole dry-run plan in one call (fleetplace.h `fp_plan_stage`, the
     /// `fleet up --dry-run` path of up.rs:57-136): the legacy order, the Kahn levels and start
     /// order and, with `placement = Some((containers, nodes))` (container v = vertex v), the
@@ -450,6 +478,32 @@ pub fn place_stage(flow: &Flow, stage_name: &str, c: &Containers, nodes: &mut No
         return Err(PlanError(ffi::FP_EINVAL));
     }
     let (assign, _) = with_planner(|p| p.place(c, nodes, None))?;
+    Ok(assign.iter().map(|&a| if a == ffi::FP_NONE { None } else { Some(stage.servers[a as usize].clone()) }).collect())
+}
+
+/// `fp_strategy` of a tenant `PlacementPolicy.strategy` string
+/// (crates/fleetflow-controlplane/src/model.rs:56-95); None for anything else.
+pub fn strategy_from_policy(strategy: &str) -> Option<u32> {
+    match strategy {
+        "spread_across_pool" => Some(ffi::FP_STRATEGY_SPREAD),
+        "pack_into_dedicated" => Some(ffi::FP_STRATEGY_PACK),
+        "fill_lowest" => Some(ffi::FP_STRATEGY_FILL_LOWEST),
+        _ => None,
+    }
+}
+
+/// `place_stage` under a placement strategy (SPEC.md 2.6): the same tables, the server chosen by the
+/// strategy's key among the feasible ones instead of the first.  `preferred_labels` is the soft
+/// preferred-label mask in the stage's label dictionary; `node_count` the containers already on each
+/// server (None = none).
+pub fn place_stage_with_policy(flow: &Flow, stage_name: &str, c: &Containers, nodes: &mut Nodes, strategy: u32,
+                               preferred_labels: u32, node_count: Option<&mut [u32]>)
+                               -> Result<Vec<Option<String>>, PlanError> {
+    let Some(stage) = flow.stages.get(stage_name) else { return Err(PlanError(ffi::FP_EINVAL)) };
+    if nodes.cpu_free.len() != stage.servers.len() || c.cpu_m.len() != stage.services.len() {
+        return Err(PlanError(ffi::FP_EINVAL));
+    }
+    let (assign, _) = with_planner(|p| p.place_policy(c, nodes, None, strategy, preferred_labels, node_count))?;
     Ok(assign.iter().map(|&a| if a == ffi::FP_NONE { None } else { Some(stage.servers[a as usize].clone()) }).collect())
 }
 

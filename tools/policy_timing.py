@@ -1,0 +1,106 @@
+"""Scored-placement timing (SPEC.md 2.6) on the config-4 batch shape, on cuda:0.
+
+    python tools/policy_timing.py [--scenarios S] [--containers C] [--nodes N] [--steps K] [--warmup W]
+
+Times Planner.dev_place_batch_policy per strategy on S what-if scenarios of C x N (default: the
+512-scenario slice one of eight ranks plans of config 4's 4096 x 50k x 5k; --scenarios 4096 is the
+whole batch), and the first-fit dev_place_batch on the same batch beside them.  The first-fit figure
+is there for scale only: the two kernels do different work (first fit prunes on monotonicity, a
+scored rule takes an argmin over every node for every container).
+
+Each figure is a host clock around `steps` calls that end in a device synchronise, after `warmup`
+calls, with the node state restored before each call; the placer's and the sort's own time come from
+the context's event brackets (FP_K_PLACE, FP_K_SORT) in a separate pass.  Writes
+profiles/policy_timing.json and prints it.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from fleetflow_amd import DevBatch, Planner, _lib  # noqa: E402
+
+SEED4 = 0x5EED0004
+STRATEGIES = (("first_fit_scored", 0), ("spread_across_pool", 1), ("pack_into_dedicated", 2), ("fill_lowest", 3))
+
+
+def timed(p, db, snap, call, steps, warmup):
+    """(wall ms, placer kernel ms, sort ms) per call."""
+    for _ in range(warmup):
+        db.restore_nodes(snap)
+        call()
+    p.sync()
+    torch.cuda.synchronize()
+    wall = 0.0
+    for _ in range(steps):
+        db.restore_nodes(snap)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()
+        p.sync()
+        wall += time.perf_counter() - t0
+    p.profile(True)
+    for _ in range(steps):
+        db.restore_nodes(snap)
+        call()
+    p.sync()
+    place_ms, n_place = p.kernel_stats(_lib.FP_K_PLACE)
+    sort_ms, _ = p.kernel_stats(_lib.FP_K_SORT)
+    p.profile(False)
+    return 1e3 * wall / steps, place_ms / max(n_place, 1), sort_ms / max(n_place, 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenarios", type=int, default=512)
+    ap.add_argument("--containers", type=int, default=50_000)
+    ap.add_argument("--nodes", type=int, default=5_000)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "policy_timing.json"))
+    a = ap.parse_args()
+    S, C, N = a.scenarios, a.containers, a.nodes
+    dev = torch.device("cuda", 0)
+    props = torch.cuda.get_device_properties(dev)
+    cus = props.multi_processor_count
+    out = {"shape": {"scenarios": S, "containers": C, "nodes": N, "flags": 7, "seed": SEED4}, "steps": a.steps,
+           "warmup": a.warmup, "device": props.name, "compute_units": cus, "strategies": {}}
+    with Planner(0) as p:
+        db = DevBatch.allocate(S, C, N, dev)
+        p.dev_gen_batch(SEED4, db, 7)
+        p.sync()
+        snap = db.node_snapshot()
+        wall, place_ms, sort_ms = timed(p, db, snap, lambda: p.dev_place_batch(db), a.steps, a.warmup)
+        out["first_fit_pipeline"] = {"ms_per_call": wall, "place_kernel_ms": place_ms, "sort_ms": sort_ms,
+                                     "rejected": int((db.reason != 0).sum().item())}
+        ff_assign = db.assign.clone()
+        # one 1024-thread workgroup per scenario and compute unit (N > 64; at most 4 waves per SIMD at
+        # 8 nodes a thread), so a batch takes ceil(S / CUs) rounds of C dependent placements
+        rounds = -(-S // cus) if N > 64 else None
+        for name, sid in STRATEGIES:
+            st = torch.full((S,), sid, dtype=torch.int32, device=dev)
+            wall, place_ms, sort_ms = timed(p, db, snap, lambda: p.dev_place_batch_policy(db, st), a.steps, a.warmup)
+            rec = {"ms_per_call": wall, "place_kernel_ms": place_ms, "sort_ms": sort_ms,
+                   "rejected": int((db.reason != 0).sum().item())}
+            if rounds:
+                ns = 1e6 * place_ms / (rounds * C)
+                rec["ns_per_placement"] = ns  # per workgroup: the dependent chain's step time
+                rec["cycles_per_placement_at_2400MHz"] = ns * 2.4
+            if sid == 0:  # the scored kernel under strategy 0 is first fit: the same plan
+                rec["same_plan_as_first_fit"] = bool(torch.equal(db.assign, ff_assign))
+            out["strategies"][name] = rec
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
