@@ -163,6 +163,11 @@ __device__ __forceinline__ uint32_t g_ld_u(const uint32_t *p) {  // a control wo
 __device__ __forceinline__ void g_st(uint32_t *p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// touch: an ordinary cached load whose value nothing reads (it brings the line into L2); a relaxed
+// wavefront-scope atomic load is a plain global_load that the optimiser keeps
+__device__ __forceinline__ void g_touch(const uint32_t *p) {
+    (void)__hip_atomic_load(const_cast<uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
 
 // Spin on an LDS word until pred holds; bounded, with a workgroup abort flag.
 template <class Pred>
@@ -299,6 +304,19 @@ constexpr uint32_t PF_MAX_NARROW = FPP_PF_MAX_NARROW, PF_MAX_WIDE = FPP_PF_MAX_W
 #ifndef FPP_IB1024  // ... and in the 1024-thread kernels of more than SYS_MAX_G groups: on since the mask
 #define FPP_IB1024 1  // upkeep went (512 / 1024 scenarios 4.91-4.97 / 6.15-6.20 vs 4.96-5.01 / 6.19-6.31 ms,
 #endif                // profiles/r08z_ib1024_ab.jsonl; with the upkeep round 5 measured 6.43 / 7.79 vs 6.21 / 7.58)
+// Input look-ahead of the one-wave kernels (BLK == 64; the batch loop of k_ffd_pipe):
+//  0  none: a batch's input is requested at the loop top and waited for there
+//  1  a segment fed by a global link carries the next slot's count and position words in two
+//     registers: they are requested with this batch's field gathers, so the next batch pays one
+//     round trip (the gathers) instead of two (slot, then gathers).  Only slots below a head
+//     already seen are looked at (an unpublished slot holds stale positions); no extra poll
+//  2  1, and the sorted SoA lines the next batch will read are touched (loads nothing reads)
+// Config-4 FFD, 0 against 1: 11.32-11.34 against 11.19-11.21 ms (seven alternating runs), 2048 scenarios
+// 7.66-7.72 against 7.57-7.64 ms; 0 against 2, in another call: 11.17-11.21 against 12.37-12.41 ms, 2048
+// scenarios 7.64-7.67 against 8.30-8.32 ms (profiles/r10b_lookahead_ab.jsonl).
+#ifndef FPP_LOOKAHEAD
+#define FPP_LOOKAHEAD 1
+#endif
 // the systolic group fill (fp_pipe_sys.h) is compiled for stages of at most this many groups
 constexpr uint32_t SYS_MAX_G = 4;
 // ... and the packed one (fp_pipe_pk.h) for stages of at most this many (its records take one VGPR
@@ -648,6 +666,11 @@ k_ffd_pipe(const PipeArgs a_arg) {
     uint32_t *abort_flag = &CNT[2];
     uint32_t ohead = 0, ofill = 0, itail = 0, k0 = 0;
     uint32_t ihead_seen = 0;  // last head read from the upstream link
+    // look-ahead on the input link (FPP_LOOKAHEAD): slot itail's count and position words, requested
+    // one batch early (la_ok: they were; else the loop top loads them as without look-ahead)
+    constexpr uint32_t LA = BLK == 64 ? FPP_LOOKAHEAD : 0;
+    [[maybe_unused]] uint32_t la_n = 0, la_pos = 0;
+    [[maybe_unused]] bool la_ok = false;
     // full slots written but not yet published (global link): the head store and the wait for
     // the slot stores before it (s_waitcnt vmcnt(0)) are paid once per a.publish slots; the end
     // of the stream publishes the rest
@@ -710,8 +733,14 @@ k_ffd_pipe(const PipeArgs a_arg) {
             const uint32_t *sd = gin_data + (size_t)GSLOT(itail) * LSLOT;
             // the count is wave-uniform: say so, or the loop exit below reads as divergent and every
             // loop-carried counter of the kernel is kept (and spilled) in VGPRs
-            const uint32_t n = g_ld_u(sd);
-            const uint32_t pos = g_ld(sd + 64 + lane);  // with the count: one round trip
+            uint32_t n, pos;
+            if (LA && la_ok) {  // requested with the previous batch's gathers
+                n = __builtin_amdgcn_readfirstlane(la_n);
+                pos = la_pos;
+            } else {
+                n = g_ld_u(sd);
+                pos = g_ld(sd + 64 + lane);  // with the count: one round trip
+            }
             if (n & END) break;
             valid = lane < n;
             if (valid) {
@@ -743,6 +772,19 @@ k_ffd_pipe(const PipeArgs a_arg) {
             n_rej += (uint32_t)__popcll(__ballot(cyc));
             valid = valid && !cyc;
             k0 += 64;
+            if constexpr (LA >= 2) {
+                // touch the next batch's five 256-B rows, clamped at C: words 0, 32 and 63 of each (a
+                // row that is not 128-B aligned lies in three lines).  One load per row -- a per-lane
+                // choice of the row pointer compiled to a dependent load of the pointer itself
+                if (k0 < C) {
+                    const size_t ti = cb + min(k0 + (lane == 0 ? 0u : lane == 1 ? 32u : 63u), C - 1);
+                    g_touch(a.s_cpu + ti);
+                    g_touch(a.s_mem + ti);
+                    g_touch(a.s_req + ti);
+                    g_touch(a.s_conf + ti);
+                    g_touch(a.s_idx + ti);
+                }
+            }
         } else {
             const uint32_t want = itail;
             if (!spin(&ictl[0], [want](uint32_t h) { return h != want; }, abort_flag, a.err, a.spin_ticks, st_spin_in)) break;
@@ -763,6 +805,22 @@ k_ffd_pipe(const PipeArgs a_arg) {
             }
             itail++;
             lds_rel(&ictl[1], itail);
+        }
+        if constexpr (LA != 0) {
+            // The next slot of the input link, requested in the same burst as the gathers above and not
+            // waited for before the next loop top.  Only if a head already seen covers it: an
+            // unpublished slot holds stale words, and nothing here polls (the next top does, as without
+            // look-ahead).  Outside the input branches and without a branch on la_ok, so that the loads
+            // write the loop-carried pair itself: inside the link branch, or under `if (la_ok)`, the
+            // compiler loaded into temporaries and copied them, waiting for the loads at once
+            // (DESIGN.md 4.1).  A slot not yet covered reads a word of the scenario's own s_idx row
+            // instead, which nothing uses.
+            la_ok = g_in && itail < ihead_seen;
+            if (g_in) {
+                const uint32_t *sn = la_ok ? gin_data + (size_t)GSLOT(itail) * LSLOT : a.s_idx + cb;
+                la_n = g_ld(sn);
+                la_pos = g_ld(sn + (la_ok ? 64u + lane : 0u));
+            }
         }
         // idle flush (global link): the consumer's tail, loaded now and used after the
         // candidate loop, so its round trip overlaps this batch's work
@@ -824,6 +882,21 @@ k_ffd_pipe(const PipeArgs a_arg) {
             }
         }
         cand = valid ? cand : GM(0);
+        if constexpr (LA >= 2) {
+            // touch the fields of the looked-ahead slot's containers (the prescan above has waited for
+            // this batch's gathers, so the slot words requested with them are back): the next top's
+            // gathers then hit L2.  Lanes past the count touch position 0
+            if (g_in && la_ok) {
+                const uint32_t tn = __builtin_amdgcn_readfirstlane(la_n);
+                if (!(tn & END)) {
+                    const uint32_t tp = lane < tn ? la_pos & pmask : 0u;
+                    g_touch(a.s_cpu + cb + tp);
+                    g_touch(a.s_mem + cb + tp);
+                    g_touch(a.s_req + cb + tp);
+                    g_touch(a.s_conf + cb + tp);
+                }
+            }
+        }
         const bool zero = valid && (cpu | mem | req | conf) == 0u;
         uint64_t todo = __builtin_amdgcn_ballot_w64(cand != 0 && !zero);
         uint64_t placed = 0;
