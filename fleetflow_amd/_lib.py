@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("FLEETPLACE_LIB") or os.path.join(_HERE, "libfleetplac
 
 FP_OK, FP_EINVAL, FP_ENOMEM, FP_EDEVICE, FP_EOVERFLOW, FP_ECORRUPT = 0, -1, -2, -3, -4, -5
 FP_NONE = 0xFFFFFFFF
-REASON_OK, REASON_NOFIT, REASON_CYCLE = 0, 1, 2
+REASON_OK, REASON_NOFIT, REASON_CYCLE, REASON_SKEW = 0, 1, 2, 3
 FP_K_PLACE, FP_K_SORT, FP_K_FEAS, FP_K_LEVEL, FP_K_GEN = 0, 1, 2, 3, 4
 # scored placement (fleetplace.h enum fp_strategy, SPEC.md 2.6); the strings are the control plane's
 # PlacementPolicy.strategy constants (crates/fleetflow-controlplane/src/model.rs:56-95)
@@ -24,6 +24,8 @@ STRATEGY_FIRST_FIT, STRATEGY_SPREAD, STRATEGY_PACK, STRATEGY_FILL_LOWEST = 0, 1,
 POLICY_STRATEGIES = {"spread_across_pool": STRATEGY_SPREAD, "pack_into_dedicated": STRATEGY_PACK,
                      "fill_lowest": STRATEGY_FILL_LOWEST}
 FP_POLICY_MAX_NODES = 8192
+# hard topology spread (SPEC.md 2.7): the domain ids of fp_place_policy_spread are below this
+FP_SPREAD_MAX_DOMAINS = 64
 # context options (fleetplace.h enum fp_option); FP_OPT_AUTO = the production default
 # ("segsort" is ignored by the library and kept for ABI stability)
 FP_OPT_AUTO = -1
@@ -105,6 +107,10 @@ SIGNATURES = {
                                    u32p, u32p, u8p]),
     "fp_place_batch_policy": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p]),
     "fp_dev_place_batch_policy": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp]),
+    "fp_place_policy_spread": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, ct.c_uint32,
+                                          ct.c_uint32, u32p, u32p, ct.c_uint32, u32p, u8p]),
+    "fp_place_batch_policy_spread": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u32p]),
+    "fp_dev_place_batch_policy_spread": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp]),
     "fp_dev_argmin_cost": (ct.c_int, [vp, vp, ct.c_uint32, vp]),
     "fp_dev_gen_batch": (ct.c_int, [vp, ct.c_uint64, ct.POINTER(FpBatch), ct.c_uint32]),
 }

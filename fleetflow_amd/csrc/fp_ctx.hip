@@ -528,13 +528,21 @@ extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const 
 // Scored placement (SPEC.md 2.6): fp_place_batch's staging with the per-scenario strategy and
 // preferred-label words and the optional node counts.  The strategies are host memory here, so a
 // value that is no fp_strategy is refused before anything is staged.
+// domain / max_skew (SPEC.md 2.7; either null = no constraint) are host memory too: a domain id out of
+// range in a constrained scenario is refused here as well.
 static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                             uint32_t *node_count) {
+                             uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew) {
     const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
     const size_t SC = S * C, SN = S * N;
     if (S && !strategy) return FP_EINVAL;
     for (size_t s = 0; s < S; ++s)
         if (strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (!domain || !max_skew) domain = max_skew = nullptr;
+    for (size_t s = 0; max_skew && s < S; ++s) {
+        if (max_skew[s] == 0u) continue;
+        for (size_t n = 0; n < N; ++n)
+            if (domain[s * N + n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
+    }
     if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
     if (S && C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign ||
                    !b->reason))
@@ -545,7 +553,7 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1) + SN * (4 * 5 + 1) + S * (8 + 4 + 4) + 20 * 256);
+    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1) + SN * (4 * 6 + 1) + S * (8 + 4 + 4 + 4) + 22 * 256);
     if (rc) return rc;
     fp_stage_reset(c);
     fp_batch d = *b;
@@ -562,11 +570,13 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     const uint32_t *dstrat = stage_in(c, strategy, S, &rc);
     const uint32_t *dpref = stage_in(c, preferred, S, &rc);
     uint32_t *dcount = stage_in(c, node_count, SN, &rc);
+    const uint32_t *ddom = stage_in(c, domain, SN, &rc);
+    const uint32_t *dskew = stage_in(c, max_skew, S, &rc);
     d.assign = stage_out<uint32_t>(c, SC, &rc);
     d.reason = stage_out<uint8_t>(c, SC, &rc);
     d.cost = stage_out<uint64_t>(c, S, &rc);
     if (rc) return rc;
-    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount);
+    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount, ddom, dskew);
     if (rc) return rc;
     const OutCopy o[] = {{b->assign, d.assign, SC * 4},          {b->reason, d.reason, SC},
                          {b->cost, d.cost, S * 8},                {b->cpu_free, d.cpu_free, SN * 4},
@@ -575,15 +585,22 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     return copy_back_all(c, o, 7);
 }
 
-extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
-                                     const uint32_t *preferred_labels, uint32_t *node_count) {
+extern "C" int fp_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                            const uint32_t *preferred_labels, uint32_t *node_count,
+                                            const uint32_t *domain, const uint32_t *max_skew) {
     if (!c || !b) return FP_EINVAL;
-    return batch_policy_host(c, b, strategy, preferred_labels, node_count);
+    return batch_policy_host(c, b, strategy, preferred_labels, node_count, domain, max_skew);
 }
 
-extern "C" int fp_place_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
-                               uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
-                               uint32_t *assign_out, uint8_t *reason_out) {
+extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                     const uint32_t *preferred_labels, uint32_t *node_count) {
+    return fp_place_batch_policy_spread(c, b, strategy, preferred_labels, node_count, nullptr, nullptr);
+}
+
+extern "C" int fp_place_policy_spread(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                      uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                      const uint32_t *domain, uint32_t max_skew, uint32_t *assign_out,
+                                      uint8_t *reason_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
     fp_batch b;
     memset(&b, 0, sizeof(b));
@@ -602,14 +619,29 @@ extern "C" int fp_place_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns,
     b.schedulable = ns->schedulable;
     b.assign = assign_out;
     b.reason = reason_out;
-    return batch_policy_host(c, &b, &strategy, &preferred_labels, node_count);
+    return batch_policy_host(c, &b, &strategy, &preferred_labels, node_count, domain, &max_skew);
+}
+
+extern "C" int fp_place_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                               uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                               uint32_t *assign_out, uint8_t *reason_out) {
+    return fp_place_policy_spread(c, cs, ns, level, strategy, preferred_labels, node_count, nullptr, 0u, assign_out,
+                                  reason_out);
 }
 
 extern "C" int fp_dev_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
                                          const uint32_t *preferred_labels, uint32_t *node_count) {
     if (!c || !b) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
-    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, nullptr, nullptr));
+}
+
+extern "C" int fp_dev_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                                const uint32_t *preferred_labels, uint32_t *node_count,
+                                                const uint32_t *domain, const uint32_t *max_skew) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew));
 }
 
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,

@@ -1,5 +1,6 @@
 // fp_policy.hip -- scored placement (SPEC.md 2.6): spread / pack / fill-lowest placers and soft
-// preferred labels, batched over what-if scenarios.  One workgroup owns one scenario.
+// preferred labels, batched over what-if scenarios, and the same under a hard topology spread
+// (SPEC.md 2.7, the PlacementPolicy's SpreadConstraint).  One workgroup owns one scenario.
 //
 // First fit (fp_place.hip, fp_pipe.hip) prunes and pipelines on monotonicity.  A scored rule picks the
 // feasible node with the smallest key, on state that changes after every placement, so every container
@@ -8,11 +9,14 @@
 // Per fp_dev_place_batch_policy call (asynchronous, nothing is read back):
 //   1. k_policy_check : one word, set when any scenario's strategy is not an fp_strategy value; every
 //                       later kernel of the call returns on it before writing (all-or-nothing), and
-//                       FP_EINVAL goes into the context's error word
+//                       FP_EINVAL goes into the context's error word.  With a spread constraint,
+//                       k_policy_check_domain sets the same word for a domain id of 64 or more in a
+//                       scenario whose max_skew is not 0
 //   2. k_policy_keys  : key (~cpu << 32 | ~mem), value = the index in the scenario; a stable rocprim
 //                       radix sort over 64 bits (segmented per scenario for S > 1) gives the FFD order
 //                       (cpu desc, mem desc, index asc) -- the recipe of fp_place.hip step 3b
-//   3. k_policy<BLK,K>: the placer.  The scenario's node state lives in registers for the whole
+//   3. k_policy<BLK,K,SP>: the placer (SP: with the spread constraint; launched when the call gives
+//                       domain and max_skew).  The scenario's node state lives in registers for the whole
 //                       kernel: thread t of a BLK-thread block owns nodes t + BLK * j, j < K, five
 //                       words each (cpu_free, mem_free, conflict_used, count, labels) plus the static
 //                       preferred-label miss count, a per-thread schedulable mask and a "touched" mask.
@@ -33,6 +37,16 @@
 // parity counts reductions, not containers: a CYCLE container runs none, and two reductions with only a
 // skipped container between them must still use different buffers.
 //
+// The spread constraint (SP) adds no barrier and no LDS traffic per container, so the argument above
+// holds as it stands.  Every wave keeps the 64 domain counts in one register (lane d = domain d), takes
+// their minimum with the DPP row operations of the key reduction, and ballots `count - min < max_skew`
+// into a wave-uniform mask of the domains that pass; a thread looks its K nodes up in that mask once per
+// placement (the mask changes only then), not once per container.  A node that fits and fails the skew
+// test contributes KEY_SKEW = KEY_NONE - 1, so the one reduction also tells SKEW from NOFIT.  The key's
+// node field carries n << 6 | domain: the same order, and the winner's domain reaches every wave with
+// the winner, where each wave adds one to that lane of its own copy.  The only LDS the constraint uses is
+// a 66-word table in the prologue (the domain sums of node_count and the eligible-domain mask).
+//
 // The container record (cpu, mem, req, conf, original index, CYCLE flag) is uniform across the block.
 // Each wave gathers 64 records at a time into registers (lane l holds record i0 + l, loaded a chunk
 // ahead) and broadcasts container u with v_readlane, so the record arrives in scalar registers and no
@@ -50,6 +64,12 @@ namespace {
 
 constexpr uint64_t KEY_NONE = ~0ull;
 constexpr uint32_t KEY_NODE_BITS = 26;  // key = pref_miss << 58 | primary << 26 | node
+// SPEC.md 2.7: a node that fits by 2.3 and fails the skew test.  Real keys are below 0x84 << 56
+// (pref_miss <= 32), so a block minimum of KEY_SKEW says SKEW and one of KEY_NONE says NOFIT
+constexpr uint64_t KEY_SKEW = KEY_NONE - 1;
+constexpr uint32_t DOM_BITS = 6;  // FP_SPREAD_MAX_DOMAINS = 64: a domain id is one lane of a wave
+static_assert((1u << DOM_BITS) == FP_SPREAD_MAX_DOMAINS && FP_SPREAD_MAX_DOMAINS == 64, "one domain per lane");
+static_assert((uint64_t)FP_POLICY_MAX_NODES << DOM_BITS <= (1ull << KEY_NODE_BITS), "node << 6 | domain fits the node field");
 
 __global__ __launch_bounds__(256) void k_policy_check(const uint32_t *__restrict__ strategy, uint32_t S,
                                                       uint32_t *__restrict__ bad, uint32_t *__restrict__ err) {
@@ -59,6 +79,21 @@ __global__ __launch_bounds__(256) void k_policy_check(const uint32_t *__restrict
     if (threadIdx.x == 0) {
         *bad = any ? 1u : 0u;
         if (any) atomicMax(err, (uint32_t)(-FP_EINVAL));
+    }
+}
+
+// SPEC.md 2.7: a domain id of FP_SPREAD_MAX_DOMAINS or more in a scenario whose max_skew is not 0.  Runs
+// behind k_policy_check on the stream (which initialises the word) and only ever sets it.
+__global__ __launch_bounds__(256) void k_policy_check_domain(const uint32_t *__restrict__ domain,
+                                                             const uint32_t *__restrict__ max_skew, size_t SN, uint32_t N,
+                                                             uint32_t *__restrict__ bad, uint32_t *__restrict__ err) {
+    bool b = false;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < SN; i += (size_t)gridDim.x * blockDim.x)
+        b |= domain[i] >= (uint32_t)FP_SPREAD_MAX_DOMAINS && max_skew[i / N] != 0u;
+    const bool any = __syncthreads_or(b);
+    if (threadIdx.x == 0 && any) {
+        atomicOr(bad, 1u);
+        atomicMax(err, (uint32_t)(-FP_EINVAL));
     }
 }
 
@@ -93,6 +128,8 @@ struct PolicyArgs {
     const uint8_t *schedulable;                   // [S][N]
     uint32_t *node_count;                         // [S][N] in/out or null
     const uint32_t *strategy, *preferred;         // [S]; preferred nullable
+    const uint32_t *domain;                       // [S][N] topology domain (SPEC.md 2.7); read by k_policy<.., true>
+    const uint32_t *max_skew;                     // [S], 0 = no constraint in that scenario
     uint32_t *assign;                             // [S][C]
     uint8_t *reason;                              // [S][C]
     uint64_t *cost;                               // [S] or null
@@ -133,7 +170,23 @@ __device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
     return min64(min64(lane64(v, 0), lane64(v, 16)), min64(lane64(v, 32), lane64(v, 48)));
 }
 
-template <int BLK, int K>
+// the same over 32-bit values (the domain counts of SPEC.md 2.7)
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t min32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
+    v = min32(v, dpp32<0xB1>(v));
+    v = min32(v, dpp32<0x4E>(v));
+    v = min32(v, dpp32<0x141>(v));
+    v = min32(v, dpp32<0x140>(v));
+    return min32(min32(bcast(v, 0), bcast(v, 16)), min32(bcast(v, 32), bcast(v, 48)));
+}
+
+// SP: the hard topology spread of SPEC.md 2.7 (a.domain and a.max_skew given).  SP = false is 2.6 and
+// compiles to what it did before the constraint existed.
+template <int BLK, int K, bool SP>
 __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     static_assert(BLK % 64 == 0 && (BLK & (BLK - 1)) == 0, "block of whole waves, power of two");
     constexpr uint32_t NW = BLK / 64;
@@ -158,6 +211,60 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
         cnt[j] = in && a.node_count ? a.node_count[nb + n] : 0u;
         if (in && a.schedulable[nb + n]) sched |= 1u << j;
         pmh[j] = (uint32_t)__popc(pref & ~lab[j]) << (58 - 32);
+    }
+
+    // ---- SPEC.md 2.7.  nd[j] = n << 6 | domain(n) is the key's node field of each owned node.  Every wave
+    // keeps its own copy of the domain counts in one register: lane d = dom_count[d], all-ones in a domain
+    // without a schedulable node (no feasible node is in one, so what its lane says never matters).  After
+    // every placement the wave takes the minimum (DPP), the ballot of `count - min < max_skew` is the
+    // wave-uniform mask of the domains that pass, and each thread looks up its K nodes in it: bit j of
+    // pbits = node j passes.  v_bfe_u32 reads the low five bits of its offset operand, so it takes nd[j] as
+    // it is; h5 (bit j = domain(j) >= 32) picks the mask's word.  Nothing per node is derived from the
+    // domain alone, which the compiler would hoist into K more registers ----
+    uint32_t nd[SP ? K : 1];
+    uint32_t dcnt = 0, mskew = 0, h5 = 0, pbits = ~0u;
+    auto skew_bits = [&]() {
+        const uint64_t m = __ballot(dcnt - wave_min32(dcnt) < mskew);
+        uint32_t x = 0, y = 0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            x |= __builtin_amdgcn_ubfe((uint32_t)m, nd[j], 1u) << j;
+            y |= __builtin_amdgcn_ubfe((uint32_t)(m >> 32), nd[j], 1u) << j;
+        }
+        pbits = (x & ~h5) | (y & h5);
+    };
+    if constexpr (SP) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) nd[j] = (t + (uint32_t)BLK * j) << DOM_BITS;
+        mskew = a.max_skew[s];
+        if (mskew != 0u) {  // uniform over the block; 0 is 2.6: the domains are not read
+            __shared__ uint32_t dtab[FP_SPREAD_MAX_DOMAINS + 2];  // counts, then the eligible mask's two words
+            for (uint32_t i = t; i < FP_SPREAD_MAX_DOMAINS + 2; i += (uint32_t)BLK) dtab[i] = 0u;
+            __syncthreads();
+            uint32_t e0 = 0, e1 = 0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const uint32_t n = t + (uint32_t)BLK * j;
+                if (n < N) {
+                    // k_policy_check_domain refused a value >= 64 before this kernel; the mask keeps the
+                    // LDS index in bounds whatever the memory holds
+                    const uint32_t d = a.domain[nb + n] & (FP_SPREAD_MAX_DOMAINS - 1u);
+                    nd[j] |= d;
+                    h5 |= (d >> 5) << j;
+                    if (cnt[j]) atomicAdd(&dtab[d], cnt[j]);  // u32, wraps
+                    if ((sched >> j) & 1u) {
+                        if (d < 32u) e0 |= 1u << d;
+                        else e1 |= 1u << (d - 32u);
+                    }
+                }
+            }
+            if (e0) atomicOr(&dtab[FP_SPREAD_MAX_DOMAINS], e0);
+            if (e1) atomicOr(&dtab[FP_SPREAD_MAX_DOMAINS + 1], e1);
+            __syncthreads();
+            const bool elig = (dtab[FP_SPREAD_MAX_DOMAINS + (lane >> 5)] >> (lane & 31u)) & 1u;
+            dcnt = elig ? dtab[lane] : ~0u;
+            skew_bits();
+        }
     }
 
     __shared__ uint64_t slot[2][NW];
@@ -209,9 +316,17 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
                                           : ST == FP_STRATEGY_FILL_LOWEST ? ~cf[j]
                                                                           : 0u;
                     const uint32_t hi = pmh[j] | (prim >> (32 - KEY_NODE_BITS));
-                    const uint32_t lo = (prim << KEY_NODE_BITS) | (t + (uint32_t)BLK * j);
-                    const uint64_t key = ((uint64_t)hi << 32) | lo;
-                    best = min64(best, ok ? key : KEY_NONE);
+                    if constexpr (SP) {
+                        // the node field carries n << 6 | domain: the same order (the domain is a function
+                        // of n), and the winner's domain reaches every thread with the winner
+                        const uint32_t lo = (prim << KEY_NODE_BITS) | nd[j];
+                        const uint64_t key = ((uint64_t)hi << 32) | lo;
+                        best = min64(best, ok ? ((pbits >> j) & 1u ? key : KEY_SKEW) : KEY_NONE);
+                    } else {
+                        const uint32_t lo = (prim << KEY_NODE_BITS) | (t + (uint32_t)BLK * j);
+                        const uint64_t key = ((uint64_t)hi << 32) | lo;
+                        best = min64(best, ok ? key : KEY_NONE);
+                    }
                 }
             };
             switch (strat) {  // uniform
@@ -232,8 +347,9 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
             }
 
             // ---- the winner ----
-            const bool placed = best != KEY_NONE;
-            const uint32_t n = (uint32_t)best & ((1u << KEY_NODE_BITS) - 1u);
+            const bool placed = SP ? best < KEY_SKEW : best != KEY_NONE;
+            const uint32_t nf = (uint32_t)best & ((1u << KEY_NODE_BITS) - 1u);
+            const uint32_t n = SP ? nf >> DOM_BITS : nf;
             if (placed && (n & (uint32_t)(BLK - 1)) == t) {
                 const uint32_t J = n / (uint32_t)BLK;
 #pragma unroll
@@ -247,10 +363,16 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
                     }
                 }
             }
+            if constexpr (SP) {
+                if (placed && mskew != 0u) {  // every wave: the winner's domain gains one, the mask follows
+                    dcnt += lane == (nf & (FP_SPREAD_MAX_DOMAINS - 1u)) ? 1u : 0u;
+                    skew_bits();
+                }
+            }
             if (!placed) ++rejected;
             if (t == 0) {
                 a.assign[cb + idx] = placed ? n : FP_NONE;
-                a.reason[cb + idx] = (uint8_t)(placed ? FP_REASON_OK : FP_REASON_NOFIT);
+                a.reason[cb + idx] = (uint8_t)(placed ? FP_REASON_OK : SP && best == KEY_SKEW ? FP_REASON_SKEW : FP_REASON_NOFIT);
             }
         }
     }
@@ -306,7 +428,7 @@ int policy_sort_tmp(hipStream_t st, uint32_t S, size_t SC, size_t *bytes) {
 }  // namespace
 
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                                   uint32_t *node_count) {
+                                   uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew) {
     const uint32_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
     // this call resets the arena the last first-fit call's range words live in (fp_ctx_place_path)
     c->last_rng = nullptr;
@@ -319,6 +441,7 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     if (C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign || !b->reason)) return FP_EINVAL;
     if (C && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable)) return FP_EINVAL;
     hipStream_t st = c->stream;
+    const bool sp = domain && max_skew;  // SPEC.md 2.7: either pointer null = no constraint anywhere
 
     size_t sort_tmp = 0;
     if (C)
@@ -330,6 +453,10 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     if (!bad) return FP_ENOMEM;
     k_policy_check<<<1, 256, 0, st>>>(strategy, S, bad, c->d_err);
     FP_HIP(hipGetLastError());
+    if (sp && N) {
+        k_policy_check_domain<<<grid_for((size_t)S * N, 256), 256, 0, st>>>(domain, max_skew, (size_t)S * N, N, bad, c->d_err);
+        FP_HIP(hipGetLastError());
+    }
     if (C == 0) {  // nothing to place: every scenario costs (0 rejected, 0 nodes used)
         if (b->cost) {
             k_policy_fill_cost<<<(S + 255) / 256, 256, 0, st>>>(S, b->scen_base, bad, b->cost);
@@ -370,14 +497,23 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     a.labels = b->labels; a.schedulable = b->schedulable;
     a.node_count = node_count;
     a.strategy = strategy; a.preferred = preferred;
+    a.domain = sp ? domain : nullptr; a.max_skew = sp ? max_skew : nullptr;
     a.assign = b->assign; a.reason = b->reason; a.cost = b->cost;
     a.bad = bad;
     fp_prof_begin(c, FP_K_PLACE, &ev);
-    if (N <= 64) k_policy<64, 1><<<S, 64, 0, st>>>(a);
-    else if (N <= 1024) k_policy<1024, 1><<<S, 1024, 0, st>>>(a);
-    else if (N <= 2048) k_policy<1024, 2><<<S, 1024, 0, st>>>(a);
-    else if (N <= 4096) k_policy<1024, 4><<<S, 1024, 0, st>>>(a);
-    else k_policy<1024, 8><<<S, 1024, 0, st>>>(a);
+    if (sp) {
+        if (N <= 64) k_policy<64, 1, true><<<S, 64, 0, st>>>(a);
+        else if (N <= 1024) k_policy<1024, 1, true><<<S, 1024, 0, st>>>(a);
+        else if (N <= 2048) k_policy<1024, 2, true><<<S, 1024, 0, st>>>(a);
+        else if (N <= 4096) k_policy<1024, 4, true><<<S, 1024, 0, st>>>(a);
+        else k_policy<1024, 8, true><<<S, 1024, 0, st>>>(a);
+    } else {
+        if (N <= 64) k_policy<64, 1, false><<<S, 64, 0, st>>>(a);
+        else if (N <= 1024) k_policy<1024, 1, false><<<S, 1024, 0, st>>>(a);
+        else if (N <= 2048) k_policy<1024, 2, false><<<S, 1024, 0, st>>>(a);
+        else if (N <= 4096) k_policy<1024, 4, false><<<S, 1024, 0, st>>>(a);
+        else k_policy<1024, 8, false><<<S, 1024, 0, st>>>(a);
+    }
     FP_HIP(hipGetLastError());
     fp_prof_end(c, FP_K_PLACE, ev);
     return FP_OK;

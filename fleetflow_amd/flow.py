@@ -90,14 +90,28 @@ POLICY_STRATEGIES = ("spread_across_pool", "pack_into_dedicated", "fill_lowest")
 @dataclass
 class PlacementPolicy:
     """The tenant PlacementPolicy subset the planner reads (controlplane model.rs:56-95): one of the
-    three strategy constants (None = first fit) and the soft ``preferred_labels`` map.
-    SpreadConstraint, fallback_policy and resource_quota are not read."""
+    three strategy constants (None = first fit), the soft ``preferred_labels`` map and the hard
+    ``SpreadConstraint{topology_key, max_skew}`` (model.rs:56-63; SPEC.md 2.7), which constrains when
+    both fields are set and ``max_skew`` >= 1.  fallback_policy and resource_quota are not read
+    (DESIGN.md 4.8).  Two policies compare equal on strategy and preferred labels, the fields SPEC.md 2.6
+    reads; compare ``spread`` for the constraint."""
     strategy: str | None = None
     preferred_labels: dict[str, str] = field(default_factory=dict)
+    spread_topology_key: str | None = field(default=None, compare=False)
+    spread_max_skew: int | None = field(default=None, compare=False)
 
     def __post_init__(self):
         if self.strategy is not None and self.strategy not in POLICY_STRATEGIES:
             raise ValueError(f"unknown placement strategy '{self.strategy}' (expected {'|'.join(POLICY_STRATEGIES)})")
+        if self.spread_max_skew is not None and not 0 <= self.spread_max_skew <= U32_MAX:
+            raise ValueError(f"spread max_skew must be in 0..{U32_MAX}, got {self.spread_max_skew!r}")
+
+    @property
+    def spread(self) -> tuple[str, int] | None:
+        """(topology_key, max_skew) when the policy carries a constraint that constrains, else None."""
+        if self.spread_topology_key is None or self.spread_max_skew is None or self.spread_max_skew < 1:
+            return None
+        return self.spread_topology_key, self.spread_max_skew
 
     @property
     def preferred(self) -> list[str]:
@@ -106,7 +120,7 @@ class PlacementPolicy:
 
     @property
     def active(self) -> bool:
-        return self.strategy is not None or bool(self.preferred_labels)
+        return self.strategy is not None or bool(self.preferred_labels) or self.spread is not None
 
 
 @dataclass
@@ -258,6 +272,28 @@ class Plan:
     # the placement strategy the assignment was made under (SPEC.md 2.6); None = first fit
     strategy: str | None = None
     preferred: list[str] = field(default_factory=list)
+    # the hard topology spread the assignment was made under (SPEC.md 2.7); None = no constraint
+    spread_topology_key: str | None = None
+    spread_max_skew: int | None = None
+
+
+def spread_domains(nodes: list[Server], topology_key: str) -> tuple[list[int], list[bool]]:
+    """The topology domain of each server under ``topology_key`` (SPEC.md 2.7): the value of its
+    ``key=value`` label, numbered in the order of first appearance in node-index order.  A server
+    without the key is no candidate under the constraint (k8s PodTopologySpread): has_key is False and
+    its domain id is 0, which nothing reads.  More than 64 distinct values is a ValueError."""
+    from ._lib import FP_SPREAD_MAX_DOMAINS
+    ids: dict[str, int] = {}
+    domain, has_key = [], []
+    prefix = topology_key + "="
+    for nd in nodes:
+        value = next((lab[len(prefix):] for lab in nd.labels if lab.startswith(prefix)), None)
+        has_key.append(value is not None)
+        domain.append(ids.setdefault(value, len(ids)) if value is not None else 0)
+    if len(ids) > FP_SPREAD_MAX_DOMAINS:
+        raise ValueError(f"spread constraint: topology key '{topology_key}' has {len(ids)} distinct values in this "
+                         f"stage (at most {FP_SPREAD_MAX_DOMAINS})")
+    return domain, has_key
 
 
 def _server_nodes(flow: Flow, servers: list[str]):
@@ -311,10 +347,13 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
     candidates and the FFD plan -- when every service name appears once in the stage; a stage
     listing a name twice (positions != vertices) takes the per-output calls.
 
-    ``policy`` (or, without one, the stage's parsed ``placement`` node) selects a placement strategy
-    and soft preferred labels (SPEC.md 2.6): levels, orders and candidates are computed as without
-    one, and the assignment comes from ``Planner.place_policy``.  No policy, or one that sets
-    nothing: exactly the path above."""
+    ``policy`` (or, without one, the stage's parsed ``placement`` node) selects a placement strategy,
+    soft preferred labels (SPEC.md 2.6) and a hard topology spread (SPEC.md 2.7): levels, orders and
+    candidates are computed as without one, and the assignment comes from ``Planner.place_policy``.
+    Under a spread constraint the servers' ``topology_key=value`` labels give the domains
+    (``spread_domains``); a server without the key goes to the policy call as unschedulable and
+    receives nothing, and a service some server fits but none within the skew is rejected as "SKEW".
+    No policy, or one that sets nothing: exactly the path above."""
     p = planner or default_planner()
     stage = flow.stages[stage_name]
     services = list(stage.services)
@@ -355,8 +394,14 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
         lvl_v = dict(zip(services, levels))
         cont, ntab = _stage_tables(names, flow, nodes, pol.preferred)
         pmask = _stage_labels(names, flow, nodes, pol.preferred).mask(pol.preferred)
+        domain, max_skew = None, 0
+        if pol.spread is not None:
+            domain, has_key = spread_domains(nodes, pol.spread[0])
+            max_skew = pol.spread[1]
+            ntab = (*ntab[:4], [s if k else 0 for s, k in zip(ntab[4], has_key)])
         assign, reason, _, _ = p.place_policy(cont, ntab, pol.strategy if pol.strategy is not None else 0,
-                                              preferred=pmask, level=[lvl_v[n] for n in names])
+                                              preferred=pmask, level=[lvl_v[n] for n in names], domain=domain,
+                                              max_skew=max_skew)
         placed = (placed[0], placed[1], assign, reason, None)
     if placed is not None:
         first, count, assign, reason, _ = placed
@@ -366,10 +411,12 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
             if assign[v] != NONE:
                 assignment[n] = nodes[assign[v]].slug
             else:
-                rejected[n] = "CYCLE" if reason[v] == 2 else "NOFIT"
+                rejected[n] = "CYCLE" if reason[v] == 2 else "SKEW" if reason[v] == 3 else "NOFIT"
     plan = Plan(stage_name, order, dict(zip(services, levels)), level_order, assignment, rejected, candidates)
     if placed is not None and pol is not None:
         plan.strategy, plan.preferred = pol.strategy, pol.preferred
+        if pol.spread is not None:
+            plan.spread_topology_key, plan.spread_max_skew = pol.spread
     return plan
 
 

@@ -172,8 +172,9 @@ def parse_stage(node) -> tuple[str, Stage, dict[str, Service]]:
 
 
 def parse_placement(node, stage_name: str) -> PlacementPolicy:
-    """``placement strategy="spread_across_pool" { prefer "region=tokyo" }``: the tenant
-    PlacementPolicy's strategy constant and soft preferred labels (controlplane model.rs:56-95)."""
+    """``placement strategy="spread_across_pool" { prefer "region=tokyo"; spread "region" max-skew=1 }``:
+    the tenant PlacementPolicy's strategy constant, soft preferred labels and hard
+    SpreadConstraint{topology_key, max_skew} (controlplane model.rs:56-95)."""
     strategy = None
     if node.has("strategy"):
         strategy = as_str(node.get("strategy"))
@@ -181,6 +182,7 @@ def parse_placement(node, stage_name: str) -> PlacementPolicy:
             raise FlowError(f"stage {stage_name}: unknown placement strategy {node.get('strategy')!r} "
                             f"(expected {'|'.join(POLICY_STRATEGIES)})")
     preferred: dict[str, str] = {}
+    spread_key = spread_skew = None
     for ch in node.children or []:
         if ch.name == "prefer":
             for _, v in ch.entries:
@@ -188,7 +190,18 @@ def parse_placement(node, stage_name: str) -> PlacementPolicy:
                     raise FlowError(f"stage {stage_name}: prefer takes \"key=value\" labels, got {v!r}")
                 k, val = v.split("=", 1)
                 preferred[k] = val
-    return PlacementPolicy(strategy, preferred)
+        elif ch.name == "spread":
+            key = ch.args()[0] if ch.args() else None
+            if not isinstance(key, str) or not key or "=" in key or len(ch.args()) != 1:
+                raise FlowError(f"stage {stage_name}: spread takes one topology key (a label key such as \"region\"), "
+                                f"got {ch.args()!r}")
+            if not ch.has("max-skew"):
+                raise FlowError(f"stage {stage_name}: spread \"{key}\" requires max-skew=<integer >= 1>")
+            skew = ch.get("max-skew")
+            if not kdl.is_int(skew) or not 1 <= skew <= U32_MAX:
+                raise FlowError(f"stage {stage_name}: spread max-skew must be an integer in 1..{U32_MAX}, got {skew!r}")
+            spread_key, spread_skew = key, skew
+    return PlacementPolicy(strategy, preferred, spread_key, spread_skew)
 
 
 # ---- parser/cloud.rs:46-140 (+ SPEC.md 4 capacity/labels/scheduling) ------------------------

@@ -33,8 +33,11 @@ def plan_to_json(plan: Plan, indent: int | None = None) -> str:
         "rejected": plan.rejected,
         "candidates": {k: {"count": c, "first": f} for k, (c, f) in plan.candidates.items()},
     }
-    if plan.strategy is not None or plan.preferred:  # a plan made under a placement policy (SPEC.md 2.6)
+    spread = plan.spread_topology_key is not None
+    if plan.strategy is not None or plan.preferred or spread:  # made under a placement policy (SPEC.md 2.6, 2.7)
         d["placement"] = {"strategy": plan.strategy, "preferred": plan.preferred}
+        if spread:
+            d["placement"]["spread"] = {"topology_key": plan.spread_topology_key, "max_skew": plan.spread_max_skew}
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
@@ -44,7 +47,8 @@ def plan_from_json(text: str) -> Plan:
     return Plan(d["stage"], d["order"], {k: (U32_MAX if v is None else v) for k, v in d["levels"].items()},
                 d["level_order"], d["assign"], d["rejected"],
                 {k: (v["count"], v["first"]) for k, v in d.get("candidates", {}).items()},
-                pol.get("strategy"), list(pol.get("preferred") or []))
+                pol.get("strategy"), list(pol.get("preferred") or []),
+                (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"))
 
 
 def get_network_name(project: str, stage: str) -> str:
@@ -91,13 +95,17 @@ _FOOTER = "[dry-run] å®Ÿéš›ã®æ“ä½œã¯è¡Œã‚ã‚Œã¾ã›ã‚“ã€‚--dry-run ã‚’å¤–ã—ã
 
 
 def _policy_lines(plan: Plan | None) -> list[str]:
-    """The placement strategy a plan was made under (SPEC.md 2.6); nothing without one."""
-    if plan is None or (plan.strategy is None and not plan.preferred):
+    """The placement strategy (SPEC.md 2.6) and the hard topology spread (2.7) a plan was made under;
+    nothing without either."""
+    if plan is None or (plan.strategy is None and not plan.preferred and plan.spread_topology_key is None):
         return []
     line = f"  é…ç½®æˆ¦ç•¥: {plan.strategy if plan.strategy is not None else 'first_fit'}"
     if plan.preferred:
         line += f" (å„ªå…ˆãƒ©ãƒ™ãƒ«: {', '.join(plan.preferred)})"
-    return [line]
+    lines = [line]
+    if plan.spread_topology_key is not None:
+        lines.append(f"  é…ç½®åˆ†æ•£ä¿è¨¼: {plan.spread_topology_key} (max_skew={plan.spread_max_skew})")
+    return lines
 
 
 def format_up_dry_run(flow: Flow, stage_name: str, plan: Plan | None = None) -> str:

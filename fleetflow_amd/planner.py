@@ -272,11 +272,16 @@ class Planner:
         check(self._L.fp_place_batch(self._ctx, ct.byref(b)), "fp_place_batch")
         return assign, reason, cost, (cf, mf, lab, cu, sched)
 
-    def place_policy(self, cont, nodes, strategy, preferred=0, level=None, node_count=None):
+    def place_policy(self, cont, nodes, strategy, preferred=0, level=None, node_count=None, *, domain=None,
+                     max_skew=0):
         """Scored placement (SPEC.md 2.6, fp_place_policy): ``strategy`` is an fp_strategy value or one
         of the control plane's policy strings, ``preferred`` the soft preferred-label mask,
-        ``node_count`` the containers already on each node (None = zero).  Inputs are not mutated.
-        Returns (assign, reason, nodes_after, node_count_after); the last is None without node_count."""
+        ``node_count`` the containers already on each node (None = zero).  ``domain`` ([N] topology
+        domain ids below FP_SPREAD_MAX_DOMAINS) with ``max_skew`` >= 1 is the hard topology spread of
+        SPEC.md 2.7 (fp_place_policy_spread): a container some node fits but none within the skew comes
+        back with reason REASON_SKEW.  No domain, or max_skew = 0, is no constraint.  Inputs are not
+        mutated.  Returns (assign, reason, nodes_after, node_count_after); the last is None without
+        node_count."""
         cpu, mem, req, conf = (_u32(x) for x in cont)
         cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
         lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
@@ -287,21 +292,30 @@ class Planner:
         self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
         self._need(lv is None or lv.size == C, "level must hold C entries")
         self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        dom = _u32(domain) if domain is not None else None
+        self._need(dom is None or dom.size == N, "domain must hold N entries")
+        self._need(0 <= int(max_skew) <= 0xFFFFFFFF, "max_skew must be a u32")
         assign = np.empty(C, np.uint32)
         reason = np.empty(C, np.uint8)
         cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
         ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
         p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        if dom is not None:
+            check(self._L.fp_place_policy_spread(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
+                                                 int(preferred) & 0xFFFFFFFF, p32(nc), p32(dom), int(max_skew),
+                                                 p32(assign), reason.ctypes.data_as(_lib.u8p)), "fp_place_policy_spread")
+            return assign, reason, (cf, mf, lab, cu, sched), nc
         check(self._L.fp_place_policy(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
                                       int(preferred) & 0xFFFFFFFF, p32(nc), p32(assign),
                                       reason.ctypes.data_as(_lib.u8p)), "fp_place_policy")
         return assign, reason, (cf, mf, lab, cu, sched), nc
 
     def place_batch_policy(self, S, C, N, cont, nodes, strategy, preferred=None, level=None, node_count=None,
-                           scen_base=0):
+                           scen_base=0, *, domain=None, max_skew=None):
         """place_batch under per-scenario strategies ([S] ints or policy strings), preferred-label masks
-        ([S] or None) and node counts ([S*N] or None).  Returns (assign, reason, cost, nodes_after,
-        node_count_after)."""
+        ([S] or None) and node counts ([S*N] or None).  ``domain`` ([S*N]) with ``max_skew`` ([S], 0 = no
+        constraint in that scenario) is the topology spread of SPEC.md 2.7; either one None is no
+        constraint anywhere.  Returns (assign, reason, cost, nodes_after, node_count_after)."""
         cpu, mem, req, conf = (_u32(x) for x in cont)
         cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
         lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
@@ -320,6 +334,12 @@ class Planner:
         b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
                     _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
         p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        if domain is not None and max_skew is not None:
+            dom, sk = _u32(domain), _u32(max_skew)
+            self._need(dom.size == S * N and sk.size == S, "domain must hold S * N and max_skew S entries")
+            check(self._L.fp_place_batch_policy_spread(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc), p32(dom),
+                                                       p32(sk)), "fp_place_batch_policy_spread")
+            return assign, reason, cost, (cf, mf, lab, cu, sched), nc
         check(self._L.fp_place_batch_policy(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc)), "fp_place_batch_policy")
         return assign, reason, cost, (cf, mf, lab, cu, sched), nc
 
@@ -346,13 +366,23 @@ class Planner:
     def dev_place_batch(self, db: "DevBatch"):
         self._dev(lambda: check(self._L.fp_dev_place_batch(self._ctx, ct.byref(db.struct())), "fp_dev_place_batch"))
 
-    def dev_place_batch_policy(self, db: "DevBatch", strategy_t, preferred_t=None, count_t=None):
+    def dev_place_batch_policy(self, db: "DevBatch", strategy_t, preferred_t=None, count_t=None, *, domain_t=None,
+                               max_skew_t=None):
         """fp_dev_place_batch_policy: ``strategy_t`` [S] (int32 storage of fp_strategy values),
-        ``preferred_t`` [S] or None, ``count_t`` [S*N] in/out or None -- device tensors."""
+        ``preferred_t`` [S] or None, ``count_t`` [S*N] in/out or None -- device tensors.  ``domain_t``
+        [S*N] with ``max_skew_t`` [S] (int32 storage of u32 values) is the topology spread of SPEC.md 2.7
+        (fp_dev_place_batch_policy_spread); either one None is no constraint."""
         self._need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
         self._need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
         self._need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        if domain_t is not None and max_skew_t is not None:
+            self._need(domain_t.numel() == db.S * db.N and max_skew_t.numel() == db.S,
+                       "domain_t must hold S * N and max_skew_t S entries")
+            self._dev(lambda: check(self._L.fp_dev_place_batch_policy_spread(
+                self._ctx, ct.byref(db.struct()), p(strategy_t), p(preferred_t), p(count_t), p(domain_t), p(max_skew_t)),
+                "fp_dev_place_batch_policy_spread"))
+            return
         self._dev(lambda: check(self._L.fp_dev_place_batch_policy(self._ctx, ct.byref(db.struct()), p(strategy_t),
                                                                   p(preferred_t), p(count_t)),
                                 "fp_dev_place_batch_policy"))

@@ -93,8 +93,9 @@ def node_table(rows: list[dict]) -> list[Server]:
 
 def placement_policy(tenant_row: dict | None) -> PlacementPolicy | None:
     """A tenant row's ``placement_policy`` (as JSON; model.rs:82-95) -> the planner's policy: its
-    ``strategy`` constant and soft ``preferred_labels`` map.  None when the row has no policy; a
-    strategy that is none of the three constants is a ValueError.  ``spread_constraint``,
+    ``strategy`` constant, soft ``preferred_labels`` map and hard ``spread_constraint``
+    (``topology_key``, ``max_skew``; SPEC.md 2.7).  None when the row has no policy; a strategy that is
+    none of the three constants, or a constraint with a key and a ``max_skew`` below 1, is a ValueError.
     ``fallback_policy`` and ``resource_quota`` are not read."""
     pol = (tenant_row or {}).get("placement_policy")
     if pol is None:
@@ -103,7 +104,15 @@ def placement_policy(tenant_row: dict | None) -> PlacementPolicy | None:
     if strategy is not None and strategy not in POLICY_STRATEGIES:
         raise ValueError(f"unknown placement strategy {strategy!r} (expected {'|'.join(POLICY_STRATEGIES)})")
     pref = pol.get("preferred_labels") or {}
-    return PlacementPolicy(strategy, {str(k): str(v) for k, v in pref.items()})
+    spread = pol.get("spread_constraint") or {}
+    key, skew = spread.get("topology_key"), spread.get("max_skew")
+    if key is not None:
+        if isinstance(skew, bool) or not isinstance(skew, int) or not 1 <= skew <= U32_MAX:
+            raise ValueError(f"spread_constraint on '{key}': max_skew must be an integer in 1..{U32_MAX}, got {skew!r}")
+        key = str(key)
+    else:
+        skew = None
+    return PlacementPolicy(strategy, {str(k): str(v) for k, v in pref.items()}, key, skew)
 
 
 def pool_required_labels(pool: dict | None) -> list[str]:

@@ -16,6 +16,8 @@
  *   fp_place_batch    <- new: what-if scenarios, one plan per scenario + packed cost
  *   fp_place_policy   <- new: fp_place under the tenant PlacementPolicy's strategy and preferred labels
  *                        crates/fleetflow-controlplane/src/model.rs:56-95 (schema nothing reads upstream)
+ *   fp_place_policy_spread <- new: the same under the policy's SpreadConstraint{topology_key, max_skew}
+ *                        crates/fleetflow-controlplane/src/model.rs:56-63
  *   fp_feasibility    <- new: stage-2 containers x nodes feasibility/score sweep
  *   fp_dev_feasibility_batch <- new: the same sweep over many what-if scenarios
  *
@@ -71,7 +73,8 @@ extern "C" {
 
 #define FP_NONE 0xFFFFFFFFu /* "no node" / "no level" (cycle)                    */
 
-enum fp_reason { FP_REASON_OK = 0, FP_REASON_NOFIT = 1, FP_REASON_CYCLE = 2 };
+/* FP_REASON_SKEW: only from the *_policy_spread entries (SPEC.md 2.7): some node fits, none within max_skew */
+enum fp_reason { FP_REASON_OK = 0, FP_REASON_NOFIT = 1, FP_REASON_CYCLE = 2, FP_REASON_SKEW = 3 };
 
 typedef struct fp_ctx fp_ctx;
 
@@ -213,6 +216,27 @@ int fp_place_policy(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const 
 /* strategy, preferred_labels: [S] per scenario (preferred_labels nullable = 0) */
 int fp_place_batch_policy(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
                           const uint32_t *preferred_labels, uint32_t *node_count);
+/* Scored placement under a hard topology spread (SPEC.md 2.7), the PlacementPolicy's
+ * SpreadConstraint{topology_key, max_skew} (model.rs:56-63; the counterpart of k8s PodTopologySpread with
+ * whenUnsatisfiable = DoNotSchedule).  domain[n] < FP_SPREAD_MAX_DOMAINS is the topology domain of node n.
+ * dom_count[d] = the sum of node_count[n] over the nodes of domain d (zero without node_count; u32, wraps);
+ * a domain is eligible when one of its nodes is schedulable (fixed for the call, whatever the container).
+ * A node is feasible when it is feasible for fp_place_policy and
+ *   dom_count[domain[n]] - min(dom_count over the eligible domains) < max_skew
+ * on the state the call's earlier placements left; among the feasible nodes fp_place_policy's key decides,
+ * and a placement adds one to its domain's count.  A container some node fits but none within the skew is
+ * FP_REASON_SKEW (counted as rejected in the cost); one no node fits stays FP_REASON_NOFIT.
+ * max_skew = 0 is no constraint: that scenario is exactly fp_place_policy and its domain values are not read.
+ * domain = NULL or max_skew = NULL (batch entries) is no constraint anywhere.  A domain value of
+ * FP_SPREAD_MAX_DOMAINS or more in a scenario whose max_skew is not 0 is FP_EINVAL and nothing is written. */
+#define FP_SPREAD_MAX_DOMAINS 64
+int fp_place_policy_spread(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32_t *level,
+                           uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                           const uint32_t *domain, uint32_t max_skew, uint32_t *assign_out, uint8_t *reason_out);
+/* domain: [S][N]; max_skew: [S] */
+int fp_place_batch_policy_spread(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                                 const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                                 const uint32_t *max_skew);
 /* Stage 2: first feasible node (FP_NONE) and feasible-node count per container on
  * the given node state; bitmap_out (nullable, ceil(C/64) * N words) holds
  * bit (c, n) at word [(c/64) * N + n], bit c % 64. */
@@ -262,6 +286,11 @@ int fp_dev_feasibility_batch(fp_ctx *ctx, const fp_batch *b, uint32_t *first_out
  * fp_ctx_sync() reports FP_EINVAL. */
 int fp_dev_place_batch_policy(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
                               const uint32_t *preferred_labels, uint32_t *node_count);
+/* As fp_place_batch_policy_spread on device pointers.  A domain value that is out of range is found on
+ * the device with the strategy check: nothing is written and fp_ctx_sync() reports FP_EINVAL. */
+int fp_dev_place_batch_policy_spread(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                                     const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                                     const uint32_t *max_skew);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

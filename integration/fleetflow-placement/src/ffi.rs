@@ -15,11 +15,13 @@ pub const FP_NONE: u32 = 0xFFFF_FFFF;
 pub const FP_REASON_OK: u8 = 0;
 pub const FP_REASON_NOFIT: u8 = 1;
 pub const FP_REASON_CYCLE: u8 = 2;
+pub const FP_REASON_SKEW: u8 = 3;
 pub const FP_STRATEGY_FIRST_FIT: u32 = 0;
 pub const FP_STRATEGY_SPREAD: u32 = 1;
 pub const FP_STRATEGY_PACK: u32 = 2;
 pub const FP_STRATEGY_FILL_LOWEST: u32 = 3;
 pub const FP_POLICY_MAX_NODES: u32 = 8192;
+pub const FP_SPREAD_MAX_DOMAINS: u32 = 64;
 pub const FP_K_PLACE: c_int = 0;
 pub const FP_K_SORT: c_int = 1;
 pub const FP_K_FEAS: c_int = 2;
@@ -148,6 +150,12 @@ unsafe extern "C" {
                                  preferred_labels: *const u32, node_count: *mut u32) -> c_int;
     pub fn fp_dev_place_batch_policy(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
                                      preferred_labels: *const u32, node_count: *mut u32) -> c_int;
+    pub fn fp_place_policy_spread(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
+                                  strategy: u32, preferred_labels: u32, node_count: *mut u32, domain: *const u32,
+                                  max_skew: u32, assign_out: *mut u32, reason_out: *mut u8) -> c_int;
+    pub fn fp_place_batch_policy_spread(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                        preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                        max_skew: *const u32) -> c_int;
     pub fn fp_feasibility(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, first_out: *mut u32,
                           count_out: *mut u32, bitmap_out: *mut u64) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,
@@ -167,6 +175,9 @@ unsafe extern "C" {
                               first_out: *mut u32, count_out: *mut u32, bitmap_out: *mut u64) -> c_int;
     pub fn fp_dev_feasibility_batch(ctx: *mut fp_ctx, b: *const fp_batch, first_out: *mut u32,
                                     count_out: *mut u32) -> c_int;
+    pub fn fp_dev_place_batch_policy_spread(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                            preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                            max_skew: *const u32) -> c_int;
     pub fn fp_dev_argmin_cost(ctx: *mut fp_ctx, cost: *const u64, n: u32, best_dev: *mut u32) -> c_int;
     pub fn fp_dev_gen_batch(ctx: *mut fp_ctx, seed: u64, b: *const fp_batch, flags: u32) -> c_int;
 }

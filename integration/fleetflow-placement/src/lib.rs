@@ -134,6 +134,37 @@ impl Planner {
         Ok((assign, reason))
     }
 
+    /// Scored placement under a hard topology spread (SPEC.md 2.7, fleetplace.h `fp_place_policy_spread`),
+    /// the PlacementPolicy's `SpreadConstraint { topology_key, max_skew }`: `domain[n]` is the topology
+    /// domain of node n (below `ffi::FP_SPREAD_MAX_DOMAINS`, else FP_EINVAL) and a node is feasible only
+    /// while its domain's container count stays within `max_skew` of the emptiest eligible domain.  A
+    /// container some node fits but none within the skew has reason `ffi::FP_REASON_SKEW`.
+    /// `max_skew = 0` is `place_policy`.
+    pub fn place_policy_spread(&mut self, c: &Containers, nodes: &mut Nodes, level: Option<&[u32]>, strategy: u32,
+                               preferred_labels: u32, node_count: Option<&mut [u32]>, domain: &[u32], max_skew: u32)
+                               -> Result<(Vec<u32>, Vec<u8>), PlanError> {
+        let n = c.cpu_m.len();
+        let nn = nodes.cpu_free.len();
+        if !c.all_len(n) || !nodes.all_len(nn) || level.map_or(false, |l| l.len() != n)
+            || node_count.as_ref().map_or(false, |k| k.len() != nn) || domain.len() != nn {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        let mut ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_mut_ptr(),
+                                     mem_free: nodes.mem_free.as_mut_ptr(), labels: nodes.labels.as_ptr(),
+                                     conflict_used: nodes.conflict_used.as_mut_ptr(),
+                                     schedulable: nodes.schedulable.as_ptr() };
+        let (mut assign, mut reason) = (vec![0u32; n], vec![0u8; n]);
+        let count_ptr = node_count.map_or(std::ptr::null_mut(), |k| k.as_mut_ptr());
+        check(unsafe {
+            ffi::fp_place_policy_spread(self.ctx, &cs, &mut ns, level.map_or(std::ptr::null(), |l| l.as_ptr()),
+                                        strategy, preferred_labels, count_ptr, domain.as_ptr(), max_skew,
+                                        assign.as_mut_ptr(), reason.as_mut_ptr())
+        })?;
+        Ok((assign, reason))
+    }
+
     /// One stage's whole dry-run plan in one call (fleetplace.h `fp_plan_stage`, the
     /// `fleet up --dry-run` path of up.rs:57-136): the legacy order, the Kahn levels and start
     /// order and, with `placement = Some((containers, nodes))` (container v = vertex v), the

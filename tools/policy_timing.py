@@ -12,11 +12,23 @@ Each figure is a host clock around `steps` calls that end in a device synchronis
 calls, with the node state restored before each call; the placer's and the sort's own time come from
 the context's event brackets (FP_K_PLACE, FP_K_SORT) in a separate pass.  Writes
 profiles/policy_timing.json and prints it.
+
+    python tools/policy_timing.py --spread [--rounds R] [--parent-tree DIR]
+
+The hard topology spread (SPEC.md 2.7) on and off, per strategy, on the same batch: the unconstrained
+call, and fp_dev_place_batch_policy_spread with domain = n % D for D in {4, 64} and max_skew = 1.  Every
+round is a fresh process; with --parent-tree (a checkout of the commit to compare with, its library
+built) the rounds alternate with that tree's own tools/policy_timing.py, so the unconstrained calls of
+both builds are measured side by side in one run.  Writes profiles/policy_spread_timing.json: every
+round's figures, and their minimum, median and maximum.
 """
 import argparse
 import json
 import os
+import statistics
+import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,6 +68,86 @@ def timed(p, db, snap, call, steps, warmup):
     return 1e3 * wall / steps, place_ms / max(n_place, 1), sort_ms / max(n_place, 1)
 
 
+SPREAD_DOMAINS = (4, 64)
+
+
+def spread_round(a):
+    """One process's figures: per strategy the unconstrained call and the constrained one per D."""
+    S, C, N = a.scenarios, a.containers, a.nodes
+    dev = torch.device("cuda", 0)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    rounds = -(-S // cus) if N > 64 else None
+    out = {}
+    with Planner(0) as p:
+        db = DevBatch.allocate(S, C, N, dev)
+        p.dev_gen_batch(SEED4, db, 7)
+        p.sync()
+        snap = db.node_snapshot()
+        skew = torch.ones(S, dtype=torch.int32, device=dev)
+        doms = {D: (torch.arange(N, dtype=torch.int32, device=dev) % D).repeat(S) for D in SPREAD_DOMAINS}
+        for name, sid in STRATEGIES:
+            st = torch.full((S,), sid, dtype=torch.int32, device=dev)
+            calls = [("off", lambda: p.dev_place_batch_policy(db, st))]
+            calls += [(f"on_D{D}", lambda D=D: p.dev_place_batch_policy(db, st, domain_t=doms[D], max_skew_t=skew))
+                      for D in SPREAD_DOMAINS]
+            out[name] = {}
+            for label, call in calls:
+                wall, place_ms, sort_ms = timed(p, db, snap, call, a.steps, a.warmup)
+                reason = db.reason
+                rec = {"ms_per_call": wall, "place_kernel_ms": place_ms, "sort_ms": sort_ms,
+                       "rejected": int((reason != 0).sum().item()), "skew": int((reason == _lib.REASON_SKEW).sum().item())}
+                if rounds:
+                    rec["ns_per_placement"] = 1e6 * place_ms / (rounds * C)
+                out[name][label] = rec
+    return out
+
+
+def _child(cmd, cwd, out_path):
+    subprocess.run(cmd, cwd=cwd, check=True, stdout=subprocess.DEVNULL)
+    with open(out_path) as f:
+        return json.load(f)
+
+
+def _stats(xs):
+    return {"min": min(xs), "median": statistics.median(xs), "max": max(xs)}
+
+
+def spread_main(a):
+    """The driver: starts every round as a child process and makes no GPU call itself."""
+    shape = ["--scenarios", str(a.scenarios), "--containers", str(a.containers), "--nodes", str(a.nodes), "--steps", str(a.steps),
+             "--warmup", str(a.warmup)]
+    new_rounds, parent_rounds = [], []
+    with tempfile.TemporaryDirectory() as tmp:
+        for r in range(a.rounds):
+            if a.parent_tree:
+                path = os.path.join(tmp, f"parent{r}.json")
+                tool = os.path.join(os.path.abspath(a.parent_tree), "tools", "policy_timing.py")
+                parent_rounds.append(_child([sys.executable, tool, *shape, "--out", path], os.path.abspath(a.parent_tree), path))
+            path = os.path.join(tmp, f"new{r}.json")
+            new_rounds.append(_child([sys.executable, os.path.abspath(__file__), *shape, "--spread-child", "--out", path], ROOT, path))
+    out = {"shape": {"scenarios": a.scenarios, "containers": a.containers, "nodes": a.nodes, "flags": 7, "seed": SEED4},
+           "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "domain_map": "n % D", "max_skew": 1,
+           "order": "each round: the parent build's process, then this build's", "strategies": {}}
+    for name, _ in STRATEGIES:
+        rec = {}
+        for label in ["off"] + [f"on_D{D}" for D in SPREAD_DOMAINS]:
+            runs = [r[name][label] for r in new_rounds]
+            rec[label] = {"place_kernel_ms": _stats([x["place_kernel_ms"] for x in runs]),
+                          "ms_per_call": _stats([x["ms_per_call"] for x in runs]),
+                          "place_kernel_ms_rounds": [x["place_kernel_ms"] for x in runs],
+                          "rejected": runs[0]["rejected"], "skew": runs[0]["skew"]}
+            if "ns_per_placement" in runs[0]:
+                rec[label]["ns_per_placement"] = _stats([x["ns_per_placement"] for x in runs])
+        if parent_rounds:
+            runs = [r["strategies"][name] for r in parent_rounds]
+            rec["parent_off"] = {"place_kernel_ms": _stats([x["place_kernel_ms"] for x in runs]),
+                                 "ms_per_call": _stats([x["ms_per_call"] for x in runs]),
+                                 "place_kernel_ms_rounds": [x["place_kernel_ms"] for x in runs],
+                                 "rejected": runs[0]["rejected"]}
+        out["strategies"][name] = rec
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenarios", type=int, default=512)
@@ -63,8 +155,22 @@ def main():
     ap.add_argument("--nodes", type=int, default=5_000)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "policy_timing.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--spread", action="store_true", help="the topology spread on and off (see above)")
+    ap.add_argument("--rounds", type=int, default=3, help="--spread: processes per build")
+    ap.add_argument("--parent-tree", default=None, help="--spread: a built checkout of the commit to compare with")
+    ap.add_argument("--spread-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "policy_spread_timing.json" if a.spread else "policy_timing.json")
+    if a.spread or a.spread_child:
+        out = spread_round(a) if a.spread_child else spread_main(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
     S, C, N = a.scenarios, a.containers, a.nodes
     dev = torch.device("cuda", 0)
     props = torch.cuda.get_device_properties(dev)
