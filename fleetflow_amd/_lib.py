@@ -26,6 +26,8 @@ POLICY_STRATEGIES = {"spread_across_pool": STRATEGY_SPREAD, "pack_into_dedicated
 FP_POLICY_MAX_NODES = 8192
 # hard topology spread (SPEC.md 2.7): the domain ids of fp_place_policy_spread are below this
 FP_SPREAD_MAX_DOMAINS = 64
+# fallback chain (SPEC.md 2.8): at most this many hops, relax_mask rows hold this many words
+FP_FALLBACK_MAX_HOPS = 4
 # context options (fleetplace.h enum fp_option); FP_OPT_AUTO = the production default
 # ("segsort" is ignored by the library and kept for ABI stability)
 FP_OPT_AUTO = -1
@@ -111,6 +113,11 @@ SIGNATURES = {
                                           ct.c_uint32, u32p, u32p, ct.c_uint32, u32p, u8p]),
     "fp_place_batch_policy_spread": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u32p]),
     "fp_dev_place_batch_policy_spread": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp]),
+    "fp_place_policy_fallback": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, ct.c_uint32,
+                                            ct.c_uint32, u32p, u32p, ct.c_uint32, u32p, ct.c_uint32, u32p, u8p, u8p]),
+    "fp_place_batch_policy_fallback": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u32p, u32p, u32p,
+                                                  u8p]),
+    "fp_dev_place_batch_policy_fallback": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp, vp, vp, vp]),
     "fp_dev_argmin_cost": (ct.c_int, [vp, vp, ct.c_uint32, vp]),
     "fp_dev_gen_batch": (ct.c_int, [vp, ct.c_uint64, ct.POINTER(FpBatch), ct.c_uint32]),
 }

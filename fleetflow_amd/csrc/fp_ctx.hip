@@ -530,8 +530,11 @@ extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const 
 // value that is no fp_strategy is refused before anything is staged.
 // domain / max_skew (SPEC.md 2.7; either null = no constraint) are host memory too: a domain id out of
 // range in a constrained scenario is refused here as well.
+// relax_mask / n_hops (SPEC.md 2.8; either null = no fallback) likewise: an n_hops above
+// FP_FALLBACK_MAX_HOPS is refused here.  hops_out (nullable) receives the winners' hops.
 static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                             uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew) {
+                             uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
+                             const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
     const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
     const size_t SC = S * C, SN = S * N;
     if (S && !strategy) return FP_EINVAL;
@@ -543,6 +546,9 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
         for (size_t n = 0; n < N; ++n)
             if (domain[s * N + n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
     }
+    if (!relax_mask || !n_hops) relax_mask = n_hops = nullptr;
+    for (size_t s = 0; n_hops && s < S; ++s)
+        if (n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
     if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
     if (S && C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign ||
                    !b->reason))
@@ -553,7 +559,8 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1) + SN * (4 * 6 + 1) + S * (8 + 4 + 4 + 4) + 22 * 256);
+    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1 + 1) + SN * (4 * 6 + 1) +
+                                     S * (8 + 4 + 4 + 4 + 4 * FP_FALLBACK_MAX_HOPS + 4) + 25 * 256);
     if (rc) return rc;
     fp_stage_reset(c);
     fp_batch d = *b;
@@ -572,24 +579,35 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     uint32_t *dcount = stage_in(c, node_count, SN, &rc);
     const uint32_t *ddom = stage_in(c, domain, SN, &rc);
     const uint32_t *dskew = stage_in(c, max_skew, S, &rc);
+    const uint32_t *drelax = stage_in(c, relax_mask, S * FP_FALLBACK_MAX_HOPS, &rc);
+    const uint32_t *dhops_n = stage_in(c, n_hops, S, &rc);
     d.assign = stage_out<uint32_t>(c, SC, &rc);
     d.reason = stage_out<uint8_t>(c, SC, &rc);
     d.cost = stage_out<uint64_t>(c, S, &rc);
+    uint8_t *dhops = hops_out ? stage_out<uint8_t>(c, SC, &rc) : nullptr;
     if (rc) return rc;
-    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount, ddom, dskew);
+    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount, ddom, dskew, drelax, dhops_n, dhops);
     if (rc) return rc;
     const OutCopy o[] = {{b->assign, d.assign, SC * 4},          {b->reason, d.reason, SC},
                          {b->cost, d.cost, S * 8},                {b->cpu_free, d.cpu_free, SN * 4},
                          {b->mem_free, d.mem_free, SN * 4},       {b->conflict_used, d.conflict_used, SN * 4},
-                         {node_count, dcount, SN * 4}};
-    return copy_back_all(c, o, 7);
+                         {node_count, dcount, SN * 4},             {hops_out, dhops, SC}};
+    return copy_back_all(c, o, 8);
+}
+
+extern "C" int fp_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                              const uint32_t *preferred_labels, uint32_t *node_count,
+                                              const uint32_t *domain, const uint32_t *max_skew,
+                                              const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
+    if (!c || !b) return FP_EINVAL;
+    return batch_policy_host(c, b, strategy, preferred_labels, node_count, domain, max_skew, relax_mask, n_hops, hops_out);
 }
 
 extern "C" int fp_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
                                             const uint32_t *preferred_labels, uint32_t *node_count,
                                             const uint32_t *domain, const uint32_t *max_skew) {
-    if (!c || !b) return FP_EINVAL;
-    return batch_policy_host(c, b, strategy, preferred_labels, node_count, domain, max_skew);
+    return fp_place_batch_policy_fallback(c, b, strategy, preferred_labels, node_count, domain, max_skew, nullptr, nullptr,
+                                          nullptr);
 }
 
 extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
@@ -597,10 +615,10 @@ extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_
     return fp_place_batch_policy_spread(c, b, strategy, preferred_labels, node_count, nullptr, nullptr);
 }
 
-extern "C" int fp_place_policy_spread(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
-                                      uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
-                                      const uint32_t *domain, uint32_t max_skew, uint32_t *assign_out,
-                                      uint8_t *reason_out) {
+extern "C" int fp_place_policy_fallback(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                        uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                        const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
+                                        uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
     fp_batch b;
     memset(&b, 0, sizeof(b));
@@ -619,7 +637,16 @@ extern "C" int fp_place_policy_spread(fp_ctx *c, const fp_containers *cs, fp_nod
     b.schedulable = ns->schedulable;
     b.assign = assign_out;
     b.reason = reason_out;
-    return batch_policy_host(c, &b, &strategy, &preferred_labels, node_count, domain, &max_skew);
+    return batch_policy_host(c, &b, &strategy, &preferred_labels, node_count, domain, &max_skew, relax_mask, &n_hops,
+                             hops_out);
+}
+
+extern "C" int fp_place_policy_spread(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                      uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                      const uint32_t *domain, uint32_t max_skew, uint32_t *assign_out,
+                                      uint8_t *reason_out) {
+    return fp_place_policy_fallback(c, cs, ns, level, strategy, preferred_labels, node_count, domain, max_skew, nullptr, 0u,
+                                    assign_out, reason_out, nullptr);
 }
 
 extern "C" int fp_place_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
@@ -633,7 +660,8 @@ extern "C" int fp_dev_place_batch_policy(fp_ctx *c, const fp_batch *b, const uin
                                          const uint32_t *preferred_labels, uint32_t *node_count) {
     if (!c || !b) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
-    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, nullptr, nullptr));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, nullptr, nullptr,
+                                                         nullptr, nullptr, nullptr));
 }
 
 extern "C" int fp_dev_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
@@ -641,7 +669,18 @@ extern "C" int fp_dev_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, co
                                                 const uint32_t *domain, const uint32_t *max_skew) {
     if (!c || !b) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
-    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
+                                                         nullptr, nullptr, nullptr));
+}
+
+extern "C" int fp_dev_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                                  const uint32_t *preferred_labels, uint32_t *node_count,
+                                                  const uint32_t *domain, const uint32_t *max_skew,
+                                                  const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
+                                                         relax_mask, n_hops, hops_out));
 }
 
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,

@@ -137,9 +137,12 @@ int fp_dev_feasibility_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
                             uint32_t *first, uint32_t *count, uint64_t *bitmap);
 int fp_dev_feasibility_batch_impl(fp_ctx *c, const fp_batch *b, uint32_t *first, uint32_t *count);
 // scored placement (fp_policy.hip, SPEC.md 2.6 and 2.7); every pointer is device memory.  domain [S][N]
-// and max_skew [S] are the topology spread of 2.7; either one null = no constraint
+// and max_skew [S] are the topology spread of 2.7; either one null = no constraint.  relax_mask [S][4] and
+// n_hops [S] are the fallback chain of 2.8; either one null = no fallback.  hops [S][C] (nullable) receives
+// the winner's hop: all zero when the call has no chain
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                                   uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew);
+                                   uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
+                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops);
 
 // tile-pipeline FFD (fp_pipe.hip)
 bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint32_t *W_out, uint32_t *B_out,

@@ -1,6 +1,7 @@
 // fp_policy.hip -- scored placement (SPEC.md 2.6): spread / pack / fill-lowest placers and soft
 // preferred labels, batched over what-if scenarios, and the same under a hard topology spread
-// (SPEC.md 2.7, the PlacementPolicy's SpreadConstraint).  One workgroup owns one scenario.
+// (SPEC.md 2.7, the PlacementPolicy's SpreadConstraint) and under a fallback chain that gives required
+// labels up hop by hop (SPEC.md 2.8, the PlacementPolicy's FallbackPolicy).  One workgroup owns one scenario.
 //
 // First fit (fp_place.hip, fp_pipe.hip) prunes and pipelines on monotonicity.  A scored rule picks the
 // feasible node with the smallest key, on state that changes after every placement, so every container
@@ -11,12 +12,14 @@
 //                       later kernel of the call returns on it before writing (all-or-nothing), and
 //                       FP_EINVAL goes into the context's error word.  With a spread constraint,
 //                       k_policy_check_domain sets the same word for a domain id of 64 or more in a
-//                       scenario whose max_skew is not 0
+//                       scenario whose max_skew is not 0, and with a fallback chain k_policy_check_hops
+//                       sets it for an n_hops above FP_FALLBACK_MAX_HOPS
 //   2. k_policy_keys  : key (~cpu << 32 | ~mem), value = the index in the scenario; a stable rocprim
 //                       radix sort over 64 bits (segmented per scenario for S > 1) gives the FFD order
 //                       (cpu desc, mem desc, index asc) -- the recipe of fp_place.hip step 3b
-//   3. k_policy<BLK,K,SP>: the placer (SP: with the spread constraint; launched when the call gives
-//                       domain and max_skew).  The scenario's node state lives in registers for the whole
+//   3. k_policy<BLK,K,SP,FB>: the placer (SP: with the spread constraint; launched when the call gives
+//                       domain and max_skew.  FB: with the fallback chain; launched when the call gives
+//                       relax_mask and n_hops).  The scenario's node state lives in registers for the whole
 //                       kernel: thread t of a BLK-thread block owns nodes t + BLK * j, j < K, five
 //                       words each (cpu_free, mem_free, conflict_used, count, labels) plus the static
 //                       preferred-label miss count, a per-thread schedulable mask and a "touched" mask.
@@ -47,6 +50,15 @@
 // the winner, where each wave adds one to that lane of its own copy.  The only LDS the constraint uses is
 // a 66-word table in the prologue (the domain sums of node_count and the eligible-domain mask).
 //
+// The fallback chain (FB) adds no barrier and no LDS traffic either.  The scenario's cumulative relax
+// masks are uniform and live in scalar registers; a node's hop for a container is four compares on
+// `req & ~labels` and goes into the key above pref_miss, so the one reduction picks the smallest
+// (hop, key) and the winner's hop arrives with the winner.  64 bits are full in the 2.6 layout, but the
+// node field needs only 19 of its 26 bits (n << 6 | domain), so the FB variants use
+// hop:3 | pref_miss:6 | primary:32 | node:23 -- the same order, and still below KEY_SKEW.  A container
+// that requires none of the labels the scenario may give up (uniform over the block) cannot relax and
+// skips the hop arithmetic.
+//
 // The container record (cpu, mem, req, conf, original index, CYCLE flag) is uniform across the block.
 // Each wave gathers 64 records at a time into registers (lane l holds record i0 + l, loaded a chunk
 // ahead) and broadcasts container u with v_readlane, so the record arrives in scalar registers and no
@@ -64,12 +76,17 @@ namespace {
 
 constexpr uint64_t KEY_NONE = ~0ull;
 constexpr uint32_t KEY_NODE_BITS = 26;  // key = pref_miss << 58 | primary << 26 | node
+// SPEC.md 2.8, the FB variants: key = hop << 61 | pref_miss << 55 | primary << 23 | node
+constexpr uint32_t KEY_NODE_BITS_FB = 23;
+constexpr uint32_t KEY_HOP_SHIFT = 61;
 // SPEC.md 2.7: a node that fits by 2.3 and fails the skew test.  Real keys are below 0x84 << 56
-// (pref_miss <= 32), so a block minimum of KEY_SKEW says SKEW and one of KEY_NONE says NOFIT
+// (pref_miss <= 32; with a fallback chain hop <= 4 as well: below 0x91 << 56), so a block minimum of
+// KEY_SKEW says SKEW and one of KEY_NONE says NOFIT
 constexpr uint64_t KEY_SKEW = KEY_NONE - 1;
 constexpr uint32_t DOM_BITS = 6;  // FP_SPREAD_MAX_DOMAINS = 64: a domain id is one lane of a wave
 static_assert((1u << DOM_BITS) == FP_SPREAD_MAX_DOMAINS && FP_SPREAD_MAX_DOMAINS == 64, "one domain per lane");
-static_assert((uint64_t)FP_POLICY_MAX_NODES << DOM_BITS <= (1ull << KEY_NODE_BITS), "node << 6 | domain fits the node field");
+static_assert((uint64_t)FP_POLICY_MAX_NODES << DOM_BITS <= (1ull << KEY_NODE_BITS_FB), "node << 6 | domain fits the node field");
+static_assert(FP_FALLBACK_MAX_HOPS == 4 && FP_FALLBACK_MAX_HOPS < (1u << (64 - KEY_HOP_SHIFT)), "the hop fits its field");
 
 __global__ __launch_bounds__(256) void k_policy_check(const uint32_t *__restrict__ strategy, uint32_t S,
                                                       uint32_t *__restrict__ bad, uint32_t *__restrict__ err) {
@@ -95,6 +112,25 @@ __global__ __launch_bounds__(256) void k_policy_check_domain(const uint32_t *__r
         atomicOr(bad, 1u);
         atomicMax(err, (uint32_t)(-FP_EINVAL));
     }
+}
+
+// SPEC.md 2.8: an n_hops above FP_FALLBACK_MAX_HOPS.  Behind k_policy_check, like the domain check.
+__global__ __launch_bounds__(256) void k_policy_check_hops(const uint32_t *__restrict__ n_hops, uint32_t S,
+                                                           uint32_t *__restrict__ bad, uint32_t *__restrict__ err) {
+    bool b = false;
+    for (uint32_t s = threadIdx.x; s < S; s += blockDim.x) b |= n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS;
+    const bool any = __syncthreads_or(b);
+    if (threadIdx.x == 0 && any) {
+        atomicOr(bad, 1u);
+        atomicMax(err, (uint32_t)(-FP_EINVAL));
+    }
+}
+
+// hops of a call that asks for them without a fallback chain: every winner's hop is 0
+__global__ __launch_bounds__(256) void k_policy_zero_hops(uint8_t *__restrict__ hops, size_t n,
+                                                          const uint32_t *__restrict__ bad) {
+    if (*bad) return;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) hops[i] = 0;
 }
 
 __global__ void k_policy_fill_cost(uint32_t S, uint32_t scen_base, const uint32_t *__restrict__ bad,
@@ -134,6 +170,11 @@ struct PolicyArgs {
     uint8_t *reason;                              // [S][C]
     uint64_t *cost;                               // [S] or null
     const uint32_t *bad;                          // k_policy_check's word
+    // SPEC.md 2.8, read by k_policy<.., .., true> only.  Behind everything else, so that the other variants
+    // load their arguments from where they always did
+    const uint32_t *relax_mask;                   // [S][4] label bits hop h + 1 gives up
+    const uint32_t *n_hops;                       // [S], 0 = no fallback in that scenario
+    uint8_t *hops;                                // [S][C] or null: the winner's hop
 };
 
 __device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
@@ -186,10 +227,13 @@ __device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
 
 // SP: the hard topology spread of SPEC.md 2.7 (a.domain and a.max_skew given).  SP = false is 2.6 and
 // compiles to what it did before the constraint existed.
-template <int BLK, int K, bool SP>
+// FB: the fallback chain of SPEC.md 2.8 (a.relax_mask and a.n_hops given).  FB = false compiles to what
+// it did before the chain existed.
+template <int BLK, int K, bool SP, bool FB>
 __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     static_assert(BLK % 64 == 0 && (BLK & (BLK - 1)) == 0, "block of whole waves, power of two");
     constexpr uint32_t NW = BLK / 64;
+    constexpr uint32_t NB = FB ? KEY_NODE_BITS_FB : KEY_NODE_BITS;  // pref_miss sits at bit 32 + NB in both layouts
     if (*a.bad) return;  // an invalid strategy somewhere in the batch: nothing is written
     const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
     const uint32_t s = blockIdx.x, C = a.C, N = a.N;
@@ -198,7 +242,13 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     const uint32_t pref = a.preferred ? a.preferred[s] : 0u;
 
     // ---- the scenario's node state, in registers ----
-    uint32_t cf[K], mf[K], cu[K], cnt[K], lab[K], pmh[K];  // pmh = pref_miss << 26: the key's high word
+    // 1024 x 8 under both the spread and the chain is past the 128 registers of a 1024-thread block with
+    // pmh in registers of its own: that variant keeps pref_miss in nd[j], above the 23-bit node field (where
+    // it sits in the key's high word), and takes the two apart with one more VALU operation a node
+    constexpr bool KEEP_PMH = !(FB && SP && K == 8);
+    uint32_t cf[K], mf[K], cu[K], cnt[K], lab[K];
+    uint32_t pmh[KEEP_PMH ? K : 1];  // pmh = pref_miss << NB: the key's high word
+    auto pref_hi = [&](uint32_t l) { return (uint32_t)__popc(pref & ~l) << NB; };
     uint32_t sched = 0, touched = 0;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
@@ -210,7 +260,22 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
         lab[j] = in ? a.labels[nb + n] : 0u;
         cnt[j] = in && a.node_count ? a.node_count[nb + n] : 0u;
         if (in && a.schedulable[nb + n]) sched |= 1u << j;
-        pmh[j] = (uint32_t)__popc(pref & ~lab[j]) << (58 - 32);
+        if constexpr (KEEP_PMH) pmh[j] = pref_hi(lab[j]);
+    }
+
+    // ---- SPEC.md 2.8.  keep[h] = ~cum[h + 1], uniform: the required bits hop h + 1 still asks for.  Entries
+    // past n_hops repeat the last one, so keep[3] is the test under req_{n_hops} whatever n_hops is, and a
+    // node's hop is the number of h in 0..3 whose requirement it misses.  n_hops was checked before this
+    // kernel; the clamp keeps the loop at four whatever the memory holds ----
+    uint32_t keep[FB ? FP_FALLBACK_MAX_HOPS : 1];
+    if constexpr (FB) {
+        const uint32_t nh = min32(a.n_hops[s], (uint32_t)FP_FALLBACK_MAX_HOPS);
+        uint32_t cum = 0;
+#pragma unroll
+        for (uint32_t h = 0; h < FP_FALLBACK_MAX_HOPS; ++h) {
+            if (h < nh) cum |= a.relax_mask[(size_t)s * FP_FALLBACK_MAX_HOPS + h];
+            keep[h] = ~cum;
+        }
     }
 
     // ---- SPEC.md 2.7.  nd[j] = n << 6 | domain(n) is the key's node field of each owned node.  Every wave
@@ -235,7 +300,10 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     };
     if constexpr (SP) {
 #pragma unroll
-        for (int j = 0; j < K; ++j) nd[j] = (t + (uint32_t)BLK * j) << DOM_BITS;
+        for (int j = 0; j < K; ++j) {
+            nd[j] = (t + (uint32_t)BLK * j) << DOM_BITS;
+            if constexpr (!KEEP_PMH) nd[j] |= pref_hi(lab[j]);
+        }
         mskew = a.max_skew[s];
         if (mskew != 0u) {  // uniform over the block; 0 is 2.6: the domains are not read
             __shared__ uint32_t dtab[FP_SPREAD_MAX_DOMAINS + 2];  // counts, then the eligible mask's two words
@@ -284,6 +352,9 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
         if (in && r_idx == FP_NONE && w == 0) {  // CYCLE: reported here, skipped below
             a.assign[cb + o] = FP_NONE;
             a.reason[cb + o] = (uint8_t)FP_REASON_CYCLE;
+            if constexpr (FB) {
+                if (a.hops) a.hops[cb + o] = 0;
+            }
         }
     };
     gather(lane, ld_ord(lane));
@@ -303,37 +374,78 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
 
             // ---- this thread's min key ----
             uint64_t best = KEY_NONE;
-            auto local_min = [&](auto strat_c) {
+            // the node field's mask, opaque per container: taking nd[j] apart is loop-invariant, and hoisted
+            // out of the container loop it would cost the K registers that packing saved
+            uint32_t nmask = (1u << NB) - 1u;
+            if constexpr (!KEEP_PMH) asm volatile("" : "+s"(nmask));
+            auto local_min = [&](auto strat_c, auto relax_c) {
                 constexpr uint32_t ST = decltype(strat_c)::value;
+                constexpr bool RX = decltype(relax_c)::value;  // the container may relax (FB only)
 #pragma unroll
                 for (int j = 0; j < K; ++j) {
                     // a slot row past N holds no node (uniform): N = 5000 evaluates 5 of K = 8 rows.
                     // The kernel is bound by VALU issue (4 waves a SIMD, ~18 instructions a node)
                     if (K > 1 && (uint32_t)BLK * j >= N) break;
-                    const bool ok = ((sched >> j) & 1u) && fpd::fits(cpu, mem, req, conf, cf[j], mf[j], lab[j], cu[j]);
+                    bool ok;
+                    uint32_t hoph = 0;  // hop << 29: the key's high word
+                    if constexpr (RX) {
+                        // 2.3 under req_{n_hops}; the hop counts the earlier requirements the node misses
+                        const uint32_t miss = req & ~lab[j];
+                        ok = ((sched >> j) & 1u) && fpd::fits(cpu, mem, 0u, conf, cf[j], mf[j], 0u, cu[j]) &&
+                             (miss & keep[3]) == 0u;
+                        hoph = ((miss != 0u ? 1u : 0u) + ((miss & keep[0]) != 0u ? 1u : 0u) +
+                                ((miss & keep[1]) != 0u ? 1u : 0u) + ((miss & keep[2]) != 0u ? 1u : 0u))
+                               << (KEY_HOP_SHIFT - 32);
+                    } else {
+                        ok = ((sched >> j) & 1u) && fpd::fits(cpu, mem, req, conf, cf[j], mf[j], lab[j], cu[j]);
+                    }
                     const uint32_t prim = ST == FP_STRATEGY_SPREAD        ? cnt[j]
                                           : ST == FP_STRATEGY_PACK        ? cf[j] - cpu
                                           : ST == FP_STRATEGY_FILL_LOWEST ? ~cf[j]
                                                                           : 0u;
-                    const uint32_t hi = pmh[j] | (prim >> (32 - KEY_NODE_BITS));
+                    uint32_t hi;
+                    if constexpr (KEEP_PMH) hi = pmh[j] | (prim >> (32 - NB));
+                    else hi = (nd[j] & ~nmask) | (prim >> (32 - NB));
+                    if constexpr (RX) hi |= hoph;
                     if constexpr (SP) {
                         // the node field carries n << 6 | domain: the same order (the domain is a function
                         // of n), and the winner's domain reaches every thread with the winner
-                        const uint32_t lo = (prim << KEY_NODE_BITS) | nd[j];
+                        const uint32_t lo = (prim << NB) | (KEEP_PMH ? nd[j] : nd[j] & nmask);
                         const uint64_t key = ((uint64_t)hi << 32) | lo;
                         best = min64(best, ok ? ((pbits >> j) & 1u ? key : KEY_SKEW) : KEY_NONE);
                     } else {
-                        const uint32_t lo = (prim << KEY_NODE_BITS) | (t + (uint32_t)BLK * j);
+                        const uint32_t lo = (prim << NB) | (t + (uint32_t)BLK * j);
                         const uint64_t key = ((uint64_t)hi << 32) | lo;
                         best = min64(best, ok ? key : KEY_NONE);
                     }
                 }
             };
-            switch (strat) {  // uniform
-            case FP_STRATEGY_SPREAD: local_min(std::integral_constant<uint32_t, FP_STRATEGY_SPREAD>{}); break;
-            case FP_STRATEGY_PACK: local_min(std::integral_constant<uint32_t, FP_STRATEGY_PACK>{}); break;
-            case FP_STRATEGY_FILL_LOWEST: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FILL_LOWEST>{}); break;
-            default: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FIRST_FIT>{}); break;
+            auto by_strategy = [&](auto relax_c) {
+                switch (strat) {  // uniform
+                case FP_STRATEGY_SPREAD: local_min(std::integral_constant<uint32_t, FP_STRATEGY_SPREAD>{}, relax_c); break;
+                case FP_STRATEGY_PACK: local_min(std::integral_constant<uint32_t, FP_STRATEGY_PACK>{}, relax_c); break;
+                case FP_STRATEGY_FILL_LOWEST: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FILL_LOWEST>{}, relax_c); break;
+                default: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FIRST_FIT>{}, relax_c); break;
+                }
+            };
+            if constexpr (FB) {
+                // a container that requires none of the bits the chain gives up cannot relax (uniform):
+                // the 2.6 loop, hop 0 in every key
+                if ((req & ~keep[3]) != 0u) by_strategy(std::true_type{});
+                else by_strategy(std::false_type{});
+            } else {
+                // The same switch as by_strategy, spelled out on purpose: keep it a plain switch at this
+                // level.  Routed through the lambda, the compiler laid the SP = true kernels out
+                // differently (branches where the selects were) and they measured 1 to 4 % slower; written
+                // like this the FB = false kernels are, instruction for instruction, the kernels from
+                // before the chain existed.  After a change here, compare their assembly
+                // and their time with the build before it
+                switch (strat) {  // uniform
+                case FP_STRATEGY_SPREAD: local_min(std::integral_constant<uint32_t, FP_STRATEGY_SPREAD>{}, std::false_type{}); break;
+                case FP_STRATEGY_PACK: local_min(std::integral_constant<uint32_t, FP_STRATEGY_PACK>{}, std::false_type{}); break;
+                case FP_STRATEGY_FILL_LOWEST: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FILL_LOWEST>{}, std::false_type{}); break;
+                default: local_min(std::integral_constant<uint32_t, FP_STRATEGY_FIRST_FIT>{}, std::false_type{}); break;
+                }
             }
 
             // ---- wave min, then block min over the per-wave slots ----
@@ -348,7 +460,7 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
 
             // ---- the winner ----
             const bool placed = SP ? best < KEY_SKEW : best != KEY_NONE;
-            const uint32_t nf = (uint32_t)best & ((1u << KEY_NODE_BITS) - 1u);
+            const uint32_t nf = (uint32_t)best & ((1u << NB) - 1u);
             const uint32_t n = SP ? nf >> DOM_BITS : nf;
             if (placed && (n & (uint32_t)(BLK - 1)) == t) {
                 const uint32_t J = n / (uint32_t)BLK;
@@ -373,6 +485,9 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
             if (t == 0) {
                 a.assign[cb + idx] = placed ? n : FP_NONE;
                 a.reason[cb + idx] = (uint8_t)(placed ? FP_REASON_OK : SP && best == KEY_SKEW ? FP_REASON_SKEW : FP_REASON_NOFIT);
+                if constexpr (FB) {
+                    if (a.hops) a.hops[cb + idx] = (uint8_t)(placed ? (uint32_t)(best >> KEY_HOP_SHIFT) : 0u);
+                }
             }
         }
     }
@@ -404,6 +519,15 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     }
 }
 
+template <bool SP, bool FB>
+void launch_policy(const PolicyArgs &a, uint32_t S, uint32_t N, hipStream_t st) {
+    if (N <= 64) k_policy<64, 1, SP, FB><<<S, 64, 0, st>>>(a);
+    else if (N <= 1024) k_policy<1024, 1, SP, FB><<<S, 1024, 0, st>>>(a);
+    else if (N <= 2048) k_policy<1024, 2, SP, FB><<<S, 1024, 0, st>>>(a);
+    else if (N <= 4096) k_policy<1024, 4, SP, FB><<<S, 1024, 0, st>>>(a);
+    else k_policy<1024, 8, SP, FB><<<S, 1024, 0, st>>>(a);
+}
+
 static inline unsigned grid_for(size_t n, unsigned block) {
     size_t g = (n + block - 1) / block;
     if (g > 65535u * 4) g = 65535u * 4;
@@ -428,7 +552,8 @@ int policy_sort_tmp(hipStream_t st, uint32_t S, size_t SC, size_t *bytes) {
 }  // namespace
 
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                                   uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew) {
+                                   uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
+                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops) {
     const uint32_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
     // this call resets the arena the last first-fit call's range words live in (fp_ctx_place_path)
     c->last_rng = nullptr;
@@ -442,6 +567,7 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     if (C && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable)) return FP_EINVAL;
     hipStream_t st = c->stream;
     const bool sp = domain && max_skew;  // SPEC.md 2.7: either pointer null = no constraint anywhere
+    const bool fb = relax_mask && n_hops;  // SPEC.md 2.8: either pointer null = no fallback anywhere
 
     size_t sort_tmp = 0;
     if (C)
@@ -455,6 +581,10 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     FP_HIP(hipGetLastError());
     if (sp && N) {
         k_policy_check_domain<<<grid_for((size_t)S * N, 256), 256, 0, st>>>(domain, max_skew, (size_t)S * N, N, bad, c->d_err);
+        FP_HIP(hipGetLastError());
+    }
+    if (fb) {
+        k_policy_check_hops<<<1, 256, 0, st>>>(n_hops, S, bad, c->d_err);
         FP_HIP(hipGetLastError());
     }
     if (C == 0) {  // nothing to place: every scenario costs (0 rejected, 0 nodes used)
@@ -498,23 +628,20 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     a.node_count = node_count;
     a.strategy = strategy; a.preferred = preferred;
     a.domain = sp ? domain : nullptr; a.max_skew = sp ? max_skew : nullptr;
+    a.relax_mask = fb ? relax_mask : nullptr; a.n_hops = fb ? n_hops : nullptr;
     a.assign = b->assign; a.reason = b->reason; a.cost = b->cost;
+    a.hops = fb ? hops : nullptr;
     a.bad = bad;
     fp_prof_begin(c, FP_K_PLACE, &ev);
-    if (sp) {
-        if (N <= 64) k_policy<64, 1, true><<<S, 64, 0, st>>>(a);
-        else if (N <= 1024) k_policy<1024, 1, true><<<S, 1024, 0, st>>>(a);
-        else if (N <= 2048) k_policy<1024, 2, true><<<S, 1024, 0, st>>>(a);
-        else if (N <= 4096) k_policy<1024, 4, true><<<S, 1024, 0, st>>>(a);
-        else k_policy<1024, 8, true><<<S, 1024, 0, st>>>(a);
-    } else {
-        if (N <= 64) k_policy<64, 1, false><<<S, 64, 0, st>>>(a);
-        else if (N <= 1024) k_policy<1024, 1, false><<<S, 1024, 0, st>>>(a);
-        else if (N <= 2048) k_policy<1024, 2, false><<<S, 1024, 0, st>>>(a);
-        else if (N <= 4096) k_policy<1024, 4, false><<<S, 1024, 0, st>>>(a);
-        else k_policy<1024, 8, false><<<S, 1024, 0, st>>>(a);
-    }
+    if (sp && fb) launch_policy<true, true>(a, S, N, st);
+    else if (sp) launch_policy<true, false>(a, S, N, st);
+    else if (fb) launch_policy<false, true>(a, S, N, st);
+    else launch_policy<false, false>(a, S, N, st);
     FP_HIP(hipGetLastError());
     fp_prof_end(c, FP_K_PLACE, ev);
+    if (hops && !fb) {
+        k_policy_zero_hops<<<grid_for(SC, 256), 256, 0, st>>>(hops, SC, bad);
+        FP_HIP(hipGetLastError());
+    }
     return FP_OK;
 }

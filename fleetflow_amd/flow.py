@@ -92,19 +92,43 @@ class PlacementPolicy:
     """The tenant PlacementPolicy subset the planner reads (controlplane model.rs:56-95): one of the
     three strategy constants (None = first fit), the soft ``preferred_labels`` map and the hard
     ``SpreadConstraint{topology_key, max_skew}`` (model.rs:56-63; SPEC.md 2.7), which constrains when
-    both fields are set and ``max_skew`` >= 1.  fallback_policy and resource_quota are not read
-    (DESIGN.md 4.8).  Two policies compare equal on strategy and preferred labels, the fields SPEC.md 2.6
-    reads; compare ``spread`` for the constraint."""
+    both fields are set and ``max_skew`` >= 1, and ``FallbackPolicy{relax_order, max_hops}``
+    (model.rs:47-54; SPEC.md 2.8): the label keys a service may give up, in that order, when the pool that
+    matches its required labels has no feasible server.  resource_quota is not read.  Two
+    policies compare equal on strategy and preferred labels, the fields SPEC.md 2.6 reads; compare
+    ``spread`` for the constraint and ``fallback`` for the chain."""
     strategy: str | None = None
     preferred_labels: dict[str, str] = field(default_factory=dict)
     spread_topology_key: str | None = field(default=None, compare=False)
     spread_max_skew: int | None = field(default=None, compare=False)
+    fallback_relax_order: tuple[str, ...] = field(default=(), compare=False)
+    fallback_max_hops: int | None = field(default=None, compare=False)
 
     def __post_init__(self):
         if self.strategy is not None and self.strategy not in POLICY_STRATEGIES:
             raise ValueError(f"unknown placement strategy '{self.strategy}' (expected {'|'.join(POLICY_STRATEGIES)})")
         if self.spread_max_skew is not None and not 0 <= self.spread_max_skew <= U32_MAX:
             raise ValueError(f"spread max_skew must be in 0..{U32_MAX}, got {self.spread_max_skew!r}")
+        self.fallback_relax_order = tuple(self.fallback_relax_order)
+        _ = self.fallback  # validates the chain
+
+    @property
+    def fallback(self) -> tuple[str, ...]:
+        """The label keys the chain gives up, one per hop: ``relax_order[:max_hops]`` (``max_hops`` None =
+        every key).  Empty = no fallback (no keys, or ``max_hops`` 0).  A ``max_hops`` that is no integer
+        >= 0, or more than FP_FALLBACK_MAX_HOPS effective hops, is a ValueError."""
+        from ._lib import FP_FALLBACK_MAX_HOPS
+        hops = self.fallback_max_hops
+        if hops is not None and (isinstance(hops, bool) or not isinstance(hops, int) or hops < 0):
+            raise ValueError(f"fallback max_hops must be an integer >= 0, got {hops!r}")
+        keys = tuple(self.fallback_relax_order)
+        if any(not isinstance(k, str) or not k or "=" in k for k in keys):
+            raise ValueError(f"fallback relax_order takes label keys (such as \"class\"), got {keys!r}")
+        keys = keys if hops is None else keys[:hops]
+        if len(keys) > FP_FALLBACK_MAX_HOPS:
+            raise ValueError(f"fallback chain of {len(keys)} hops (at most {FP_FALLBACK_MAX_HOPS}): shorten relax_order "
+                             "or set max_hops")
+        return keys
 
     @property
     def spread(self) -> tuple[str, int] | None:
@@ -120,7 +144,8 @@ class PlacementPolicy:
 
     @property
     def active(self) -> bool:
-        return self.strategy is not None or bool(self.preferred_labels) or self.spread is not None
+        return (self.strategy is not None or bool(self.preferred_labels) or self.spread is not None
+                or bool(self.fallback))
 
 
 @dataclass
@@ -257,6 +282,16 @@ class LabelDict:
             m |= 1 << self.bits[lab]
         return m
 
+    def key_mask(self, key: str) -> int:
+        """The bits of every ``key=...`` label of the dictionary: what a fallback hop on ``key`` gives up
+        (SPEC.md 2.8).  A key no label uses gives 0."""
+        prefix = key + "="
+        m = 0
+        for lab, bit in self.bits.items():
+            if lab.startswith(prefix):
+                m |= 1 << bit
+        return m
+
 
 @dataclass
 class Plan:
@@ -275,6 +310,11 @@ class Plan:
     # the hard topology spread the assignment was made under (SPEC.md 2.7); None = no constraint
     spread_topology_key: str | None = None
     spread_max_skew: int | None = None
+    # the fallback chain the assignment was made under (SPEC.md 2.8); no keys = no fallback.  relaxed:
+    # service -> the label keys it required and gave up (services placed at hop >= 1 only)
+    fallback_relax_order: list[str] = field(default_factory=list)
+    fallback_max_hops: int | None = None
+    relaxed: dict[str, list[str]] = field(default_factory=dict)
 
 
 def spread_domains(nodes: list[Server], topology_key: str) -> tuple[list[int], list[bool]]:
@@ -348,8 +388,12 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
     listing a name twice (positions != vertices) takes the per-output calls.
 
     ``policy`` (or, without one, the stage's parsed ``placement`` node) selects a placement strategy,
-    soft preferred labels (SPEC.md 2.6) and a hard topology spread (SPEC.md 2.7): levels, orders and
-    candidates are computed as without one, and the assignment comes from ``Planner.place_policy``.
+    soft preferred labels (SPEC.md 2.6), a hard topology spread (SPEC.md 2.7) and a fallback chain
+    (SPEC.md 2.8): levels, orders and candidates are computed as without one, and the assignment comes
+    from ``Planner.place_policy``, or ``Planner.place_policy_fallback`` when the policy has a chain.
+    Under a chain each hop gives up every ``key=...`` label of one key (``LabelDict.key_mask`` over the
+    stage's dictionary); ``Plan.relaxed`` names, per service placed at hop >= 1, the keys it required
+    and gave up.
     Under a spread constraint the servers' ``topology_key=value`` labels give the domains
     (``spread_domains``); a server without the key goes to the policy call as unschedulable and
     receives nothing, and a service some server fits but none within the skew is rejected as "SKEW".
@@ -361,7 +405,7 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
     pol = policy if policy is not None else stage.placement
     if pol is not None and not pol.active:
         pol = None
-    assignment, rejected, candidates = {}, {}, {}
+    assignment, rejected, candidates, relaxed = {}, {}, {}, {}
     if not services:
         return Plan(stage_name, [], {}, [], assignment, rejected, candidates)
     if not nodes:
@@ -399,9 +443,19 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
             domain, has_key = spread_domains(nodes, pol.spread[0])
             max_skew = pol.spread[1]
             ntab = (*ntab[:4], [s if k else 0 for s, k in zip(ntab[4], has_key)])
-        assign, reason, _, _ = p.place_policy(cont, ntab, pol.strategy if pol.strategy is not None else 0,
-                                              preferred=pmask, level=[lvl_v[n] for n in names], domain=domain,
-                                              max_skew=max_skew)
+        strategy = pol.strategy if pol.strategy is not None else 0
+        if pol.fallback:
+            ld = _stage_labels(names, flow, nodes, pol.preferred)
+            assign, reason, hops, _, _ = p.place_policy_fallback(cont, ntab, strategy, [ld.key_mask(k) for k in pol.fallback],
+                                                                 preferred=pmask, level=[lvl_v[n] for n in names],
+                                                                 domain=domain, max_skew=max_skew)
+            for v, n in enumerate(names):
+                if assign[v] != NONE and hops[v]:
+                    required = {lab.split("=", 1)[0] for lab in flow.services.get(n, Service()).labels}
+                    relaxed[n] = [k for k in pol.fallback[:int(hops[v])] if k in required]
+        else:
+            assign, reason, _, _ = p.place_policy(cont, ntab, strategy, preferred=pmask, level=[lvl_v[n] for n in names],
+                                                  domain=domain, max_skew=max_skew)
         placed = (placed[0], placed[1], assign, reason, None)
     if placed is not None:
         first, count, assign, reason, _ = placed
@@ -417,6 +471,9 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
         plan.strategy, plan.preferred = pol.strategy, pol.preferred
         if pol.spread is not None:
             plan.spread_topology_key, plan.spread_max_skew = pol.spread
+        if pol.fallback:
+            plan.fallback_relax_order, plan.fallback_max_hops = list(pol.fallback_relax_order), pol.fallback_max_hops
+            plan.relaxed = relaxed
     return plan
 
 

@@ -172,9 +172,10 @@ def parse_stage(node) -> tuple[str, Stage, dict[str, Service]]:
 
 
 def parse_placement(node, stage_name: str) -> PlacementPolicy:
-    """``placement strategy="spread_across_pool" { prefer "region=tokyo"; spread "region" max-skew=1 }``:
-    the tenant PlacementPolicy's strategy constant, soft preferred labels and hard
-    SpreadConstraint{topology_key, max_skew} (controlplane model.rs:56-95)."""
+    """``placement strategy="spread_across_pool" { prefer "region=tokyo"; spread "region" max-skew=1;
+    fallback "class" "region" max-hops=2 }``: the tenant PlacementPolicy's strategy constant, soft preferred
+    labels, hard SpreadConstraint{topology_key, max_skew} and FallbackPolicy{relax_order, max_hops}
+    (controlplane model.rs:47-95; ``max-hops`` is optional)."""
     strategy = None
     if node.has("strategy"):
         strategy = as_str(node.get("strategy"))
@@ -183,6 +184,7 @@ def parse_placement(node, stage_name: str) -> PlacementPolicy:
                             f"(expected {'|'.join(POLICY_STRATEGIES)})")
     preferred: dict[str, str] = {}
     spread_key = spread_skew = None
+    relax_order, max_hops = (), None
     for ch in node.children or []:
         if ch.name == "prefer":
             for _, v in ch.entries:
@@ -201,7 +203,26 @@ def parse_placement(node, stage_name: str) -> PlacementPolicy:
             if not kdl.is_int(skew) or not 1 <= skew <= U32_MAX:
                 raise FlowError(f"stage {stage_name}: spread max-skew must be an integer in 1..{U32_MAX}, got {skew!r}")
             spread_key, spread_skew = key, skew
-    return PlacementPolicy(strategy, preferred, spread_key, spread_skew)
+        elif ch.name == "fallback":
+            keys = ch.args()
+            if not keys or any(not isinstance(k, str) or not k or "=" in k for k in keys):
+                raise FlowError(f"stage {stage_name}: fallback takes label keys in the order they are given up "
+                                f"(such as \"class\" \"region\"), got {keys!r}")
+            if len(set(keys)) != len(keys):
+                raise FlowError(f"stage {stage_name}: fallback names a label key twice: {keys!r}")
+            if any(k != "max-hops" for k, _ in ch.entries if k is not None):
+                raise FlowError(f"stage {stage_name}: fallback takes label keys and max-hops=<integer>, got "
+                                f"{[k for k, _ in ch.entries if k is not None]!r}")
+            hops = None
+            if ch.has("max-hops"):
+                hops = ch.get("max-hops")
+                if not kdl.is_int(hops) or hops < 0:
+                    raise FlowError(f"stage {stage_name}: fallback max-hops must be an integer >= 0, got {hops!r}")
+            relax_order, max_hops = tuple(keys), hops
+    try:
+        return PlacementPolicy(strategy, preferred, spread_key, spread_skew, relax_order, max_hops)
+    except ValueError as e:
+        raise FlowError(f"stage {stage_name}: {e}") from None
 
 
 # ---- parser/cloud.rs:46-140 (+ SPEC.md 4 capacity/labels/scheduling) ------------------------

@@ -2,7 +2,9 @@
 
 ``plan_to_json`` is the machine form carried to the control plane next to
 ``DeployRequest`` (crates/fleetflow-container/src/engine.rs:16-25):
-``{stage, order, levels, level_order, assign, rejected}``.
+``{stage, order, levels, level_order, assign, rejected}``, and for a plan made under a placement
+policy ``placement`` (``strategy``, ``preferred``, ``spread``, ``fallback``) and, under a fallback chain
+(SPEC.md 2.8), ``relaxed``: the label keys each relaxed service gave up.
 
 ``format_up_dry_run`` / ``format_deploy_dry_run`` reproduce the reference's
 ``fleet up --dry-run`` (crates/fleetflow/src/commands/up.rs:57-136) and
@@ -34,10 +36,14 @@ def plan_to_json(plan: Plan, indent: int | None = None) -> str:
         "candidates": {k: {"count": c, "first": f} for k, (c, f) in plan.candidates.items()},
     }
     spread = plan.spread_topology_key is not None
-    if plan.strategy is not None or plan.preferred or spread:  # made under a placement policy (SPEC.md 2.6, 2.7)
+    fallback = bool(plan.fallback_relax_order)
+    if plan.strategy is not None or plan.preferred or spread or fallback:  # made under a placement policy (SPEC.md 2.6-2.8)
         d["placement"] = {"strategy": plan.strategy, "preferred": plan.preferred}
         if spread:
             d["placement"]["spread"] = {"topology_key": plan.spread_topology_key, "max_skew": plan.spread_max_skew}
+        if fallback:
+            d["placement"]["fallback"] = {"relax_order": plan.fallback_relax_order, "max_hops": plan.fallback_max_hops}
+            d["relaxed"] = plan.relaxed
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
@@ -48,7 +54,9 @@ def plan_from_json(text: str) -> Plan:
                 d["level_order"], d["assign"], d["rejected"],
                 {k: (v["count"], v["first"]) for k, v in d.get("candidates", {}).items()},
                 pol.get("strategy"), list(pol.get("preferred") or []),
-                (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"))
+                (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"),
+                list((pol.get("fallback") or {}).get("relax_order") or []), (pol.get("fallback") or {}).get("max_hops"),
+                {k: list(v) for k, v in (d.get("relaxed") or {}).items()})
 
 
 def get_network_name(project: str, stage: str) -> str:
@@ -83,7 +91,8 @@ def _service_block(flow: Flow, stage: str, name: str, container_suffix: str, pla
             cnt, first = plan.candidates[name]
             lines.append(f"    é…ç½®å€™è£œ: {cnt} å°" + (f" (æœ€åˆ: {first})" if first else ""))
         if name in plan.assignment:
-            lines.append(f"    é…ç½®å…ˆ: {plan.assignment[name]}")
+            relaxed = plan.relaxed.get(name)  # SPEC.md 2.8: placed after giving these label keys up
+            lines.append(f"    é…ç½®å…ˆ: {plan.assignment[name]}" + (f" (ç·©å’Œ: {', '.join(relaxed)})" if relaxed else ""))
         elif name in plan.rejected:
             lines.append(f"    é…ç½®å…ˆ: (é…ç½®ä¸å¯: {plan.rejected[name]})")
         else:
@@ -95,9 +104,10 @@ _FOOTER = "[dry-run] å®Ÿéš›ã®æ“ä½œã¯è¡Œã‚ã‚Œã¾ã›ã‚“ã€‚--dry-run ã‚’å¤–ã—ã
 
 
 def _policy_lines(plan: Plan | None) -> list[str]:
-    """The placement strategy (SPEC.md 2.6) and the hard topology spread (2.7) a plan was made under;
-    nothing without either."""
-    if plan is None or (plan.strategy is None and not plan.preferred and plan.spread_topology_key is None):
+    """The placement strategy (SPEC.md 2.6), the hard topology spread (2.7) and the fallback chain (2.8) a
+    plan was made under; nothing without any."""
+    if plan is None or (plan.strategy is None and not plan.preferred and plan.spread_topology_key is None
+                        and not plan.fallback_relax_order):
         return []
     line = f"  é…ç½®æˆ¦ç•¥: {plan.strategy if plan.strategy is not None else 'first_fit'}"
     if plan.preferred:
@@ -105,6 +115,9 @@ def _policy_lines(plan: Plan | None) -> list[str]:
     lines = [line]
     if plan.spread_topology_key is not None:
         lines.append(f"  é…ç½®åˆ†æ•£ä¿è¨¼: {plan.spread_topology_key} (max_skew={plan.spread_max_skew})")
+    if plan.fallback_relax_order:
+        hops = "" if plan.fallback_max_hops is None else f" (max_hops={plan.fallback_max_hops})"
+        lines.append(f"  é…ç½®ãƒ•ã‚©ãƒ¼ãƒ«ãƒãƒƒã‚¯: {' â†’ '.join(plan.fallback_relax_order)}{hops}")
     return lines
 
 

@@ -343,6 +343,92 @@ class Planner:
         check(self._L.fp_place_batch_policy(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc)), "fp_place_batch_policy")
         return assign, reason, cost, (cf, mf, lab, cu, sched), nc
 
+    @staticmethod
+    def _relax_row(relax_mask):
+        """One scenario's relax masks as the FP_FALLBACK_MAX_HOPS words of the ABI (zero-padded)."""
+        row = [int(m) & 0xFFFFFFFF for m in relax_mask]
+        if len(row) > _lib.FP_FALLBACK_MAX_HOPS:
+            raise ValueError(f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+        return row + [0] * (_lib.FP_FALLBACK_MAX_HOPS - len(row))
+
+    def place_policy_fallback(self, cont, nodes, strategy, relax_mask, preferred=0, level=None, node_count=None, *,
+                              domain=None, max_skew=0, n_hops=None, want_hops=True):
+        """place_policy under a fallback chain (SPEC.md 2.8, fp_place_policy_fallback): ``relax_mask`` holds,
+        per hop, the required-label bits that hop gives up (at most FP_FALLBACK_MAX_HOPS masks), ``n_hops``
+        the number of hops (None = every mask given; the library refuses more than FP_FALLBACK_MAX_HOPS).  A
+        container goes to the feasible node of the smallest (hop, key); it gives a requirement up only when
+        no node of an earlier hop is feasible.  ``domain`` / ``max_skew`` as in place_policy.  Returns
+        (assign, reason, hops, nodes_after, node_count_after): hops[c] is the winner's hop (0 when rejected),
+        or None with ``want_hops`` False."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
+        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
+        C, N = cpu.size, cf.size
+        lv = _u32(level) if level is not None else None
+        nc = _u32(node_count).copy() if node_count is not None else None
+        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
+        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
+        self._need(lv is None or lv.size == C, "level must hold C entries")
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        dom = _u32(domain) if domain is not None else None
+        self._need(dom is None or dom.size == N, "domain must hold N entries")
+        self._need(0 <= int(max_skew) <= 0xFFFFFFFF, "max_skew must be a u32")
+        rm = _u32(self._relax_row(relax_mask))
+        nh = len(relax_mask) if n_hops is None else int(n_hops)
+        self._need(0 <= nh <= 0xFFFFFFFF, "n_hops must be a u32")
+        assign = np.empty(C, np.uint32)
+        reason = np.empty(C, np.uint8)
+        hops = np.empty(C, np.uint8) if want_hops else None
+        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
+        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
+        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        check(self._L.fp_place_policy_fallback(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
+                                               int(preferred) & 0xFFFFFFFF, p32(nc), p32(dom), int(max_skew), p32(rm),
+                                               nh, p32(assign), reason.ctypes.data_as(_lib.u8p),
+                                               hops.ctypes.data_as(_lib.u8p) if want_hops else None),
+              "fp_place_policy_fallback")
+        return assign, reason, hops, (cf, mf, lab, cu, sched), nc
+
+    def place_batch_policy_fallback(self, S, C, N, cont, nodes, strategy, preferred=None, level=None, node_count=None,
+                                    scen_base=0, *, domain=None, max_skew=None, relax_mask=None, n_hops=None,
+                                    want_hops=True):
+        """place_batch_policy under per-scenario fallback chains (SPEC.md 2.8): ``relax_mask``
+        ([S * FP_FALLBACK_MAX_HOPS], scenario-major) with ``n_hops`` ([S], 0 = no fallback in that scenario);
+        either one None is no fallback anywhere.  Returns (assign, reason, hops, cost, nodes_after,
+        node_count_after); hops is [S*C] u8, or None with ``want_hops`` False."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
+        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
+        lv = _u32(level) if level is not None else None
+        st = _u32([strategy_id(x) for x in strategy])
+        pf = _u32(preferred) if preferred is not None else None
+        nc = _u32(node_count).copy() if node_count is not None else None
+        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
+        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
+        self._need(lv is None or lv.size == S * C, "level must hold S * C entries")
+        self._need(st.size == S and (pf is None or pf.size == S), "strategy and preferred must hold S entries")
+        self._need(nc is None or nc.size == S * N, "node_count must hold S * N entries")
+        dom = sk = rm = nh = None
+        if domain is not None and max_skew is not None:
+            dom, sk = _u32(domain), _u32(max_skew)
+            self._need(dom.size == S * N and sk.size == S, "domain must hold S * N and max_skew S entries")
+        if relax_mask is not None and n_hops is not None:
+            rm, nh = _u32(relax_mask).reshape(-1), _u32(n_hops)
+            self._need(rm.size == S * _lib.FP_FALLBACK_MAX_HOPS and nh.size == S,
+                       "relax_mask must hold S * FP_FALLBACK_MAX_HOPS and n_hops S entries")
+        assign = np.empty(S * C, np.uint32)
+        reason = np.empty(S * C, np.uint8)
+        hops = np.empty(S * C, np.uint8) if want_hops else None
+        cost = np.empty(S, np.uint64)
+        b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
+                    _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
+        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        check(self._L.fp_place_batch_policy_fallback(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc), p32(dom), p32(sk),
+                                                     p32(rm), p32(nh),
+                                                     hops.ctypes.data_as(_lib.u8p) if want_hops else None),
+              "fp_place_batch_policy_fallback")
+        return assign, reason, hops, cost, (cf, mf, lab, cu, sched), nc
+
     def feasibility(self, cont, nodes, bitmap=True):
         cpu, mem, req, conf = (_u32(x) for x in cont)
         cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
@@ -386,6 +472,34 @@ class Planner:
         self._dev(lambda: check(self._L.fp_dev_place_batch_policy(self._ctx, ct.byref(db.struct()), p(strategy_t),
                                                                   p(preferred_t), p(count_t)),
                                 "fp_dev_place_batch_policy"))
+
+    def dev_place_batch_policy_fallback(self, db: "DevBatch", strategy_t, preferred_t=None, count_t=None, *,
+                                        domain_t=None, max_skew_t=None, relax_mask_t=None, n_hops_t=None, hops_t=None):
+        """fp_dev_place_batch_policy_fallback: dev_place_batch_policy under the fallback chains of SPEC.md
+        2.8 -- ``relax_mask_t`` [S * FP_FALLBACK_MAX_HOPS] with ``n_hops_t`` [S] (int32 storage of u32
+        values; either one None is no fallback), ``hops_t`` [S*C] uint8 out or None.  An n_hops above
+        FP_FALLBACK_MAX_HOPS is found on the device: nothing is written and sync() raises FP_EINVAL.
+        Returns hops_t."""
+        self._need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
+        self._need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
+        self._need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
+        if domain_t is None or max_skew_t is None:
+            domain_t = max_skew_t = None
+        else:
+            self._need(domain_t.numel() == db.S * db.N and max_skew_t.numel() == db.S,
+                       "domain_t must hold S * N and max_skew_t S entries")
+        if relax_mask_t is None or n_hops_t is None:
+            relax_mask_t = n_hops_t = None
+        else:
+            self._need(relax_mask_t.numel() == db.S * _lib.FP_FALLBACK_MAX_HOPS and n_hops_t.numel() == db.S,
+                       "relax_mask_t must hold S * FP_FALLBACK_MAX_HOPS and n_hops_t S entries")
+        self._need(hops_t is None or (hops_t.numel() == db.S * db.C and hops_t.element_size() == 1),
+                   "hops_t must hold S * C bytes")
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._dev(lambda: check(self._L.fp_dev_place_batch_policy_fallback(
+            self._ctx, ct.byref(db.struct()), p(strategy_t), p(preferred_t), p(count_t), p(domain_t), p(max_skew_t),
+            p(relax_mask_t), p(n_hops_t), p(hops_t)), "fp_dev_place_batch_policy_fallback"))
+        return hops_t
 
     def dev_argmin_cost(self, cost_t, out_t):
         self._dev(lambda: check(self._L.fp_dev_argmin_cost(self._ctx, cost_t.data_ptr(), cost_t.numel(),

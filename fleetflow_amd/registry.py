@@ -93,10 +93,12 @@ def node_table(rows: list[dict]) -> list[Server]:
 
 def placement_policy(tenant_row: dict | None) -> PlacementPolicy | None:
     """A tenant row's ``placement_policy`` (as JSON; model.rs:82-95) -> the planner's policy: its
-    ``strategy`` constant, soft ``preferred_labels`` map and hard ``spread_constraint``
-    (``topology_key``, ``max_skew``; SPEC.md 2.7).  None when the row has no policy; a strategy that is
-    none of the three constants, or a constraint with a key and a ``max_skew`` below 1, is a ValueError.
-    ``fallback_policy`` and ``resource_quota`` are not read."""
+    ``strategy`` constant, soft ``preferred_labels`` map, hard ``spread_constraint``
+    (``topology_key``, ``max_skew``; SPEC.md 2.7) and ``fallback_policy`` (``relax_order``, ``max_hops``;
+    SPEC.md 2.8).  None when the row has no policy; a strategy that is none of the three constants, a
+    constraint with a key and a ``max_skew`` below 1, a ``relax_order`` that is no list of label keys, a
+    ``max_hops`` that is no integer >= 0, or a chain of more than four effective hops is a ValueError.
+    ``resource_quota`` is not read."""
     pol = (tenant_row or {}).get("placement_policy")
     if pol is None:
         return None
@@ -112,7 +114,13 @@ def placement_policy(tenant_row: dict | None) -> PlacementPolicy | None:
         key = str(key)
     else:
         skew = None
-    return PlacementPolicy(strategy, {str(k): str(v) for k, v in pref.items()}, key, skew)
+    fb = pol.get("fallback_policy") or {}
+    if not isinstance(fb, dict):
+        raise ValueError(f"fallback_policy must be an object with relax_order and max_hops, got {fb!r}")
+    order, hops = fb.get("relax_order") or (), fb.get("max_hops")
+    if isinstance(order, str) or not all(isinstance(k, str) for k in order):
+        raise ValueError(f"fallback_policy: relax_order must be a list of label keys, got {order!r}")
+    return PlacementPolicy(strategy, {str(k): str(v) for k, v in pref.items()}, key, skew, tuple(order), hops)
 
 
 def pool_required_labels(pool: dict | None) -> list[str]:

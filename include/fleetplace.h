@@ -18,6 +18,8 @@
  *                        crates/fleetflow-controlplane/src/model.rs:56-95 (schema nothing reads upstream)
  *   fp_place_policy_spread <- new: the same under the policy's SpreadConstraint{topology_key, max_skew}
  *                        crates/fleetflow-controlplane/src/model.rs:56-63
+ *   fp_place_policy_fallback <- new: the same under the policy's FallbackPolicy{relax_order, max_hops}
+ *                        crates/fleetflow-controlplane/src/model.rs:47-54
  *   fp_feasibility    <- new: stage-2 containers x nodes feasibility/score sweep
  *   fp_dev_feasibility_batch <- new: the same sweep over many what-if scenarios
  *
@@ -237,6 +239,32 @@ int fp_place_policy_spread(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes,
 int fp_place_batch_policy_spread(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
                                  const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
                                  const uint32_t *max_skew);
+/* Scored placement under a fallback chain (SPEC.md 2.8), the PlacementPolicy's
+ * FallbackPolicy{relax_order, max_hops} (model.rs:47-54): the required labels a container may give up, hop
+ * by hop, when the pool that matches them has no feasible node.  relax_mask[h - 1] holds the label bits hop h
+ * gives up (every key=value bit of one label key; any 32-bit masks are legal, they may overlap or be 0),
+ * n_hops <= FP_FALLBACK_MAX_HOPS is the number of hops.  With cum[0] = 0, cum[h] = cum[h-1] | relax_mask[h-1]
+ * and req_h = req_labels & ~cum[h], the hop of node n is the smallest h <= n_hops with
+ * (labels[n] & req_h) == req_h.  A node is feasible when it is feasible for fp_place_policy_spread with
+ * the label test replaced by "has a hop"; the container goes to the feasible node with the smallest
+ * (hop, key), key being fp_place_policy's.  So a requirement is given up only when no node of any earlier
+ * hop is feasible -- without capacity, in conflict, or outside max_skew.  hops_out (nullable) receives
+ * the winner's hop, 0 for a rejected or CYCLE container.  FP_REASON_NOFIT: no node fits even under
+ * req_{n_hops}; FP_REASON_SKEW: some node does, none within max_skew.  The cost is unchanged: a relaxed
+ * placement counts as placed.  n_hops = 0 is no fallback: that scenario is exactly fp_place_policy_spread
+ * and its relax_mask is not read.  relax_mask = NULL or n_hops = NULL (batch entries) is no fallback
+ * anywhere.  domain = NULL or max_skew = NULL is still no spread constraint.  An n_hops above
+ * FP_FALLBACK_MAX_HOPS is FP_EINVAL and nothing is written. */
+#define FP_FALLBACK_MAX_HOPS 4
+int fp_place_policy_fallback(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32_t *level,
+                             uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                             const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                             uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out);
+/* relax_mask: [S][FP_FALLBACK_MAX_HOPS]; n_hops: [S]; hops_out: [S][C] or NULL */
+int fp_place_batch_policy_fallback(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                                   const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                                   const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
+                                   uint8_t *hops_out);
 /* Stage 2: first feasible node (FP_NONE) and feasible-node count per container on
  * the given node state; bitmap_out (nullable, ceil(C/64) * N words) holds
  * bit (c, n) at word [(c/64) * N + n], bit c % 64. */
@@ -291,6 +319,12 @@ int fp_dev_place_batch_policy(fp_ctx *ctx, const fp_batch *b, const uint32_t *st
 int fp_dev_place_batch_policy_spread(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
                                      const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
                                      const uint32_t *max_skew);
+/* As fp_place_batch_policy_fallback on device pointers.  An n_hops above FP_FALLBACK_MAX_HOPS is found on
+ * the device with the strategy check: nothing is written and fp_ctx_sync() reports FP_EINVAL. */
+int fp_dev_place_batch_policy_fallback(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                                       const uint32_t *preferred_labels, uint32_t *node_count,
+                                       const uint32_t *domain, const uint32_t *max_skew, const uint32_t *relax_mask,
+                                       const uint32_t *n_hops, uint8_t *hops_out);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

@@ -22,6 +22,7 @@ pub const FP_STRATEGY_PACK: u32 = 2;
 pub const FP_STRATEGY_FILL_LOWEST: u32 = 3;
 pub const FP_POLICY_MAX_NODES: u32 = 8192;
 pub const FP_SPREAD_MAX_DOMAINS: u32 = 64;
+pub const FP_FALLBACK_MAX_HOPS: u32 = 4;
 pub const FP_K_PLACE: c_int = 0;
 pub const FP_K_SORT: c_int = 1;
 pub const FP_K_FEAS: c_int = 2;
@@ -156,6 +157,14 @@ unsafe extern "C" {
     pub fn fp_place_batch_policy_spread(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
                                         preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
                                         max_skew: *const u32) -> c_int;
+    pub fn fp_place_policy_fallback(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
+                                    strategy: u32, preferred_labels: u32, node_count: *mut u32, domain: *const u32,
+                                    max_skew: u32, relax_mask: *const u32, n_hops: u32, assign_out: *mut u32,
+                                    reason_out: *mut u8, hops_out: *mut u8) -> c_int;
+    pub fn fp_place_batch_policy_fallback(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                          preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                          max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
+                                          hops_out: *mut u8) -> c_int;
     pub fn fp_feasibility(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, first_out: *mut u32,
                           count_out: *mut u32, bitmap_out: *mut u64) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,
@@ -178,6 +187,10 @@ unsafe extern "C" {
     pub fn fp_dev_place_batch_policy_spread(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
                                             preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
                                             max_skew: *const u32) -> c_int;
+    pub fn fp_dev_place_batch_policy_fallback(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                              preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                              max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
+                                              hops_out: *mut u8) -> c_int;
     pub fn fp_dev_argmin_cost(ctx: *mut fp_ctx, cost: *const u64, n: u32, best_dev: *mut u32) -> c_int;
     pub fn fp_dev_gen_batch(ctx: *mut fp_ctx, seed: u64, b: *const fp_batch, flags: u32) -> c_int;
 }

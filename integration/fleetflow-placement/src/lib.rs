@@ -165,6 +165,43 @@ impl Planner {
         Ok((assign, reason))
     }
 
+    /// Scored placement under a fallback chain (SPEC.md 2.8, fleetplace.h `fp_place_policy_fallback`), the
+    /// PlacementPolicy's `FallbackPolicy { relax_order, max_hops }`: `relax_mask[h - 1]` holds the required
+    /// label bits hop h gives up (at most `ffi::FP_FALLBACK_MAX_HOPS` hops, else FP_EINVAL).  A container
+    /// goes to the feasible node of the smallest (hop, key) and gives a requirement up only when no node of
+    /// an earlier hop is feasible.  `spread` is `place_policy_spread`'s `(domain, max_skew)`, None for no
+    /// constraint.  Returns (assign, reason, hops): hops[c] is the winner's hop, 0 when rejected.  No masks
+    /// is `place_policy_spread`.
+    pub fn place_policy_fallback(&mut self, c: &Containers, nodes: &mut Nodes, level: Option<&[u32]>, strategy: u32,
+                                 preferred_labels: u32, node_count: Option<&mut [u32]>, spread: Option<(&[u32], u32)>,
+                                 relax_mask: &[u32]) -> Result<(Vec<u32>, Vec<u8>, Vec<u8>), PlanError> {
+        let n = c.cpu_m.len();
+        let nn = nodes.cpu_free.len();
+        if !c.all_len(n) || !nodes.all_len(nn) || level.map_or(false, |l| l.len() != n)
+            || node_count.as_ref().map_or(false, |k| k.len() != nn) || spread.map_or(false, |(d, _)| d.len() != nn)
+            || relax_mask.len() > ffi::FP_FALLBACK_MAX_HOPS as usize {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        let mut ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_mut_ptr(),
+                                     mem_free: nodes.mem_free.as_mut_ptr(), labels: nodes.labels.as_ptr(),
+                                     conflict_used: nodes.conflict_used.as_mut_ptr(),
+                                     schedulable: nodes.schedulable.as_ptr() };
+        let (mut assign, mut reason, mut hops) = (vec![0u32; n], vec![0u8; n], vec![0u8; n]);
+        let count_ptr = node_count.map_or(std::ptr::null_mut(), |k| k.as_mut_ptr());
+        let mut masks = [0u32; ffi::FP_FALLBACK_MAX_HOPS as usize];
+        masks[..relax_mask.len()].copy_from_slice(relax_mask);
+        let (domain, max_skew) = spread.map_or((std::ptr::null(), 0), |(d, k)| (d.as_ptr(), k));
+        check(unsafe {
+            ffi::fp_place_policy_fallback(self.ctx, &cs, &mut ns, level.map_or(std::ptr::null(), |l| l.as_ptr()),
+                                          strategy, preferred_labels, count_ptr, domain, max_skew, masks.as_ptr(),
+                                          relax_mask.len() as u32, assign.as_mut_ptr(), reason.as_mut_ptr(),
+                                          hops.as_mut_ptr())
+        })?;
+        Ok((assign, reason, hops))
+    }
+
     /// One stage's whole dry-run plan in one call (fleetplace.h `fp_plan_stage`, the
     /// `fleet up --dry-run` path of up.rs:57-136): the legacy order, the Kahn levels and start
     /// order and, with `placement = Some((containers, nodes))` (container v = vertex v), the

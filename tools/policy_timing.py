@@ -21,6 +21,17 @@ round is a fresh process; with --parent-tree (a checkout of the commit to compar
 built) the rounds alternate with that tree's own tools/policy_timing.py, so the unconstrained calls of
 both builds are measured side by side in one run.  Writes profiles/policy_spread_timing.json: every
 round's figures, and their minimum, median and maximum.
+
+    python tools/policy_timing.py --fallback [--rounds R] [--parent-tree DIR]
+
+The fallback chain (SPEC.md 2.8) by the same method: per strategy the calls without a chain (the
+unconstrained call and the two constrained ones of --spread) and fp_dev_place_batch_policy_fallback with
+n_hops = 2 (class, region) and n_hops = 4 (class, region, arch, tier) over the generator's label
+dimensions (SPEC.md 3.2).  With --parent-tree the rounds alternate with that tree's `--spread-child`
+process, and every call without a chain is held against the parent build: its median may exceed the
+parent's maximum by at most the parent's own min-max range over the rounds (`within_margin`).  The
+calls with a chain have no target: their time, ns per placement and hop histogram are recorded.  Writes
+profiles/policy_fallback_timing.json.
 """
 import argparse
 import json
@@ -102,6 +113,96 @@ def spread_round(a):
     return out
 
 
+# the generator's label dimensions (SPEC.md 3.2): tier bits 0-2, region 3-6, class 7-10, arch 11-12
+FALLBACK_CHAINS = {"fb_h2": [0x780, 0x78], "fb_h4": [0x780, 0x78, 0x1800, 0x7]}
+
+
+def fallback_round(a):
+    """One process's figures: spread_round's calls, and the calls with a chain per FALLBACK_CHAINS."""
+    S, C, N = a.scenarios, a.containers, a.nodes
+    dev = torch.device("cuda", 0)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    rounds = -(-S // cus) if N > 64 else None
+    out = {}
+    with Planner(0) as p:
+        db = DevBatch.allocate(S, C, N, dev)
+        p.dev_gen_batch(SEED4, db, 7)
+        p.sync()
+        snap = db.node_snapshot()
+        skew = torch.ones(S, dtype=torch.int32, device=dev)
+        doms = {D: (torch.arange(N, dtype=torch.int32, device=dev) % D).repeat(S) for D in SPREAD_DOMAINS}
+        hops = torch.zeros(S * C, dtype=torch.uint8, device=dev)
+        chains = {}
+        for label, masks in FALLBACK_CHAINS.items():
+            row = masks + [0] * (_lib.FP_FALLBACK_MAX_HOPS - len(masks))
+            chains[label] = (torch.tensor(row * S, dtype=torch.int32, device=dev),
+                             torch.full((S,), len(masks), dtype=torch.int32, device=dev))
+        for name, sid in STRATEGIES:
+            st = torch.full((S,), sid, dtype=torch.int32, device=dev)
+            calls = [("off", lambda: p.dev_place_batch_policy(db, st))]
+            calls += [(f"on_D{D}", lambda D=D: p.dev_place_batch_policy(db, st, domain_t=doms[D], max_skew_t=skew))
+                      for D in SPREAD_DOMAINS]
+            calls += [(label, lambda label=label: p.dev_place_batch_policy_fallback(
+                db, st, relax_mask_t=chains[label][0], n_hops_t=chains[label][1], hops_t=hops)) for label in FALLBACK_CHAINS]
+            out[name] = {}
+            for label, call in calls:
+                wall, place_ms, sort_ms = timed(p, db, snap, call, a.steps, a.warmup)
+                reason = db.reason
+                rec = {"ms_per_call": wall, "place_kernel_ms": place_ms, "sort_ms": sort_ms,
+                       "rejected": int((reason != 0).sum().item()), "skew": int((reason == _lib.REASON_SKEW).sum().item())}
+                if rounds:
+                    rec["ns_per_placement"] = 1e6 * place_ms / (rounds * C)
+                if label in FALLBACK_CHAINS:  # placed containers per hop
+                    rec["hop_histogram"] = torch.bincount(hops[reason == 0].long(),
+                                                          minlength=_lib.FP_FALLBACK_MAX_HOPS + 1).tolist()
+                out[name][label] = rec
+    return out
+
+
+def fallback_main(a):
+    """The driver: starts every round as a child process and makes no GPU call itself."""
+    shape = ["--scenarios", str(a.scenarios), "--containers", str(a.containers), "--nodes", str(a.nodes), "--steps", str(a.steps),
+             "--warmup", str(a.warmup)]
+    new_rounds, parent_rounds = [], []
+    with tempfile.TemporaryDirectory() as tmp:
+        for r in range(a.rounds):
+            if a.parent_tree:
+                path = os.path.join(tmp, f"parent{r}.json")
+                tool = os.path.join(os.path.abspath(a.parent_tree), "tools", "policy_timing.py")
+                parent_rounds.append(_child([sys.executable, tool, *shape, "--spread-child", "--out", path],
+                                            os.path.abspath(a.parent_tree), path))
+            path = os.path.join(tmp, f"new{r}.json")
+            new_rounds.append(_child([sys.executable, os.path.abspath(__file__), *shape, "--fallback-child", "--out", path], ROOT, path))
+    plain = ["off"] + [f"on_D{D}" for D in SPREAD_DOMAINS]
+    out = {"shape": {"scenarios": a.scenarios, "containers": a.containers, "nodes": a.nodes, "flags": 7, "seed": SEED4},
+           "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "domain_map": "n % D", "max_skew": 1,
+           "chains": {k: [hex(m) for m in v] for k, v in FALLBACK_CHAINS.items()},
+           "order": "each round: the parent build's process, then this build's",
+           "margin": "a call without a chain: this build's median <= the parent's max + (the parent's max - min)",
+           "strategies": {}}
+    for name, _ in STRATEGIES:
+        rec = {}
+        for label in plain + list(FALLBACK_CHAINS):
+            runs = [r[name][label] for r in new_rounds]
+            rec[label] = {"place_kernel_ms": _stats([x["place_kernel_ms"] for x in runs]),
+                          "ms_per_call": _stats([x["ms_per_call"] for x in runs]),
+                          "place_kernel_ms_rounds": [x["place_kernel_ms"] for x in runs],
+                          "rejected": runs[0]["rejected"], "skew": runs[0]["skew"]}
+            if "ns_per_placement" in runs[0]:
+                rec[label]["ns_per_placement"] = _stats([x["ns_per_placement"] for x in runs])
+            if "hop_histogram" in runs[0]:
+                rec[label]["hop_histogram"] = runs[0]["hop_histogram"]
+        for label in plain if parent_rounds else []:
+            runs = [r[name][label] for r in parent_rounds]
+            st = _stats([x["place_kernel_ms"] for x in runs])
+            rec["parent_" + label] = {"place_kernel_ms": st, "ms_per_call": _stats([x["ms_per_call"] for x in runs]),
+                                      "place_kernel_ms_rounds": [x["place_kernel_ms"] for x in runs],
+                                      "rejected": runs[0]["rejected"]}
+            rec[label]["within_margin"] = rec[label]["place_kernel_ms"]["median"] <= st["max"] + (st["max"] - st["min"])
+        out["strategies"][name] = rec
+    return out
+
+
 def _child(cmd, cwd, out_path):
     subprocess.run(cmd, cwd=cwd, check=True, stdout=subprocess.DEVNULL)
     with open(out_path) as f:
@@ -157,14 +258,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--spread", action="store_true", help="the topology spread on and off (see above)")
-    ap.add_argument("--rounds", type=int, default=3, help="--spread: processes per build")
-    ap.add_argument("--parent-tree", default=None, help="--spread: a built checkout of the commit to compare with")
+    ap.add_argument("--rounds", type=int, default=3, help="--spread, --fallback: processes per build")
+    ap.add_argument("--parent-tree", default=None,
+                    help="--spread, --fallback: a built checkout of the commit to compare with")
     ap.add_argument("--spread-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--fallback", action="store_true", help="the fallback chain on and off (see above)")
+    ap.add_argument("--fallback-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "policy_spread_timing.json" if a.spread else "policy_timing.json")
-    if a.spread or a.spread_child:
-        out = spread_round(a) if a.spread_child else spread_main(a)
+        a.out = os.path.join(ROOT, "profiles", "policy_fallback_timing.json" if a.fallback else
+                             "policy_spread_timing.json" if a.spread else "policy_timing.json")
+    if a.spread or a.spread_child or a.fallback or a.fallback_child:
+        out = (spread_round(a) if a.spread_child else fallback_round(a) if a.fallback_child else
+               fallback_main(a) if a.fallback else spread_main(a))
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
