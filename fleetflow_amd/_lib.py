@@ -28,6 +28,11 @@ FP_POLICY_MAX_NODES = 8192
 FP_SPREAD_MAX_DOMAINS = 64
 # fallback chain (SPEC.md 2.8): at most this many hops, relax_mask rows hold this many words
 FP_FALLBACK_MAX_HOPS = 4
+# rejection diagnosis (SPEC.md 2.9): fp_why bits, the word indices of an fp_explain row and of a histogram
+WHY_CORDON, WHY_CPU, WHY_MEM, WHY_LABEL, WHY_CONFLICT = 1, 2, 4, 8, 16
+EXPLAIN_FAIL, EXPLAIN_ONLY, EXPLAIN_FEASIBLE, EXPLAIN_ALL, EXPLAIN_MISSING, EXPLAIN_NEAR = 0, 5, 10, 11, 12, 13
+EXPLAIN_WORDS = 16
+EXPLAIN_HIST_MIXED, EXPLAIN_HIST_FITS, EXPLAIN_HIST_SELECTED, EXPLAIN_HIST_WORDS = 5, 6, 7, 8
 # context options (fleetplace.h enum fp_option); FP_OPT_AUTO = the production default
 # ("segsort" is ignored by the library and kept for ABI stability)
 FP_OPT_AUTO = -1
@@ -118,6 +123,10 @@ SIGNATURES = {
     "fp_place_batch_policy_fallback": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u32p, u32p, u32p,
                                                   u8p]),
     "fp_dev_place_batch_policy_fallback": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fp_explain": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, ct.c_uint32, ct.c_uint32, u32p]),
+    "fp_explain_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), ct.c_uint32, u32p, u32p]),
+    "fp_dev_explain": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, ct.c_uint32, ct.c_uint32, vp]),
+    "fp_dev_explain_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), ct.c_uint32, vp, vp]),
     "fp_dev_argmin_cost": (ct.c_int, [vp, vp, ct.c_uint32, vp]),
     "fp_dev_gen_batch": (ct.c_int, [vp, ct.c_uint64, ct.POINTER(FpBatch), ct.c_uint32]),
 }

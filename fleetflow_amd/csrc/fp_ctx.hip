@@ -719,3 +719,95 @@ extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes
     const OutCopy o[] = {{first_out, dfirst, C * 4}, {count_out, dcount, C * 4}, {bitmap_out, dbits, WC * N * 8}};
     return copy_back_all(c, o, 3);
 }
+
+// ---- rejection diagnosis (SPEC.md 2.9, fp_explain.hip) ---------------------------
+extern "C" int fp_dev_explain(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *sel,
+                              uint32_t n_sel, uint32_t ignore_labels, uint32_t *rows_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_explain_impl(c, cs, ns, sel, n_sel, ignore_labels, rows_out));
+}
+
+extern "C" int fp_dev_explain_batch(fp_ctx *c, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
+                                    uint32_t *hist_out) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_explain_batch_impl(c, b, reason_mask, ignore_labels, hist_out));
+}
+
+extern "C" int fp_explain(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *sel, uint32_t n_sel,
+                          uint32_t ignore_labels, uint32_t *rows_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const size_t C = cs->n, N = ns->n;
+    if (!sel) n_sel = cs->n;
+    const size_t M = n_sel;
+    if (M == 0) return FP_OK;
+    if (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !rows_out) return FP_EINVAL;
+    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable))
+        return FP_EINVAL;
+    for (size_t i = 0; sel && i < M; ++i)
+        if (sel[i] >= C) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    int rc = fp_stage_reserve(c, C * 16 + N * 17 + M * (4 + FP_EXPLAIN_WORDS * 4) + 16 * 256);
+    if (rc) return rc;
+    fp_stage_reset(c);
+    fp_containers dc = *cs;
+    fp_nodes dn = *ns;
+    dc.cpu_m = stage_in(c, cs->cpu_m, C, &rc);
+    dc.mem_mib = stage_in(c, cs->mem_mib, C, &rc);
+    dc.req_labels = stage_in(c, cs->req_labels, C, &rc);
+    dc.conflict = stage_in(c, cs->conflict, C, &rc);
+    dn.cpu_free = stage_in(c, ns->cpu_free, N, &rc);
+    dn.mem_free = stage_in(c, ns->mem_free, N, &rc);
+    dn.labels = stage_in(c, ns->labels, N, &rc);
+    dn.conflict_used = stage_in(c, ns->conflict_used, N, &rc);
+    dn.schedulable = stage_in(c, ns->schedulable, N, &rc);
+    const uint32_t *dsel = stage_in(c, sel, M, &rc);
+    uint32_t *drows = stage_out<uint32_t>(c, M * FP_EXPLAIN_WORDS, &rc);  // 256-byte aligned
+    if (rc) return rc;
+    rc = fp_dev_explain_impl(c, &dc, &dn, dsel, n_sel, ignore_labels, drows);
+    if (rc) return rc;
+    const OutCopy o[] = {{rows_out, drows, M * FP_EXPLAIN_WORDS * 4}};
+    return copy_back_all(c, o, 1);
+}
+
+extern "C" int fp_explain_batch(fp_ctx *c, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
+                                uint32_t *hist_out) {
+    if (!c || !b) return FP_EINVAL;
+    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
+    const size_t SC = S * C, SN = S * N;
+    if (S == 0) return FP_OK;
+    if (S > 65535u) return FP_EOVERFLOW;
+    if (!hist_out) return FP_EINVAL;
+    if (C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || (reason_mask && !b->reason)))
+        return FP_EINVAL;
+    if (C && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable))
+        return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    int rc = fp_stage_reserve(c, SC * 17 + SN * 17 + S * (4 + FP_EXPLAIN_HIST_WORDS * 4) + 16 * 256);
+    if (rc) return rc;
+    fp_stage_reset(c);
+    fp_batch d = *b;
+    d.level = nullptr; d.assign = nullptr; d.cost = nullptr;
+    d.cpu_m = stage_in(c, b->cpu_m, SC, &rc);
+    d.mem_mib = stage_in(c, b->mem_mib, SC, &rc);
+    d.req_labels = stage_in(c, b->req_labels, SC, &rc);
+    d.conflict = stage_in(c, b->conflict, SC, &rc);
+    d.cpu_free = stage_in(c, b->cpu_free, C ? SN : 0, &rc);
+    d.mem_free = stage_in(c, b->mem_free, C ? SN : 0, &rc);
+    d.labels = stage_in(c, b->labels, C ? SN : 0, &rc);
+    d.conflict_used = stage_in(c, b->conflict_used, C ? SN : 0, &rc);
+    d.schedulable = stage_in(c, b->schedulable, C ? SN : 0, &rc);
+    d.reason = reason_mask ? stage_in(c, b->reason, SC, &rc) : nullptr;
+    const uint32_t *dign = stage_in(c, ignore_labels, S, &rc);
+    uint32_t *dhist = stage_out<uint32_t>(c, S * FP_EXPLAIN_HIST_WORDS, &rc);
+    if (rc) return rc;
+    rc = fp_dev_explain_batch_impl(c, &d, reason_mask, dign, dhist);
+    if (rc) return rc;
+    const OutCopy o[] = {{hist_out, dhist, S * FP_EXPLAIN_HIST_WORDS * 4}};
+    return copy_back_all(c, o, 1);
+}

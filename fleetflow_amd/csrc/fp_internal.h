@@ -136,6 +136,11 @@ int fp_dev_legacy_order_impl(fp_ctx *c, const fp_graph *g, uint32_t *perm);
 int fp_dev_feasibility_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,
                             uint32_t *first, uint32_t *count, uint64_t *bitmap);
 int fp_dev_feasibility_batch_impl(fp_ctx *c, const fp_batch *b, uint32_t *first, uint32_t *count);
+// rejection diagnosis (fp_explain.hip, SPEC.md 2.9); every pointer is device memory
+int fp_dev_explain_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *sel, uint32_t n_sel,
+                        uint32_t ignore_labels, uint32_t *rows);
+int fp_dev_explain_batch_impl(fp_ctx *c, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
+                              uint32_t *hist);
 // scored placement (fp_policy.hip, SPEC.md 2.6 and 2.7); every pointer is device memory.  domain [S][N]
 // and max_skew [S] are the topology spread of 2.7; either one null = no constraint.  relax_mask [S][4] and
 // n_hops [S] are the fallback chain of 2.8; either one null = no fallback.  hops [S][C] (nullable) receives

@@ -293,6 +293,37 @@ class LabelDict:
         return m
 
 
+# SPEC.md 2.9: the 2.3 predicates in the bit order of fp_why
+WHY_NAMES = ("CORDON", "CPU", "MEM", "LABEL", "CONFLICT")
+
+
+@dataclass
+class Why:
+    """Why a service has no server (SPEC.md 2.9, one fp_explain row): per cause the number of servers it
+    fails on (``fail``, non-exclusive) and the number where it is the sole blocker (``only``), the servers
+    that would still take it (``feasible``; > 0 only for SKEW rejections), the causes that fail on every
+    server (``universal``), the required labels no schedulable server carries (``missing_labels``,
+    ``key=value``) and the first server one cause away (``nearest``, a slug or None).  ``servers`` is the size of the table the counts are out of."""
+    fail: dict[str, int]
+    only: dict[str, int]
+    feasible: int
+    universal: list[str]
+    missing_labels: list[str]
+    nearest: str | None
+    servers: int = 0  # N, the servers of the table the diagnosis was taken on
+
+    @classmethod
+    def from_row(cls, row, labels: "LabelDict", slugs: list[str]) -> "Why":
+        from ._lib import EXPLAIN_ALL, EXPLAIN_FAIL, EXPLAIN_FEASIBLE, EXPLAIN_MISSING, EXPLAIN_NEAR, EXPLAIN_ONLY
+        row = [int(x) for x in row]
+        near = row[EXPLAIN_NEAR]
+        return cls({n: row[EXPLAIN_FAIL + k] for k, n in enumerate(WHY_NAMES)},
+                   {n: row[EXPLAIN_ONLY + k] for k, n in enumerate(WHY_NAMES)}, row[EXPLAIN_FEASIBLE],
+                   [n for k, n in enumerate(WHY_NAMES) if row[EXPLAIN_ALL] >> k & 1],
+                   [lab for lab, bit in labels.bits.items() if row[EXPLAIN_MISSING] >> bit & 1],
+                   slugs[near] if near != NONE else None, len(slugs))
+
+
 @dataclass
 class Plan:
     stage: str
@@ -315,6 +346,9 @@ class Plan:
     fallback_relax_order: list[str] = field(default_factory=list)
     fallback_max_hops: int | None = None
     relaxed: dict[str, list[str]] = field(default_factory=dict)
+    # rejection diagnosis (SPEC.md 2.9), plan_stage(..., explain=True): service -> Why for the services
+    # rejected NOFIT or SKEW, taken on the server table the placement left; empty otherwise
+    why: dict[str, Why] = field(default_factory=dict)
 
 
 def spread_domains(nodes: list[Server], topology_key: str) -> tuple[list[int], list[bool]]:
@@ -381,7 +415,8 @@ def _stage_tables(names: list[str], flow: Flow, nodes: list[Server], preferred=(
 
 
 def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
-               servers: list[Server] | None = None, policy: PlacementPolicy | None = None) -> Plan:
+               servers: list[Server] | None = None, policy: PlacementPolicy | None = None,
+               explain: bool = False) -> Plan:
     """Full planner output for one stage (SPEC.md 2): the `fleet up --dry-run`
     plan (up.rs:57-136).  One fp_plan_stage call -- A1 order, A2 levels, and with servers the stage-2
     candidates and the FFD plan -- when every service name appears once in the stage; a stage
@@ -397,7 +432,13 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
     Under a spread constraint the servers' ``topology_key=value`` labels give the domains
     (``spread_domains``); a server without the key goes to the policy call as unschedulable and
     receives nothing, and a service some server fits but none within the skew is rejected as "SKEW".
-    No policy, or one that sets nothing: exactly the path above."""
+    No policy, or one that sets nothing: exactly the path above.
+
+    ``explain=True`` adds the rejection diagnosis of SPEC.md 2.9: ``Plan.why[name]`` for every service
+    rejected NOFIT or SKEW, one ``Planner.explain`` call on the server table the placement left (the table
+    the placer was given: under a spread constraint the servers without the topology key are
+    unschedulable there), with the label bits of the fallback chain's keys given up.  The default changes
+    nothing: ``Plan.why`` stays empty."""
     p = planner or default_planner()
     stage = flow.stages[stage_name]
     services = list(stage.services)
@@ -406,6 +447,7 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
     if pol is not None and not pol.active:
         pol = None
     assignment, rejected, candidates, relaxed = {}, {}, {}, {}
+    ignore = 0  # SPEC.md 2.9: the label bits a fallback chain gives up
     if not services:
         return Plan(stage_name, [], {}, [], assignment, rejected, candidates)
     if not nodes:
@@ -431,8 +473,8 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
             cont, ntab = _stage_tables(names, flow, nodes)
             # stage 2 (fp_feasibility): feasible-server count and first feasible server per service
             first, count, _ = p.feasibility(cont, ntab, bitmap=False)
-            assign, reason, _ = p.place(cont, ntab, level=[lvl_v[n] for n in names])
-            placed = (first, count, assign, reason, None)
+            assign, reason, after = p.place(cont, ntab, level=[lvl_v[n] for n in names])
+            placed = (first, count, assign, reason, after)
     if placed is not None and pol is not None:
         # the scored placer on the same tables; the preferred labels share the stage's dictionary
         lvl_v = dict(zip(services, levels))
@@ -446,19 +488,23 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
         strategy = pol.strategy if pol.strategy is not None else 0
         if pol.fallback:
             ld = _stage_labels(names, flow, nodes, pol.preferred)
-            assign, reason, hops, _, _ = p.place_policy_fallback(cont, ntab, strategy, [ld.key_mask(k) for k in pol.fallback],
-                                                                 preferred=pmask, level=[lvl_v[n] for n in names],
-                                                                 domain=domain, max_skew=max_skew)
+            relax = [ld.key_mask(k) for k in pol.fallback]
+            assign, reason, hops, after, _ = p.place_policy_fallback(cont, ntab, strategy, relax, preferred=pmask,
+                                                                     level=[lvl_v[n] for n in names], domain=domain,
+                                                                     max_skew=max_skew)
+            for m in relax:
+                ignore |= m
             for v, n in enumerate(names):
                 if assign[v] != NONE and hops[v]:
                     required = {lab.split("=", 1)[0] for lab in flow.services.get(n, Service()).labels}
                     relaxed[n] = [k for k in pol.fallback[:int(hops[v])] if k in required]
         else:
-            assign, reason, _, _ = p.place_policy(cont, ntab, strategy, preferred=pmask, level=[lvl_v[n] for n in names],
-                                                  domain=domain, max_skew=max_skew)
-        placed = (placed[0], placed[1], assign, reason, None)
+            assign, reason, after, _ = p.place_policy(cont, ntab, strategy, preferred=pmask, level=[lvl_v[n] for n in names],
+                                                      domain=domain, max_skew=max_skew)
+        placed = (placed[0], placed[1], assign, reason, after)
+    why = {}
     if placed is not None:
-        first, count, assign, reason, _ = placed
+        first, count, assign, reason, after = placed
         candidates = {n: (int(count[v]), nodes[int(first[v])].slug if int(first[v]) != NONE else None)
                       for v, n in enumerate(names)}
         for v, n in enumerate(names):
@@ -466,7 +512,15 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
                 assignment[n] = nodes[assign[v]].slug
             else:
                 rejected[n] = "CYCLE" if reason[v] == 2 else "SKEW" if reason[v] == 3 else "NOFIT"
+        sel = [v for v, n in enumerate(names) if rejected.get(n) in ("NOFIT", "SKEW")]
+        if explain and sel:
+            # cont holds the tables of the call that made the assignment, `after` the server table it left
+            rows = p.explain(cont, after, sel=sel, ignore_labels=ignore)
+            ld = _stage_labels(names, flow, nodes, pol.preferred if pol is not None else ())
+            slugs = [nd.slug for nd in nodes]
+            why = {names[v]: Why.from_row(rows[i], ld, slugs) for i, v in enumerate(sel)}
     plan = Plan(stage_name, order, dict(zip(services, levels)), level_order, assignment, rejected, candidates)
+    plan.why = why
     if placed is not None and pol is not None:
         plan.strategy, plan.preferred = pol.strategy, pol.preferred
         if pol.spread is not None:

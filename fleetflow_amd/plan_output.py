@@ -4,7 +4,9 @@
 ``DeployRequest`` (crates/fleetflow-container/src/engine.rs:16-25):
 ``{stage, order, levels, level_order, assign, rejected}``, and for a plan made under a placement
 policy ``placement`` (``strategy``, ``preferred``, ``spread``, ``fallback``) and, under a fallback chain
-(SPEC.md 2.8), ``relaxed``: the label keys each relaxed service gave up.
+(SPEC.md 2.8), ``relaxed``: the label keys each relaxed service gave up.  A plan made with
+``plan_stage(..., explain=True)`` carries ``why``: the rejection diagnosis (SPEC.md 2.9) of each service
+rejected NOFIT or SKEW; the key is absent when there is none.
 
 ``format_up_dry_run`` / ``format_deploy_dry_run`` reproduce the reference's
 ``fleet up --dry-run`` (crates/fleetflow/src/commands/up.rs:57-136) and
@@ -20,7 +22,9 @@ from __future__ import annotations
 
 import json
 
-from .flow import U32_MAX, Flow, Plan
+from dataclasses import asdict
+
+from .flow import U32_MAX, WHY_NAMES, Flow, Plan, Why
 from .parser import FlowError
 
 
@@ -44,6 +48,8 @@ def plan_to_json(plan: Plan, indent: int | None = None) -> str:
         if fallback:
             d["placement"]["fallback"] = {"relax_order": plan.fallback_relax_order, "max_hops": plan.fallback_max_hops}
             d["relaxed"] = plan.relaxed
+    if plan.why:  # rejection diagnosis (SPEC.md 2.9)
+        d["why"] = {k: asdict(w) for k, w in plan.why.items()}
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
@@ -56,7 +62,9 @@ def plan_from_json(text: str) -> Plan:
                 pol.get("strategy"), list(pol.get("preferred") or []),
                 (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"),
                 list((pol.get("fallback") or {}).get("relax_order") or []), (pol.get("fallback") or {}).get("max_hops"),
-                {k: list(v) for k, v in (d.get("relaxed") or {}).items()})
+                {k: list(v) for k, v in (d.get("relaxed") or {}).items()},
+                {k: Why(dict(w["fail"]), dict(w["only"]), w["feasible"], list(w["universal"]), list(w["missing_labels"]),
+                        w["nearest"], w.get("servers", 0)) for k, w in (d.get("why") or {}).items()})
 
 
 def get_network_name(project: str, stage: str) -> str:
@@ -95,9 +103,26 @@ def _service_block(flow: Flow, stage: str, name: str, container_suffix: str, pla
             lines.append(f"    配置先: {plan.assignment[name]}" + (f" (緩和: {', '.join(relaxed)})" if relaxed else ""))
         elif name in plan.rejected:
             lines.append(f"    配置先: (配置不可: {plan.rejected[name]})")
+            if name in plan.why:
+                lines.append(_why_line(plan.why[name]))
         else:
             lines.append("    配置先: local")
     return lines
+
+
+def _why_line(w: Why) -> str:
+    """The rejection diagnosis of one service (SPEC.md 2.9): the causes that fail somewhere, in the fixed
+    order, with their server counts out of N (``全台`` marks one that fails on every server), then the
+    required labels no schedulable server carries and the first server one cause away."""
+    parts = [f"{c} {w.fail[c]}/{w.servers} 台" + (" (全台)" if c in w.universal else "")
+             for c in WHY_NAMES if w.fail.get(c, 0) > 0]
+    line = "    配置不可の理由: " + (", ".join(parts) if parts else "なし")
+    notes = []
+    if w.missing_labels:
+        notes.append(f"該当ラベルなし: {', '.join(w.missing_labels)}")
+    if w.nearest is not None:
+        notes.append(f"最も近い: {w.nearest}")
+    return line + (f" ({'; '.join(notes)})" if notes else "")
 
 
 _FOOTER = "[dry-run] 実際の操作は行われません。--dry-run を外して実行してください。"

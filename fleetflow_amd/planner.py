@@ -444,7 +444,77 @@ class Planner:
                                      bm.ctypes.data_as(_lib.u64p) if bm is not None else None), "fp_feasibility")
         return first, count, bm
 
+    def explain(self, cont, nodes, sel=None, ignore_labels=0):
+        """Rejection diagnosis (SPEC.md 2.9, fp_explain): one row of EXPLAIN_WORDS u32 per explained
+        container on the given node table -- ``sel`` container indices (repeats allowed) or None = every
+        container in order; ``ignore_labels`` the required-label bits given up.  Nothing is placed.
+        Returns an ndarray [M, 16] (word indices: _lib.EXPLAIN_*)."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
+        sched = _u8(nodes[4])
+        C, N = cpu.size, cf.size
+        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
+        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
+        sl = _u32(sel).reshape(-1) if sel is not None else None
+        M = C if sl is None else sl.size
+        rows = np.empty((M, _lib.EXPLAIN_WORDS), np.uint32)
+        if M == 0:  # an empty sel must not reach the library as NULL (= every container)
+            return rows
+        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
+        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
+        check(self._L.fp_explain(self._ctx, ct.byref(cs), ct.byref(ns),
+                                 sl.ctypes.data_as(_lib.u32p) if sl is not None else None, M,
+                                 int(ignore_labels) & 0xFFFFFFFF, rows.ctypes.data_as(_lib.u32p)), "fp_explain")
+        return rows
+
+    def explain_batch(self, S, C, N, cont, nodes, reason, reason_mask, ignore_labels=None):
+        """Per-scenario cause histograms (SPEC.md 2.9, fp_explain_batch) over scenario-major arrays:
+        ``reason_mask`` bit r selects the containers with reason r (0 = every container, ``reason`` may be
+        None), ``ignore_labels`` [S] or None.  Returns an ndarray [S, 8] (word indices 0..4 = the causes,
+        _lib.EXPLAIN_HIST_*)."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
+        sched = _u8(nodes[4])
+        rs = _u8(reason) if reason is not None else None
+        ig = _u32(ignore_labels) if ignore_labels is not None else None
+        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
+        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
+        self._need(int(reason_mask) == 0 or (rs is not None and rs.size == S * C), "reason must hold S * C entries")
+        self._need(ig is None or ig.size == S, "ignore_labels must hold S entries")
+        hist = np.empty((S, _lib.EXPLAIN_HIST_WORDS), np.uint32)
+        b = FpBatch(S, 0, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), None, _ptr(cf), _ptr(mf), _ptr(lab),
+                    _ptr(cu), _ptr(sched), None, _ptr(rs), None)
+        check(self._L.fp_explain_batch(self._ctx, ct.byref(b), int(reason_mask) & 0xFFFFFFFF,
+                                       ig.ctypes.data_as(_lib.u32p) if ig is not None else None,
+                                       hist.ctypes.data_as(_lib.u32p)), "fp_explain_batch")
+        return hist
+
     # -- device-pointer API -------------------------------------------------------------
+    def dev_explain(self, db: "DevBatch", rows_t, sel_t=None, ignore_labels=0, scenario=0):
+        """fp_dev_explain on one scenario of ``db`` (offset pointers, as dev_feasibility): ``rows_t``
+        [M * 16] int32 storage, ``sel_t`` [M] container indices or None = every container.  A sel index
+        >= C is found on the device: no row is written and sync() raises FP_ECORRUPT."""
+        C, N = db.C, db.N
+        o, p = scenario * C, scenario * N
+        M = C if sel_t is None else sel_t.numel()
+        self._need(rows_t.numel() >= M * _lib.EXPLAIN_WORDS, "rows_t must hold M * 16 entries")
+        cs = FpContainers(C, db.cpu[o:].data_ptr(), db.mem[o:].data_ptr(), db.req[o:].data_ptr(),
+                          db.conf[o:].data_ptr())
+        ns = FpNodes(N, db.cf[p:].data_ptr(), db.mf[p:].data_ptr(), db.lab[p:].data_ptr(), db.cu[p:].data_ptr(),
+                     db.sched[p:].data_ptr())
+        self._dev(lambda: check(self._L.fp_dev_explain(
+            self._ctx, ct.byref(cs), ct.byref(ns), sel_t.data_ptr() if sel_t is not None else None, M,
+            int(ignore_labels) & 0xFFFFFFFF, rows_t.data_ptr()), "fp_dev_explain"))
+
+    def dev_explain_batch(self, db: "DevBatch", reason_mask, ignore_t, hist_t):
+        """fp_dev_explain_batch over every scenario of ``db`` (its containers, node state and reason):
+        ``ignore_t`` [S] or None, ``hist_t`` [S * 8] out (int32 storage of u32 values)."""
+        self._need(ignore_t is None or ignore_t.numel() == db.S, "ignore_t must hold S entries")
+        self._need(hist_t.numel() == db.S * _lib.EXPLAIN_HIST_WORDS, "hist_t must hold S * 8 entries")
+        self._dev(lambda: check(self._L.fp_dev_explain_batch(
+            self._ctx, ct.byref(db.struct()), int(reason_mask) & 0xFFFFFFFF,
+            ignore_t.data_ptr() if ignore_t is not None else None, hist_t.data_ptr()), "fp_dev_explain_batch"))
+
     def dev_gen_batch(self, seed, db: "DevBatch", flags=7):
         self._dev(lambda: check(self._L.fp_dev_gen_batch(self._ctx, ct.c_uint64(seed), ct.byref(db.struct()), flags),
                                 "fp_dev_gen_batch"))

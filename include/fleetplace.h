@@ -22,6 +22,8 @@
  *                        crates/fleetflow-controlplane/src/model.rs:47-54
  *   fp_feasibility    <- new: stage-2 containers x nodes feasibility/score sweep
  *   fp_dev_feasibility_batch <- new: the same sweep over many what-if scenarios
+ *   fp_explain        <- new: per-cause diagnosis of unplaced containers (which 2.3 predicate fails where)
+ *   fp_explain_batch  <- new: the same as one cause histogram per what-if scenario
  *
  * Conventions
  *   - All buffers are caller-owned; no allocation crosses the ABI.
@@ -270,6 +272,37 @@ int fp_place_batch_policy_fallback(fp_ctx *ctx, const fp_batch *b, const uint32_
  * bit (c, n) at word [(c/64) * N + n], bit c % 64. */
 int fp_feasibility(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes,
                    uint32_t *first_out, uint32_t *count_out, uint64_t *bitmap_out);
+/* Rejection diagnosis (SPEC.md 2.9): WHY a container has no node on the given node table -- the answer
+ * "0/5 nodes available: 3 insufficient cpu, 2 didn't match the node selector".  Nothing is placed or mutated.
+ * why(c, n) is the mask of the 2.3 predicates that fail for container c on node n, with
+ * req' = req_labels[c] & ~ignore_labels (the label bits the caller gives up, e.g. a fallback chain's
+ * cum[n_hops]); every bit is evaluated on every node, unschedulable nodes included, and why == 0 is exactly
+ * "feasible by 2.3". */
+enum fp_why { FP_WHY_CORDON = 1, FP_WHY_CPU = 2, FP_WHY_MEM = 4, FP_WHY_LABEL = 8, FP_WHY_CONFLICT = 16 };
+/* One row of FP_EXPLAIN_WORDS u32 per explained container:
+ *   FAIL[k]   nodes with bit k of why set (non-exclusive)      ONLY[k]  nodes with why == 1 << k (sole blocker)
+ *   FEASIBLE  nodes with why == 0 (fp_feasibility's count when ignore_labels = 0)
+ *   ALL       the AND of why over every node: what fails everywhere (0x1F when N = 0)
+ *   MISSING   req' & ~(OR of labels over the schedulable nodes): required labels no schedulable node carries
+ *   NEAR      the lowest node with exactly one bit of why set, else FP_NONE;  words 14, 15 are written as 0.
+ * One histogram of FP_EXPLAIN_HIST_WORDS u32 per scenario, over its selected containers: words 0..4 count the
+ * containers whose ALL has bit k (a container may count in several), MIXED those with FEASIBLE = 0 and ALL = 0,
+ * FITS those with FEASIBLE > 0 (SKEW rejections, or a table that is not the final one), SELECTED all of them. */
+enum { FP_EXPLAIN_FAIL = 0, FP_EXPLAIN_ONLY = 5, FP_EXPLAIN_FEASIBLE = 10, FP_EXPLAIN_ALL = 11,
+       FP_EXPLAIN_MISSING = 12, FP_EXPLAIN_NEAR = 13, FP_EXPLAIN_WORDS = 16 };
+enum { FP_EXPLAIN_HIST_MIXED = 5, FP_EXPLAIN_HIST_FITS = 6, FP_EXPLAIN_HIST_SELECTED = 7, FP_EXPLAIN_HIST_WORDS = 8 };
+/* sel: n_sel container indices (< c->n, repeats allowed; one >= c->n is FP_EINVAL), or NULL = every container in
+ * order (n_sel is then c->n whatever was passed).  rows_out: [n_sel][FP_EXPLAIN_WORDS].  After fp_place, or
+ * fp_place_policy* without a spread constraint and with ignore_labels = cum[n_hops], every FP_REASON_NOFIT
+ * container has FEASIBLE = 0 on the node table that call left (SPEC.md 2.3 monotonicity). */
+int fp_explain(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *sel, uint32_t n_sel,
+               uint32_t ignore_labels, uint32_t *rows_out);
+/* Per-scenario histograms over b's containers and node state (e.g. the state fp_place_batch left).
+ * reason_mask: bit r selects the containers with b->reason[s][c] == r; 0 = every container, b->reason is not
+ * read.  ignore_labels: [S] or NULL = 0.  hist_out: [S][FP_EXPLAIN_HIST_WORDS].  Reads b's containers, node
+ * state and reason; writes only hist_out.  n_scen <= 65535. */
+int fp_explain_batch(fp_ctx *ctx, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
+                     uint32_t *hist_out);
 /* One stage's whole plan, the `fleet up --dry-run` path (crates/fleetflow/src/commands/up.rs:57-136):
  *   perm_out                 A1 legacy start order (engine.rs:64-85, as fp_legacy_order)
  *   level_out, order_out, n_cycle_out   A2 levels and start order (as fp_levelize)
@@ -309,6 +342,14 @@ int fp_dev_feasibility(fp_ctx *ctx, const fp_containers *c, const fp_nodes *node
  * lowest feasible node (FP_NONE if none) and count_out[s*C + c] = the number of feasible
  * nodes.  n_scen <= 65535. */
 int fp_dev_feasibility_batch(fp_ctx *ctx, const fp_batch *b, uint32_t *first_out, uint32_t *count_out);
+/* As fp_explain on device pointers; rows_out is 64-byte aligned (else FP_EINVAL).  A sel index >= c->n is found
+ * on the device before any row is written: no row is written and fp_ctx_sync() reports FP_ECORRUPT. */
+int fp_dev_explain(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *sel, uint32_t n_sel,
+                   uint32_t ignore_labels, uint32_t *rows_out);
+/* As fp_explain_batch on device pointers.  The selection is compacted on the device; the call takes at most
+ * 8 bytes per container of the batch plus 4 per scenario from the context's workspace. */
+int fp_dev_explain_batch(fp_ctx *ctx, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
+                         uint32_t *hist_out);
 /* As fp_place_batch_policy on device pointers (strategy, preferred_labels and node_count included).
  * A strategy value that is no fp_strategy is found on the device: nothing is written and
  * fp_ctx_sync() reports FP_EINVAL. */

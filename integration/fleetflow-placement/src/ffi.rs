@@ -23,6 +23,23 @@ pub const FP_STRATEGY_FILL_LOWEST: u32 = 3;
 pub const FP_POLICY_MAX_NODES: u32 = 8192;
 pub const FP_SPREAD_MAX_DOMAINS: u32 = 64;
 pub const FP_FALLBACK_MAX_HOPS: u32 = 4;
+// rejection diagnosis (SPEC.md 2.9): enum fp_why, the word indices of a row and of a histogram
+pub const FP_WHY_CORDON: u32 = 1;
+pub const FP_WHY_CPU: u32 = 2;
+pub const FP_WHY_MEM: u32 = 4;
+pub const FP_WHY_LABEL: u32 = 8;
+pub const FP_WHY_CONFLICT: u32 = 16;
+pub const FP_EXPLAIN_FAIL: usize = 0;
+pub const FP_EXPLAIN_ONLY: usize = 5;
+pub const FP_EXPLAIN_FEASIBLE: usize = 10;
+pub const FP_EXPLAIN_ALL: usize = 11;
+pub const FP_EXPLAIN_MISSING: usize = 12;
+pub const FP_EXPLAIN_NEAR: usize = 13;
+pub const FP_EXPLAIN_WORDS: usize = 16;
+pub const FP_EXPLAIN_HIST_MIXED: usize = 5;
+pub const FP_EXPLAIN_HIST_FITS: usize = 6;
+pub const FP_EXPLAIN_HIST_SELECTED: usize = 7;
+pub const FP_EXPLAIN_HIST_WORDS: usize = 8;
 pub const FP_K_PLACE: c_int = 0;
 pub const FP_K_SORT: c_int = 1;
 pub const FP_K_FEAS: c_int = 2;
@@ -167,6 +184,10 @@ unsafe extern "C" {
                                           hops_out: *mut u8) -> c_int;
     pub fn fp_feasibility(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, first_out: *mut u32,
                           count_out: *mut u32, bitmap_out: *mut u64) -> c_int;
+    pub fn fp_explain(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, sel: *const u32, n_sel: u32,
+                      ignore_labels: u32, rows_out: *mut u32) -> c_int;
+    pub fn fp_explain_batch(ctx: *mut fp_ctx, b: *const fp_batch, reason_mask: u32, ignore_labels: *const u32,
+                            hist_out: *mut u32) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,
                          perm_out: *mut u32, level_out: *mut u32, order_out: *mut u32, n_cycle_out: *mut u32,
                          first_out: *mut u32, count_out: *mut u32, assign_out: *mut u32, reason_out: *mut u8)
@@ -184,6 +205,10 @@ unsafe extern "C" {
                               first_out: *mut u32, count_out: *mut u32, bitmap_out: *mut u64) -> c_int;
     pub fn fp_dev_feasibility_batch(ctx: *mut fp_ctx, b: *const fp_batch, first_out: *mut u32,
                                     count_out: *mut u32) -> c_int;
+    pub fn fp_dev_explain(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, sel: *const u32,
+                          n_sel: u32, ignore_labels: u32, rows_out: *mut u32) -> c_int;
+    pub fn fp_dev_explain_batch(ctx: *mut fp_ctx, b: *const fp_batch, reason_mask: u32, ignore_labels: *const u32,
+                                hist_out: *mut u32) -> c_int;
     pub fn fp_dev_place_batch_policy_spread(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
                                             preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
                                             max_skew: *const u32) -> c_int;

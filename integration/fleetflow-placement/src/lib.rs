@@ -106,6 +106,31 @@ impl Planner {
         Ok((assign, reason))
     }
 
+    /// Rejection diagnosis (SPEC.md 2.9, fleetplace.h `fp_explain`): one row of `ffi::FP_EXPLAIN_WORDS`
+    /// words per container of `sel` (None = every container in order) on the node table `nodes`, which is
+    /// not changed; `ignore_labels` are the required-label bits given up.  Word indices: `ffi::FP_EXPLAIN_*`.
+    pub fn explain(&mut self, c: &Containers, nodes: &Nodes, sel: Option<&[u32]>, ignore_labels: u32)
+                   -> Result<Vec<[u32; ffi::FP_EXPLAIN_WORDS]>, PlanError> {
+        let n = c.cpu_m.len();
+        if !c.all_len(n) || !nodes.all_len(nodes.cpu_free.len()) || sel.map_or(false, |s| s.iter().any(|&i| i as usize >= n)) {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        // fp_explain reads the node table only: the mutable pointers of fp_nodes are never written through
+        let ns = ffi::fp_nodes { n: nodes.cpu_free.len() as u32, cpu_free: nodes.cpu_free.as_ptr() as *mut u32,
+                                 mem_free: nodes.mem_free.as_ptr() as *mut u32, labels: nodes.labels.as_ptr(),
+                                 conflict_used: nodes.conflict_used.as_ptr() as *mut u32,
+                                 schedulable: nodes.schedulable.as_ptr() };
+        let m = sel.map_or(n, |s| s.len());
+        let mut rows = vec![[0u32; ffi::FP_EXPLAIN_WORDS]; m];
+        check(unsafe {
+            ffi::fp_explain(self.ctx, &cs, &ns, sel.map_or(std::ptr::null(), |s| s.as_ptr()), m as u32, ignore_labels,
+                            rows.as_mut_ptr() as *mut u32)
+        })?;
+        Ok(rows)
+    }
+
     /// Scored placement (SPEC.md 2.6, fleetplace.h `fp_place_policy`): `strategy` is one of
     /// `ffi::FP_STRATEGY_*`, `preferred_labels` the soft preferred-label mask, `node_count` the
     /// containers already on each node (updated in place; None starts at zero).  `nodes` is
@@ -547,6 +572,25 @@ pub fn place_stage(flow: &Flow, stage_name: &str, c: &Containers, nodes: &mut No
     }
     let (assign, _) = with_planner(|p| p.place(c, nodes, None))?;
     Ok(assign.iter().map(|&a| if a == ffi::FP_NONE { None } else { Some(stage.servers[a as usize].clone()) }).collect())
+}
+
+/// Why the services [`place_stage`] could not place have no server (SPEC.md 2.9): `assign` is its result and
+/// `nodes` the table it left.  Returns, for every unplaced service in stage order, its position in the
+/// stage and its row of `ffi::FP_EXPLAIN_WORDS` words (`ffi::FP_EXPLAIN_*`: per-cause server counts, the
+/// causes that fail on every server, the missing labels, the nearest server).
+pub fn explain_stage(flow: &Flow, stage_name: &str, c: &Containers, nodes: &Nodes, assign: &[Option<String>])
+                     -> Result<Vec<(usize, [u32; ffi::FP_EXPLAIN_WORDS])>, PlanError> {
+    let Some(stage) = flow.stages.get(stage_name) else { return Err(PlanError(ffi::FP_EINVAL)) };
+    if nodes.cpu_free.len() != stage.servers.len() || c.cpu_m.len() != stage.services.len()
+        || assign.len() != stage.services.len() {
+        return Err(PlanError(ffi::FP_EINVAL));
+    }
+    let sel: Vec<u32> = assign.iter().enumerate().filter(|(_, a)| a.is_none()).map(|(i, _)| i as u32).collect();
+    if sel.is_empty() {
+        return Ok(Vec::new());
+    }
+    let rows = with_planner(|p| p.explain(c, nodes, Some(&sel), 0))?;
+    Ok(sel.iter().map(|&i| i as usize).zip(rows).collect())
 }
 
 /// `fp_strategy` of a tenant `PlacementPolicy.strategy` string
