@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("FLEETPLACE_LIB") or os.path.join(_HERE, "libfleetplac
 
 FP_OK, FP_EINVAL, FP_ENOMEM, FP_EDEVICE, FP_EOVERFLOW, FP_ECORRUPT = 0, -1, -2, -3, -4, -5
 FP_NONE = 0xFFFFFFFF
-REASON_OK, REASON_NOFIT, REASON_CYCLE, REASON_SKEW = 0, 1, 2, 3
+REASON_OK, REASON_NOFIT, REASON_CYCLE, REASON_SKEW, REASON_QUOTA = 0, 1, 2, 3, 4
 FP_K_PLACE, FP_K_SORT, FP_K_FEAS, FP_K_LEVEL, FP_K_GEN = 0, 1, 2, 3, 4
 # scored placement (fleetplace.h enum fp_strategy, SPEC.md 2.6); the strings are the control plane's
 # PlacementPolicy.strategy constants (crates/fleetflow-controlplane/src/model.rs:56-95)
@@ -28,6 +28,11 @@ FP_POLICY_MAX_NODES = 8192
 FP_SPREAD_MAX_DOMAINS = 64
 # fallback chain (SPEC.md 2.8): at most this many hops, relax_mask rows hold this many words
 FP_FALLBACK_MAX_HOPS = 4
+# resource quota (SPEC.md 2.10): the dimension indices of a quota row (also the bits of quota_why), their
+# names in that order, and the cap that is none
+QUOTA_CPU, QUOTA_MEM, QUOTA_SERVICES, QUOTA_DIMS = 0, 1, 2, 3
+QUOTA_NAMES = ("cpu", "memory", "services")
+QUOTA_UNLIMITED = 0xFFFFFFFF
 # rejection diagnosis (SPEC.md 2.9): fp_why bits, the word indices of an fp_explain row and of a histogram
 WHY_CORDON, WHY_CPU, WHY_MEM, WHY_LABEL, WHY_CONFLICT = 1, 2, 4, 8, 16
 EXPLAIN_FAIL, EXPLAIN_ONLY, EXPLAIN_FEASIBLE, EXPLAIN_ALL, EXPLAIN_MISSING, EXPLAIN_NEAR = 0, 5, 10, 11, 12, 13
@@ -123,6 +128,13 @@ SIGNATURES = {
     "fp_place_batch_policy_fallback": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u32p, u32p, u32p,
                                                   u8p]),
     "fp_dev_place_batch_policy_fallback": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fp_place_policy_quota": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, ct.c_uint32,
+                                         ct.c_uint32, u32p, u32p, ct.c_uint32, u32p, ct.c_uint32, u32p, u8p, u8p,
+                                         u32p, u32p, u8p]),
+    "fp_place_batch_policy_quota": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u32p, u32p, u32p,
+                                               u8p, u32p, u32p, u8p]),
+    "fp_dev_place_batch_policy_quota": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                   vp]),
     "fp_explain": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, ct.c_uint32, ct.c_uint32, u32p]),
     "fp_explain_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), ct.c_uint32, u32p, u32p]),
     "fp_dev_explain": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, ct.c_uint32, ct.c_uint32, vp]),

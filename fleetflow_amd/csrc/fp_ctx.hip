@@ -532,9 +532,12 @@ extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const 
 // range in a constrained scenario is refused here as well.
 // relax_mask / n_hops (SPEC.md 2.8; either null = no fallback) likewise: an n_hops above
 // FP_FALLBACK_MAX_HOPS is refused here.  hops_out (nullable) receives the winners' hops.
+// quota (SPEC.md 2.10; null = no quota, and then quota_used and quota_why_out are not touched) has no
+// illegal value.  quota_used (nullable) goes in and comes back; quota_why_out (nullable) comes back.
 static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
                              uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
-                             const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
+                             const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out,
+                             const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why_out) {
     const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
     const size_t SC = S * C, SN = S * N;
     if (S && !strategy) return FP_EINVAL;
@@ -549,6 +552,7 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     if (!relax_mask || !n_hops) relax_mask = n_hops = nullptr;
     for (size_t s = 0; n_hops && s < S; ++s)
         if (n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (!quota) quota_used = nullptr, quota_why_out = nullptr;
     if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
     if (S && C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign ||
                    !b->reason))
@@ -559,8 +563,8 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1 + 1) + SN * (4 * 6 + 1) +
-                                     S * (8 + 4 + 4 + 4 + 4 * FP_FALLBACK_MAX_HOPS + 4) + 25 * 256);
+    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1 + 1 + 1) + SN * (4 * 6 + 1) +
+                                     S * (8 + 4 + 4 + 4 + 4 * FP_FALLBACK_MAX_HOPS + 4 + 2 * 4 * FP_QUOTA_DIMS) + 28 * 256);
     if (rc) return rc;
     fp_stage_reset(c);
     fp_batch d = *b;
@@ -581,26 +585,41 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
     const uint32_t *dskew = stage_in(c, max_skew, S, &rc);
     const uint32_t *drelax = stage_in(c, relax_mask, S * FP_FALLBACK_MAX_HOPS, &rc);
     const uint32_t *dhops_n = stage_in(c, n_hops, S, &rc);
+    const uint32_t *dquota = stage_in(c, quota, S * FP_QUOTA_DIMS, &rc);
+    uint32_t *dqused = stage_in(c, quota_used, S * FP_QUOTA_DIMS, &rc);
     d.assign = stage_out<uint32_t>(c, SC, &rc);
     d.reason = stage_out<uint8_t>(c, SC, &rc);
     d.cost = stage_out<uint64_t>(c, S, &rc);
     uint8_t *dhops = hops_out ? stage_out<uint8_t>(c, SC, &rc) : nullptr;
+    uint8_t *dqwhy = quota_why_out ? stage_out<uint8_t>(c, SC, &rc) : nullptr;
     if (rc) return rc;
-    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount, ddom, dskew, drelax, dhops_n, dhops);
+    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount, ddom, dskew, drelax, dhops_n, dhops, dquota,
+                                        dqused, dqwhy);
     if (rc) return rc;
     const OutCopy o[] = {{b->assign, d.assign, SC * 4},          {b->reason, d.reason, SC},
                          {b->cost, d.cost, S * 8},                {b->cpu_free, d.cpu_free, SN * 4},
                          {b->mem_free, d.mem_free, SN * 4},       {b->conflict_used, d.conflict_used, SN * 4},
-                         {node_count, dcount, SN * 4},             {hops_out, dhops, SC}};
-    return copy_back_all(c, o, 8);
+                         {node_count, dcount, SN * 4},             {hops_out, dhops, SC},
+                         {quota_used, dqused, S * FP_QUOTA_DIMS * 4}, {quota_why_out, dqwhy, SC}};
+    return copy_back_all(c, o, 10);
+}
+
+extern "C" int fp_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                           const uint32_t *preferred_labels, uint32_t *node_count,
+                                           const uint32_t *domain, const uint32_t *max_skew, const uint32_t *relax_mask,
+                                           const uint32_t *n_hops, uint8_t *hops_out, const uint32_t *quota,
+                                           uint32_t *quota_used, uint8_t *quota_why_out) {
+    if (!c || !b) return FP_EINVAL;
+    return batch_policy_host(c, b, strategy, preferred_labels, node_count, domain, max_skew, relax_mask, n_hops, hops_out,
+                             quota, quota_used, quota_why_out);
 }
 
 extern "C" int fp_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
                                               const uint32_t *preferred_labels, uint32_t *node_count,
                                               const uint32_t *domain, const uint32_t *max_skew,
                                               const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
-    if (!c || !b) return FP_EINVAL;
-    return batch_policy_host(c, b, strategy, preferred_labels, node_count, domain, max_skew, relax_mask, n_hops, hops_out);
+    return fp_place_batch_policy_quota(c, b, strategy, preferred_labels, node_count, domain, max_skew, relax_mask, n_hops,
+                                       hops_out, nullptr, nullptr, nullptr);
 }
 
 extern "C" int fp_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
@@ -615,10 +634,11 @@ extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_
     return fp_place_batch_policy_spread(c, b, strategy, preferred_labels, node_count, nullptr, nullptr);
 }
 
-extern "C" int fp_place_policy_fallback(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
-                                        uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
-                                        const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
-                                        uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out) {
+extern "C" int fp_place_policy_quota(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                     uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                     const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
+                                     uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
+                                     const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
     fp_batch b;
     memset(&b, 0, sizeof(b));
@@ -638,7 +658,15 @@ extern "C" int fp_place_policy_fallback(fp_ctx *c, const fp_containers *cs, fp_n
     b.assign = assign_out;
     b.reason = reason_out;
     return batch_policy_host(c, &b, &strategy, &preferred_labels, node_count, domain, &max_skew, relax_mask, &n_hops,
-                             hops_out);
+                             hops_out, quota, quota_used, quota_why_out);
+}
+
+extern "C" int fp_place_policy_fallback(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                        uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                        const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
+                                        uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out) {
+    return fp_place_policy_quota(c, cs, ns, level, strategy, preferred_labels, node_count, domain, max_skew, relax_mask,
+                                 n_hops, assign_out, reason_out, hops_out, nullptr, nullptr, nullptr);
 }
 
 extern "C" int fp_place_policy_spread(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
@@ -661,7 +689,7 @@ extern "C" int fp_dev_place_batch_policy(fp_ctx *c, const fp_batch *b, const uin
     if (!c || !b) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, nullptr, nullptr,
-                                                         nullptr, nullptr, nullptr));
+                                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 }
 
 extern "C" int fp_dev_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
@@ -670,7 +698,7 @@ extern "C" int fp_dev_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, co
     if (!c || !b) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
-                                                         nullptr, nullptr, nullptr));
+                                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
 }
 
 extern "C" int fp_dev_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
@@ -680,7 +708,18 @@ extern "C" int fp_dev_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, 
     if (!c || !b) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
-                                                         relax_mask, n_hops, hops_out));
+                                                         relax_mask, n_hops, hops_out, nullptr, nullptr, nullptr));
+}
+
+extern "C" int fp_dev_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                               const uint32_t *preferred_labels, uint32_t *node_count,
+                                               const uint32_t *domain, const uint32_t *max_skew,
+                                               const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out,
+                                               const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why_out) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
+                                                         relax_mask, n_hops, hops_out, quota, quota_used, quota_why_out));
 }
 
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,

@@ -144,10 +144,12 @@ int fp_dev_explain_batch_impl(fp_ctx *c, const fp_batch *b, uint32_t reason_mask
 // scored placement (fp_policy.hip, SPEC.md 2.6 and 2.7); every pointer is device memory.  domain [S][N]
 // and max_skew [S] are the topology spread of 2.7; either one null = no constraint.  relax_mask [S][4] and
 // n_hops [S] are the fallback chain of 2.8; either one null = no fallback.  hops [S][C] (nullable) receives
-// the winner's hop: all zero when the call has no chain
+// the winner's hop: all zero when the call has no chain.  quota [S][3] is the resource quota of 2.10, null =
+// no quota; quota_used [S][3] (in/out) and quota_why [S][C] are nullable and untouched without quota
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
                                    uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
-                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops);
+                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops,
+                                   const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why);
 
 // tile-pipeline FFD (fp_pipe.hip)
 bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint32_t *W_out, uint32_t *B_out,

@@ -17,7 +17,7 @@
 //   2. k_policy_keys  : key (~cpu << 32 | ~mem), value = the index in the scenario; a stable rocprim
 //                       radix sort over 64 bits (segmented per scenario for S > 1) gives the FFD order
 //                       (cpu desc, mem desc, index asc) -- the recipe of fp_place.hip step 3b
-//   3. k_policy<BLK,K,SP,FB>: the placer (SP: with the spread constraint; launched when the call gives
+//   3. k_policy<BLK,K,SP,FB,QT>: the placer (SP: with the spread constraint; launched when the call gives
 //                       domain and max_skew.  FB: with the fallback chain; launched when the call gives
 //                       relax_mask and n_hops).  The scenario's node state lives in registers for the whole
 //                       kernel: thread t of a BLK-thread block owns nodes t + BLK * j, j < K, five
@@ -63,6 +63,14 @@
 // Each wave gathers 64 records at a time into registers (lane l holds record i0 + l, loaded a chunk
 // ahead) and broadcasts container u with v_readlane, so the record arrives in scalar registers and no
 // lane ever issues a per-container load.
+//
+// The resource quota (QT; SPEC.md 2.10, the PlacementPolicy's ResourceQuota; launched when the call gives
+// quota) is tested on that record before anything else happens to the container: what each dimension still
+// admits sits in three lanes of one vector register of every wave and is read like the record, with no LDS
+// and no barrier.  A container over a cap is FP_REASON_QUOTA and takes the CYCLE container's way out, a
+// uniform continue in front of the reduction.  That makes the number of skipped containers between two
+// reductions data-dependent; the parity argument above never counted containers, only reductions, and par
+// changes nowhere but behind a barrier.
 //
 // No device-wide synchronisation, no spin waits, no links: the kernel cannot deadlock and has no guard.
 // N <= FP_POLICY_MAX_NODES (1024 threads x 8 nodes): past one workgroup the argmin per dependent
@@ -175,6 +183,10 @@ struct PolicyArgs {
     const uint32_t *relax_mask;                   // [S][4] label bits hop h + 1 gives up
     const uint32_t *n_hops;                       // [S], 0 = no fallback in that scenario
     uint8_t *hops;                                // [S][C] or null: the winner's hop
+    // SPEC.md 2.10, read by k_policy<.., .., .., true> only, and behind the rest for the same reason
+    const uint32_t *quota;                        // [S][3] caps, FP_QUOTA_UNLIMITED = none in that dimension
+    uint32_t *quota_used;                         // [S][3] in/out or null (null starts at zero)
+    uint8_t *quota_why;                           // [S][C] or null: the mask of the blocking dimensions
 };
 
 __device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
@@ -229,7 +241,9 @@ __device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
 // compiles to what it did before the constraint existed.
 // FB: the fallback chain of SPEC.md 2.8 (a.relax_mask and a.n_hops given).  FB = false compiles to what
 // it did before the chain existed.
-template <int BLK, int K, bool SP, bool FB>
+// QT: the resource quota of SPEC.md 2.10 (a.quota given).  QT = false compiles to what it did before the
+// quota existed.
+template <int BLK, int K, bool SP, bool FB, bool QT>
 __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     static_assert(BLK % 64 == 0 && (BLK & (BLK - 1)) == 0, "block of whole waves, power of two");
     constexpr uint32_t NW = BLK / 64;
@@ -245,7 +259,9 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     // 1024 x 8 under both the spread and the chain is past the 128 registers of a 1024-thread block with
     // pmh in registers of its own: that variant keeps pref_miss in nd[j], above the 23-bit node field (where
     // it sits in the key's high word), and takes the two apart with one more VALU operation a node
-    constexpr bool KEEP_PMH = !(FB && SP && K == 8);
+    // The quota's one register is one too many for 1024 x 8 under the spread alone as well (28 bytes of
+    // scratch): with QT that variant packs the same way, above its 26-bit node field
+    constexpr bool KEEP_PMH = !((FB || QT) && SP && K == 8);
     uint32_t cf[K], mf[K], cu[K], cnt[K], lab[K];
     uint32_t pmh[KEEP_PMH ? K : 1];  // pmh = pref_miss << NB: the key's high word
     auto pref_hi = [&](uint32_t l) { return (uint32_t)__popc(pref & ~l) << NB; };
@@ -338,6 +354,29 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
     __shared__ uint64_t slot[2][NW];
     uint32_t par = 0, rejected = 0;  // rejected is the same in every thread
 
+    // ---- SPEC.md 2.10.  The quota's state is uniform, and it lives where the container records live: in the
+    // lanes of one vector register of every wave.  Lane d < 3 of qv holds what dimension d still admits,
+    // cap - used (0 when used is above the cap on entry: every non-zero request blocks), and v_readlane brings
+    // it to a scalar register for the test, as it brings the record.  "r != 0 and not (used <= cap and
+    // r <= cap - used)" is then r > qv[d].  qlim (scalar, fixed for the kernel) has bit d set when dimension d
+    // has a cap.  A placement takes r from qv[d] in every dimension, capped or not: modulo 2^32 that is
+    // used += r, and the epilogue gets the usage back as cap - qv[d].
+    // Three scalars carried round the container loop would be the obvious home.  The compiler moves them to
+    // three vector registers: the loop's skip paths (CYCLE, QUOTA) give the structurised loop phis with an
+    // undefined input, which instruction selection materialises in a vector register, and a scalar phi with
+    // a vector input is rewritten for the vector unit with everything computed from it ----
+    uint32_t qv = 0, qlim = 0;
+    if constexpr (QT) {
+        uint32_t cap = FP_QUOTA_UNLIMITED, use = 0;
+        if (lane < FP_QUOTA_DIMS) {
+            cap = a.quota[(size_t)s * FP_QUOTA_DIMS + lane];
+            if (a.quota_used) use = a.quota_used[(size_t)s * FP_QUOTA_DIMS + lane];
+        }
+        qv = use <= cap ? cap - use : 0u;
+        qlim = (uint32_t)__ballot(cap != FP_QUOTA_UNLIMITED);
+    }
+    auto q_blocks = [&](uint32_t d, uint32_t r) { return ((qlim >> d) & 1u) != 0u && r > bcast(qv, d); };
+
     // ---- container records, 64 per chunk, one chunk ahead ----
     const uint32_t *ord = a.order + cb;
     auto ld_ord = [&](uint32_t i) -> uint32_t { return i < C ? ord[i] : 0u; };
@@ -355,6 +394,9 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
             if constexpr (FB) {
                 if (a.hops) a.hops[cb + o] = 0;
             }
+            if constexpr (QT) {
+                if (a.quota_why) a.quota_why[cb + o] = 0;
+            }
         }
     };
     gather(lane, ld_ord(lane));
@@ -371,6 +413,27 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
             const uint32_t idx = bcast(c_idx, u);
             if (idx == FP_NONE) { ++rejected; continue; }  // CYCLE (uniform)
             const uint32_t cpu = bcast(c_cpu, u), mem = bcast(c_mem, u), req = bcast(c_req, u), conf = bcast(c_conf, u);
+
+            // ---- SPEC.md 2.10: admission before scheduling.  A QUOTA container leaves like a CYCLE one, by a
+            // uniform continue before the reduction: no barrier, and par stays, so the parity still counts
+            // reductions (the header's argument) however the skipped containers fall ----
+            if constexpr (QT) {
+                const uint32_t why = (q_blocks(FP_QUOTA_CPU, cpu) ? 1u << FP_QUOTA_CPU : 0u) |
+                                     (q_blocks(FP_QUOTA_MEM, mem) ? 1u << FP_QUOTA_MEM : 0u) |
+                                     (q_blocks(FP_QUOTA_SERVICES, 1u) ? 1u << FP_QUOTA_SERVICES : 0u);
+                if (why != 0u) {  // uniform
+                    ++rejected;
+                    if (t == 0) {
+                        a.assign[cb + idx] = FP_NONE;
+                        a.reason[cb + idx] = (uint8_t)FP_REASON_QUOTA;
+                        if constexpr (FB) {
+                            if (a.hops) a.hops[cb + idx] = 0;
+                        }
+                        if (a.quota_why) a.quota_why[cb + idx] = (uint8_t)why;
+                    }
+                    continue;
+                }
+            }
 
             // ---- this thread's min key ----
             uint64_t best = KEY_NONE;
@@ -482,11 +545,19 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
                 }
             }
             if (!placed) ++rejected;
+            if constexpr (QT) {
+                // lane d's request; what the lanes from 3 up hold is never read
+                const uint32_t rq = lane == FP_QUOTA_CPU ? cpu : lane == FP_QUOTA_MEM ? mem : 1u;
+                if (placed) qv -= rq;  // u32, wraps; under a cap the test above excludes it
+            }
             if (t == 0) {
                 a.assign[cb + idx] = placed ? n : FP_NONE;
                 a.reason[cb + idx] = (uint8_t)(placed ? FP_REASON_OK : SP && best == KEY_SKEW ? FP_REASON_SKEW : FP_REASON_NOFIT);
                 if constexpr (FB) {
                     if (a.hops) a.hops[cb + idx] = (uint8_t)(placed ? (uint32_t)(best >> KEY_HOP_SHIFT) : 0u);
+                }
+                if constexpr (QT) {
+                    if (a.quota_why) a.quota_why[cb + idx] = 0;
                 }
             }
         }
@@ -517,15 +588,29 @@ __global__ __launch_bounds__(BLK) void k_policy(const PolicyArgs a) {
         }
         if (t == 0) a.cost[s] = fpd::pack_cost(rejected, used, a.scen_base + s);
     }
+    if constexpr (QT) {
+        if (t < FP_QUOTA_DIMS && a.quota_used) {  // wave 0's lanes 0..2, each its own dimension
+            // a dimension above its cap on entry admitted only zero requests: its usage stays
+            const uint32_t cap = a.quota[(size_t)s * FP_QUOTA_DIMS + t];
+            if (a.quota_used[(size_t)s * FP_QUOTA_DIMS + t] <= cap) a.quota_used[(size_t)s * FP_QUOTA_DIMS + t] = cap - qv;
+        }
+    }
 }
 
-template <bool SP, bool FB>
+template <bool SP, bool FB, bool QT>
 void launch_policy(const PolicyArgs &a, uint32_t S, uint32_t N, hipStream_t st) {
-    if (N <= 64) k_policy<64, 1, SP, FB><<<S, 64, 0, st>>>(a);
-    else if (N <= 1024) k_policy<1024, 1, SP, FB><<<S, 1024, 0, st>>>(a);
-    else if (N <= 2048) k_policy<1024, 2, SP, FB><<<S, 1024, 0, st>>>(a);
-    else if (N <= 4096) k_policy<1024, 4, SP, FB><<<S, 1024, 0, st>>>(a);
-    else k_policy<1024, 8, SP, FB><<<S, 1024, 0, st>>>(a);
+    if (N <= 64) k_policy<64, 1, SP, FB, QT><<<S, 64, 0, st>>>(a);
+    else if (N <= 1024) k_policy<1024, 1, SP, FB, QT><<<S, 1024, 0, st>>>(a);
+    else if (N <= 2048) k_policy<1024, 2, SP, FB, QT><<<S, 1024, 0, st>>>(a);
+    else if (N <= 4096) k_policy<1024, 4, SP, FB, QT><<<S, 1024, 0, st>>>(a);
+    else k_policy<1024, 8, SP, FB, QT><<<S, 1024, 0, st>>>(a);
+}
+template <bool QT>
+void launch_policy_by(bool sp, bool fb, const PolicyArgs &a, uint32_t S, uint32_t N, hipStream_t st) {
+    if (sp && fb) launch_policy<true, true, QT>(a, S, N, st);
+    else if (sp) launch_policy<true, false, QT>(a, S, N, st);
+    else if (fb) launch_policy<false, true, QT>(a, S, N, st);
+    else launch_policy<false, false, QT>(a, S, N, st);
 }
 
 static inline unsigned grid_for(size_t n, unsigned block) {
@@ -553,7 +638,8 @@ int policy_sort_tmp(hipStream_t st, uint32_t S, size_t SC, size_t *bytes) {
 
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
                                    uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
-                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops) {
+                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops,
+                                   const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why) {
     const uint32_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
     // this call resets the arena the last first-fit call's range words live in (fp_ctx_place_path)
     c->last_rng = nullptr;
@@ -568,6 +654,7 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     hipStream_t st = c->stream;
     const bool sp = domain && max_skew;  // SPEC.md 2.7: either pointer null = no constraint anywhere
     const bool fb = relax_mask && n_hops;  // SPEC.md 2.8: either pointer null = no fallback anywhere
+    const bool qt = quota != nullptr;      // SPEC.md 2.10: null = no quota anywhere; any u32 is a legal cap
 
     size_t sort_tmp = 0;
     if (C)
@@ -631,12 +718,11 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     a.relax_mask = fb ? relax_mask : nullptr; a.n_hops = fb ? n_hops : nullptr;
     a.assign = b->assign; a.reason = b->reason; a.cost = b->cost;
     a.hops = fb ? hops : nullptr;
+    a.quota = quota; a.quota_used = qt ? quota_used : nullptr; a.quota_why = qt ? quota_why : nullptr;
     a.bad = bad;
     fp_prof_begin(c, FP_K_PLACE, &ev);
-    if (sp && fb) launch_policy<true, true>(a, S, N, st);
-    else if (sp) launch_policy<true, false>(a, S, N, st);
-    else if (fb) launch_policy<false, true>(a, S, N, st);
-    else launch_policy<false, false>(a, S, N, st);
+    if (qt) launch_policy_by<true>(sp, fb, a, S, N, st);
+    else launch_policy_by<false>(sp, fb, a, S, N, st);
     FP_HIP(hipGetLastError());
     fp_prof_end(c, FP_K_PLACE, ev);
     if (hops && !fb) {

@@ -94,15 +94,21 @@ class PlacementPolicy:
     ``SpreadConstraint{topology_key, max_skew}`` (model.rs:56-63; SPEC.md 2.7), which constrains when
     both fields are set and ``max_skew`` >= 1, and ``FallbackPolicy{relax_order, max_hops}``
     (model.rs:47-54; SPEC.md 2.8): the label keys a service may give up, in that order, when the pool that
-    matches its required labels has no feasible server.  resource_quota is not read.  Two
-    policies compare equal on strategy and preferred labels, the fields SPEC.md 2.6 reads; compare
-    ``spread`` for the constraint and ``fallback`` for the chain."""
+    matches its required labels has no feasible server, and ``ResourceQuota{max_services_per_stage, cpu_cores,
+    memory_gb}`` (model.rs:38-45; SPEC.md 2.10) as three optional caps in planner units: ``quota_cpu_m``
+    (millicores), ``quota_mem_mib`` (MiB) and ``quota_services`` (services of the stage); None = no cap.
+    The quota's max_stages is not read: it caps the tenant's stage records, not a stage's placement
+    (DESIGN.md 4.8).  Two policies compare equal on strategy and preferred labels, the fields SPEC.md 2.6
+    reads; compare ``spread`` for the constraint, ``fallback`` for the chain and ``quota`` for the caps."""
     strategy: str | None = None
     preferred_labels: dict[str, str] = field(default_factory=dict)
     spread_topology_key: str | None = field(default=None, compare=False)
     spread_max_skew: int | None = field(default=None, compare=False)
     fallback_relax_order: tuple[str, ...] = field(default=(), compare=False)
     fallback_max_hops: int | None = field(default=None, compare=False)
+    quota_cpu_m: int | None = field(default=None, compare=False)
+    quota_mem_mib: int | None = field(default=None, compare=False)
+    quota_services: int | None = field(default=None, compare=False)
 
     def __post_init__(self):
         if self.strategy is not None and self.strategy not in POLICY_STRATEGIES:
@@ -111,6 +117,18 @@ class PlacementPolicy:
             raise ValueError(f"spread max_skew must be in 0..{U32_MAX}, got {self.spread_max_skew!r}")
         self.fallback_relax_order = tuple(self.fallback_relax_order)
         _ = self.fallback  # validates the chain
+        for name in ("quota_cpu_m", "quota_mem_mib", "quota_services"):
+            cap = getattr(self, name)
+            # U32_MAX itself is the ABI's "no cap" (FP_QUOTA_UNLIMITED): say None for that
+            if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or not 0 <= cap < U32_MAX):
+                raise ValueError(f"{name} must be an integer in 0..{U32_MAX - 1} or None, got {cap!r}")
+
+    @property
+    def quota(self) -> tuple[int | None, int | None, int | None] | None:
+        """(cpu millicores, memory MiB, services) when the policy has a cap in some dimension (None in the
+        others), else None."""
+        caps = (self.quota_cpu_m, self.quota_mem_mib, self.quota_services)
+        return caps if any(c is not None for c in caps) else None
 
     @property
     def fallback(self) -> tuple[str, ...]:
@@ -145,7 +163,7 @@ class PlacementPolicy:
     @property
     def active(self) -> bool:
         return (self.strategy is not None or bool(self.preferred_labels) or self.spread is not None
-                or bool(self.fallback))
+                or bool(self.fallback) or self.quota is not None)
 
 
 @dataclass
@@ -331,7 +349,7 @@ class Plan:
     levels: dict[str, int]        # Kahn levels (U32_MAX = cycle)
     level_order: list[str]        # sort by (level, position)
     assignment: dict[str, str]    # service -> server slug (unplaced absent)
-    rejected: dict[str, str]      # service -> "NOFIT" | "CYCLE"
+    rejected: dict[str, str]      # service -> "NOFIT" | "CYCLE" | "SKEW" | "QUOTA"
     # stage 2 on the stage's pristine server table: service -> (feasible servers, first feasible
     # slug or None); count 0 is an exact NOFIT before placement (SPEC.md 2.3 monotonicity)
     candidates: dict[str, tuple[int, str | None]] = field(default_factory=dict)
@@ -349,6 +367,13 @@ class Plan:
     # rejection diagnosis (SPEC.md 2.9), plan_stage(..., explain=True): service -> Why for the services
     # rejected NOFIT or SKEW, taken on the server table the placement left; empty otherwise
     why: dict[str, Why] = field(default_factory=dict)
+    # the resource quota the assignment was made under (SPEC.md 2.10): the caps (cpu millicores, memory MiB,
+    # services; None = no cap in that dimension), the tenant's usage after this plan, and service -> the
+    # dimensions that refused it ("cpu", "memory", "services") for the services rejected QUOTA.  None / empty
+    # without a quota
+    quota: tuple | None = None
+    quota_used: tuple | None = None
+    quota_why: dict[str, list[str]] = field(default_factory=dict)
 
 
 def spread_domains(nodes: list[Server], topology_key: str) -> tuple[list[int], list[bool]]:
@@ -416,7 +441,7 @@ def _stage_tables(names: list[str], flow: Flow, nodes: list[Server], preferred=(
 
 def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
                servers: list[Server] | None = None, policy: PlacementPolicy | None = None,
-               explain: bool = False) -> Plan:
+               explain: bool = False, quota_used=(0, 0, 0)) -> Plan:
     """Full planner output for one stage (SPEC.md 2): the `fleet up --dry-run`
     plan (up.rs:57-136).  One fp_plan_stage call -- A1 order, A2 levels, and with servers the stage-2
     candidates and the FFD plan -- when every service name appears once in the stage; a stage
@@ -432,6 +457,12 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
     Under a spread constraint the servers' ``topology_key=value`` labels give the domains
     (``spread_domains``); a server without the key goes to the policy call as unschedulable and
     receives nothing, and a service some server fits but none within the skew is rejected as "SKEW".
+    Under a resource quota (SPEC.md 2.10; ``policy.quota``) the assignment comes from
+    ``Planner.place_policy_quota``: ``quota_used`` = (cpu millicores, memory MiB, services) is what the
+    tenant holds already, a service the quota refuses is rejected as "QUOTA" before any server is tried,
+    ``Plan.quota_why`` names the dimensions that refused it, and ``Plan.quota`` / ``Plan.quota_used`` carry
+    the caps and the usage after the plan.  A stage without servers places nothing and is planned as
+    without a quota.
     No policy, or one that sets nothing: exactly the path above.
 
     ``explain=True`` adds the rejection diagnosis of SPEC.md 2.9: ``Plan.why[name]`` for every service
@@ -447,6 +478,7 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
     if pol is not None and not pol.active:
         pol = None
     assignment, rejected, candidates, relaxed = {}, {}, {}, {}
+    quota_after, quota_why = None, {}
     ignore = 0  # SPEC.md 2.9: the label bits a fallback chain gives up
     if not services:
         return Plan(stage_name, [], {}, [], assignment, rejected, candidates)
@@ -486,12 +518,21 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
             max_skew = pol.spread[1]
             ntab = (*ntab[:4], [s if k else 0 for s, k in zip(ntab[4], has_key)])
         strategy = pol.strategy if pol.strategy is not None else 0
-        if pol.fallback:
+        if pol.fallback or pol.quota is not None:
             ld = _stage_labels(names, flow, nodes, pol.preferred)
             relax = [ld.key_mask(k) for k in pol.fallback]
-            assign, reason, hops, after, _ = p.place_policy_fallback(cont, ntab, strategy, relax, preferred=pmask,
-                                                                     level=[lvl_v[n] for n in names], domain=domain,
-                                                                     max_skew=max_skew)
+            if pol.quota is not None:
+                from ._lib import QUOTA_NAMES
+                assign, reason, hops, after, _, qwhy, qused = p.place_policy_quota(
+                    cont, ntab, strategy, pol.quota, quota_used, relax, preferred=pmask,
+                    level=[lvl_v[n] for n in names], domain=domain, max_skew=max_skew)
+                quota_after = tuple(int(x) for x in qused)
+                quota_why = {n: [d for k, d in enumerate(QUOTA_NAMES) if qwhy[v] >> k & 1]
+                             for v, n in enumerate(names) if reason[v] == 4}
+            else:
+                assign, reason, hops, after, _ = p.place_policy_fallback(cont, ntab, strategy, relax, preferred=pmask,
+                                                                         level=[lvl_v[n] for n in names], domain=domain,
+                                                                         max_skew=max_skew)
             for m in relax:
                 ignore |= m
             for v, n in enumerate(names):
@@ -511,7 +552,7 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
             if assign[v] != NONE:
                 assignment[n] = nodes[assign[v]].slug
             else:
-                rejected[n] = "CYCLE" if reason[v] == 2 else "SKEW" if reason[v] == 3 else "NOFIT"
+                rejected[n] = {2: "CYCLE", 3: "SKEW", 4: "QUOTA"}.get(int(reason[v]), "NOFIT")
         sel = [v for v, n in enumerate(names) if rejected.get(n) in ("NOFIT", "SKEW")]
         if explain and sel:
             # cont holds the tables of the call that made the assignment, `after` the server table it left
@@ -528,6 +569,8 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
         if pol.fallback:
             plan.fallback_relax_order, plan.fallback_max_hops = list(pol.fallback_relax_order), pol.fallback_max_hops
             plan.relaxed = relaxed
+        if pol.quota is not None:
+            plan.quota, plan.quota_used, plan.quota_why = pol.quota, quota_after, quota_why
     return plan
 
 

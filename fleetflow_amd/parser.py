@@ -27,6 +27,7 @@ class FlowError(ValueError):
 
 
 _RESTART = {"no", "always", "on-failure", "unless-stopped"}
+_QUOTA_PROPS = ("cpu", "memory", "services")  # the `quota` child of `placement` (SPEC.md 4), in fp_quota_dim order
 
 
 def _first_str(node):
@@ -173,9 +174,11 @@ def parse_stage(node) -> tuple[str, Stage, dict[str, Service]]:
 
 def parse_placement(node, stage_name: str) -> PlacementPolicy:
     """``placement strategy="spread_across_pool" { prefer "region=tokyo"; spread "region" max-skew=1;
-    fallback "class" "region" max-hops=2 }``: the tenant PlacementPolicy's strategy constant, soft preferred
-    labels, hard SpreadConstraint{topology_key, max_skew} and FallbackPolicy{relax_order, max_hops}
-    (controlplane model.rs:47-95; ``max-hops`` is optional)."""
+    fallback "class" "region" max-hops=2; quota cpu=4000 memory=8192 services=10 }``: the tenant
+    PlacementPolicy's strategy constant, soft preferred labels, hard SpreadConstraint{topology_key, max_skew},
+    FallbackPolicy{relax_order, max_hops} and ResourceQuota (controlplane model.rs:38-95; ``max-hops`` is
+    optional).  ``quota`` takes its caps in the units of the ``resources`` node (millicores, MiB) and a
+    service count; each is optional, one at least is required (SPEC.md 2.10, 4)."""
     strategy = None
     if node.has("strategy"):
         strategy = as_str(node.get("strategy"))
@@ -185,6 +188,7 @@ def parse_placement(node, stage_name: str) -> PlacementPolicy:
     preferred: dict[str, str] = {}
     spread_key = spread_skew = None
     relax_order, max_hops = (), None
+    quota = None
     for ch in node.children or []:
         if ch.name == "prefer":
             for _, v in ch.entries:
@@ -219,8 +223,24 @@ def parse_placement(node, stage_name: str) -> PlacementPolicy:
                 if not kdl.is_int(hops) or hops < 0:
                     raise FlowError(f"stage {stage_name}: fallback max-hops must be an integer >= 0, got {hops!r}")
             relax_order, max_hops = tuple(keys), hops
+        elif ch.name == "quota":
+            if quota is not None:
+                raise FlowError(f"stage {stage_name}: placement has more than one quota node")
+            props = [k for k, _ in ch.entries if k is not None]
+            if ch.args() or not props or any(k not in _QUOTA_PROPS for k in props):
+                raise FlowError(f"stage {stage_name}: quota takes cpu=<millicores> memory=<MiB> services=<count> "
+                                f"(one at least, nothing else), got {ch.args() + props!r}")
+            quota = {}
+            for k in _QUOTA_PROPS:
+                if ch.has(k):
+                    v = ch.get(k)
+                    if not kdl.is_int(v) or not 0 <= v < U32_MAX:
+                        raise FlowError(f"stage {stage_name}: quota {k} must be an integer in 0..{U32_MAX - 1}, got {v!r}")
+                    quota[k] = v
+    quota = quota or {}
     try:
-        return PlacementPolicy(strategy, preferred, spread_key, spread_skew, relax_order, max_hops)
+        return PlacementPolicy(strategy, preferred, spread_key, spread_skew, relax_order, max_hops,
+                               quota.get("cpu"), quota.get("memory"), quota.get("services"))
     except ValueError as e:
         raise FlowError(f"stage {stage_name}: {e}") from None
 

@@ -6,7 +6,10 @@
 policy ``placement`` (``strategy``, ``preferred``, ``spread``, ``fallback``) and, under a fallback chain
 (SPEC.md 2.8), ``relaxed``: the label keys each relaxed service gave up.  A plan made with
 ``plan_stage(..., explain=True)`` carries ``why``: the rejection diagnosis (SPEC.md 2.9) of each service
-rejected NOFIT or SKEW; the key is absent when there is none.
+rejected NOFIT or SKEW; the key is absent when there is none.  A plan made under a resource quota
+(SPEC.md 2.10) carries ``quota`` (``caps`` and the usage after the plan, ``used``, per dimension; a null
+cap is none) and ``quota_why``: the dimensions that refused each service rejected QUOTA.  Both keys are
+absent without a quota.
 
 ``format_up_dry_run`` / ``format_deploy_dry_run`` reproduce the reference's
 ``fleet up --dry-run`` (crates/fleetflow/src/commands/up.rs:57-136) and
@@ -24,6 +27,7 @@ import json
 
 from dataclasses import asdict
 
+from ._lib import QUOTA_NAMES
 from .flow import U32_MAX, WHY_NAMES, Flow, Plan, Why
 from .parser import FlowError
 
@@ -50,13 +54,18 @@ def plan_to_json(plan: Plan, indent: int | None = None) -> str:
             d["relaxed"] = plan.relaxed
     if plan.why:  # rejection diagnosis (SPEC.md 2.9)
         d["why"] = {k: asdict(w) for k, w in plan.why.items()}
+    if plan.quota is not None:  # resource quota (SPEC.md 2.10)
+        d["quota"] = {"caps": dict(zip(QUOTA_NAMES, plan.quota)),
+                      "used": dict(zip(QUOTA_NAMES, plan.quota_used)) if plan.quota_used is not None else None}
+        d["quota_why"] = plan.quota_why
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
 def plan_from_json(text: str) -> Plan:
     d = json.loads(text)
     pol = d.get("placement") or {}
-    return Plan(d["stage"], d["order"], {k: (U32_MAX if v is None else v) for k, v in d["levels"].items()},
+    q = d.get("quota")
+    plan = Plan(d["stage"], d["order"], {k: (U32_MAX if v is None else v) for k, v in d["levels"].items()},
                 d["level_order"], d["assign"], d["rejected"],
                 {k: (v["count"], v["first"]) for k, v in d.get("candidates", {}).items()},
                 pol.get("strategy"), list(pol.get("preferred") or []),
@@ -65,6 +74,11 @@ def plan_from_json(text: str) -> Plan:
                 {k: list(v) for k, v in (d.get("relaxed") or {}).items()},
                 {k: Why(dict(w["fail"]), dict(w["only"]), w["feasible"], list(w["universal"]), list(w["missing_labels"]),
                         w["nearest"], w.get("servers", 0)) for k, w in (d.get("why") or {}).items()})
+    if q is not None:
+        plan.quota = tuple(q["caps"].get(n) for n in QUOTA_NAMES)
+        plan.quota_used = tuple(q["used"][n] for n in QUOTA_NAMES) if q.get("used") is not None else None
+        plan.quota_why = {k: list(v) for k, v in (d.get("quota_why") or {}).items()}
+    return plan
 
 
 def get_network_name(project: str, stage: str) -> str:
@@ -103,6 +117,8 @@ def _service_block(flow: Flow, stage: str, name: str, container_suffix: str, pla
             lines.append(f"    é…ç½®å…ˆ: {plan.assignment[name]}" + (f" (ç·©å’Œ: {', '.join(relaxed)})" if relaxed else ""))
         elif name in plan.rejected:
             lines.append(f"    é…ç½®å…ˆ: (é…ç½®ä¸å¯: {plan.rejected[name]})")
+            if name in plan.quota_why:  # SPEC.md 2.10: the dimensions of the quota that refused it
+                lines.append(f"    ã‚¯ã‚©ãƒ¼ã‚¿è¶…é: {', '.join(plan.quota_why[name])}")
             if name in plan.why:
                 lines.append(_why_line(plan.why[name]))
         else:
@@ -129,10 +145,11 @@ _FOOTER = "[dry-run] å®Ÿéš›ã®æ“ä½œã¯è¡Œã‚ã‚Œã¾ã›ã‚“ã€‚--dry-run ã‚’å¤–ã—ã
 
 
 def _policy_lines(plan: Plan | None) -> list[str]:
-    """The placement strategy (SPEC.md 2.6), the hard topology spread (2.7) and the fallback chain (2.8) a
-    plan was made under; nothing without any."""
+    """The placement strategy (SPEC.md 2.6), the hard topology spread (2.7), the fallback chain (2.8) and
+    the resource quota (2.10: use after the plan / cap, per capped dimension) a plan was made under; nothing
+    without any."""
     if plan is None or (plan.strategy is None and not plan.preferred and plan.spread_topology_key is None
-                        and not plan.fallback_relax_order):
+                        and not plan.fallback_relax_order and plan.quota is None):
         return []
     line = f"  é…ç½®æˆ¦ç•¥: {plan.strategy if plan.strategy is not None else 'first_fit'}"
     if plan.preferred:
@@ -143,6 +160,10 @@ def _policy_lines(plan: Plan | None) -> list[str]:
     if plan.fallback_relax_order:
         hops = "" if plan.fallback_max_hops is None else f" (max_hops={plan.fallback_max_hops})"
         lines.append(f"  é…ç½®ãƒ•ã‚©ãƒ¼ãƒ«ãƒãƒƒã‚¯: {' â†’ '.join(plan.fallback_relax_order)}{hops}")
+    if plan.quota is not None:
+        used = plan.quota_used if plan.quota_used is not None else (None,) * len(QUOTA_NAMES)
+        parts = [f"{n} {'?' if u is None else u}/{c}" for n, c, u in zip(QUOTA_NAMES, plan.quota, used) if c is not None]
+        lines.append(f"  é…ç½®ã‚¯ã‚©ãƒ¼ã‚¿: {', '.join(parts)}")
     return lines
 
 

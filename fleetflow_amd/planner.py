@@ -429,6 +429,107 @@ class Planner:
               "fp_place_batch_policy_fallback")
         return assign, reason, hops, cost, (cf, mf, lab, cu, sched), nc
 
+    @staticmethod
+    def _quota_rows(quota, S):
+        """[S * 3] u32 caps from S rows of (cpu_m, mem_mib, services); None in a row = QUOTA_UNLIMITED."""
+        rows = np.asarray([[_lib.QUOTA_UNLIMITED if x is None else int(x) for x in row]
+                           for row in np.asarray(quota, dtype=object).reshape(-1, _lib.QUOTA_DIMS)], dtype=np.int64)
+        if rows.shape[0] != S or rows.min(initial=0) < 0 or rows.max(initial=0) > 0xFFFFFFFF:
+            raise ValueError(f"quota must hold {S} rows of {_lib.QUOTA_DIMS} u32 caps")
+        return rows.astype(np.uint32).reshape(-1)
+
+    def place_policy_quota(self, cont, nodes, strategy, quota, quota_used=None, relax_mask=(), preferred=0, level=None,
+                           node_count=None, *, domain=None, max_skew=0, n_hops=None, want_hops=True, want_why=True,
+                           want_used=True):
+        """place_policy_fallback under a resource quota (SPEC.md 2.10, fp_place_policy_quota): ``quota`` =
+        (cpu millicores, memory MiB, services), None or QUOTA_UNLIMITED in a dimension = no cap there;
+        ``quota_used`` what the tenant holds already (None = zeros).  A container the quota refuses comes back
+        with reason REASON_QUOTA and the mask of the blocking dimensions in quota_why; it is tried on no node.
+        ``quota`` None is no quota: the fallback entry's result, quota_why all zero, usage as given.  Returns
+        (assign, reason, hops, nodes_after, node_count_after, quota_why, quota_used_after); quota_why is None
+        with ``want_why`` False, and with ``want_used`` False the library gets no quota_used (usage starts at
+        zero whatever was passed) and None comes back."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
+        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
+        C, N = cpu.size, cf.size
+        lv = _u32(level) if level is not None else None
+        nc = _u32(node_count).copy() if node_count is not None else None
+        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
+        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
+        self._need(lv is None or lv.size == C, "level must hold C entries")
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        dom = _u32(domain) if domain is not None else None
+        self._need(dom is None or dom.size == N, "domain must hold N entries")
+        self._need(0 <= int(max_skew) <= 0xFFFFFFFF, "max_skew must be a u32")
+        rm = _u32(self._relax_row(relax_mask))
+        nh = len(relax_mask) if n_hops is None else int(n_hops)
+        self._need(0 <= nh <= 0xFFFFFFFF, "n_hops must be a u32")
+        qt = self._quota_rows(quota, 1) if quota is not None else None
+        qu = None
+        if want_used:
+            qu = _u32([0] * _lib.QUOTA_DIMS if quota_used is None else quota_used).copy()
+            self._need(qu.size == _lib.QUOTA_DIMS, "quota_used must hold 3 entries")
+        assign = np.empty(C, np.uint32)
+        reason = np.empty(C, np.uint8)
+        hops = np.empty(C, np.uint8) if want_hops else None
+        why = np.zeros(C, np.uint8) if want_why else None
+        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
+        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
+        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        p8 = lambda a: a.ctypes.data_as(_lib.u8p) if a is not None else None  # noqa: E731
+        check(self._L.fp_place_policy_quota(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
+                                            int(preferred) & 0xFFFFFFFF, p32(nc), p32(dom), int(max_skew), p32(rm), nh,
+                                            p32(assign), p8(reason), p8(hops), p32(qt), p32(qu), p8(why)),
+              "fp_place_policy_quota")
+        return assign, reason, hops, (cf, mf, lab, cu, sched), nc, why, qu
+
+    def place_batch_policy_quota(self, S, C, N, cont, nodes, strategy, quota, quota_used=None, preferred=None,
+                                 level=None, node_count=None, scen_base=0, *, domain=None, max_skew=None,
+                                 relax_mask=None, n_hops=None, want_hops=True, want_why=True, want_used=True):
+        """place_batch_policy_fallback under per-scenario quotas (SPEC.md 2.10): ``quota`` [S * 3] (rows of
+        cpu, memory, services; QUOTA_UNLIMITED = no cap), ``quota_used`` [S * 3] or None = zeros; ``quota``
+        None is no quota anywhere.  Returns (assign, reason, hops, cost, nodes_after, node_count_after,
+        quota_why [S*C], quota_used_after [S*3]); the ``want_*`` switches as in place_policy_quota."""
+        cpu, mem, req, conf = (_u32(x) for x in cont)
+        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
+        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
+        lv = _u32(level) if level is not None else None
+        st = _u32([strategy_id(x) for x in strategy])
+        pf = _u32(preferred) if preferred is not None else None
+        nc = _u32(node_count).copy() if node_count is not None else None
+        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
+        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
+        self._need(lv is None or lv.size == S * C, "level must hold S * C entries")
+        self._need(st.size == S and (pf is None or pf.size == S), "strategy and preferred must hold S entries")
+        self._need(nc is None or nc.size == S * N, "node_count must hold S * N entries")
+        dom = sk = rm = nh = None
+        if domain is not None and max_skew is not None:
+            dom, sk = _u32(domain), _u32(max_skew)
+            self._need(dom.size == S * N and sk.size == S, "domain must hold S * N and max_skew S entries")
+        if relax_mask is not None and n_hops is not None:
+            rm, nh = _u32(relax_mask).reshape(-1), _u32(n_hops)
+            self._need(rm.size == S * _lib.FP_FALLBACK_MAX_HOPS and nh.size == S,
+                       "relax_mask must hold S * FP_FALLBACK_MAX_HOPS and n_hops S entries")
+        qt = self._quota_rows(quota, S) if quota is not None else None
+        qu = None
+        if want_used:
+            qu = (np.zeros(S * _lib.QUOTA_DIMS, np.uint32) if quota_used is None else _u32(quota_used).reshape(-1).copy())
+            self._need(qu.size == S * _lib.QUOTA_DIMS, "quota_used must hold S * 3 entries")
+        assign = np.empty(S * C, np.uint32)
+        reason = np.empty(S * C, np.uint8)
+        hops = np.empty(S * C, np.uint8) if want_hops else None
+        why = np.zeros(S * C, np.uint8) if want_why else None
+        cost = np.empty(S, np.uint64)
+        b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
+                    _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
+        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
+        p8 = lambda a: a.ctypes.data_as(_lib.u8p) if a is not None else None  # noqa: E731
+        check(self._L.fp_place_batch_policy_quota(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc), p32(dom), p32(sk),
+                                                  p32(rm), p32(nh), p8(hops), p32(qt), p32(qu), p8(why)),
+              "fp_place_batch_policy_quota")
+        return assign, reason, hops, cost, (cf, mf, lab, cu, sched), nc, why, qu
+
     def feasibility(self, cont, nodes, bitmap=True):
         cpu, mem, req, conf = (_u32(x) for x in cont)
         cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
@@ -570,6 +671,40 @@ class Planner:
             self._ctx, ct.byref(db.struct()), p(strategy_t), p(preferred_t), p(count_t), p(domain_t), p(max_skew_t),
             p(relax_mask_t), p(n_hops_t), p(hops_t)), "fp_dev_place_batch_policy_fallback"))
         return hops_t
+
+    def dev_place_batch_policy_quota(self, db: "DevBatch", strategy_t, quota_t, quota_used_t=None, preferred_t=None,
+                                     count_t=None, *, domain_t=None, max_skew_t=None, relax_mask_t=None, n_hops_t=None,
+                                     hops_t=None, quota_why_t=None):
+        """fp_dev_place_batch_policy_quota: dev_place_batch_policy_fallback under the quotas of SPEC.md 2.10
+        -- ``quota_t`` [S * 3] (int32 storage of u32 caps, -1 = QUOTA_UNLIMITED; None = no quota anywhere),
+        ``quota_used_t`` [S * 3] in/out or None (usage starts at zero and is not returned), ``quota_why_t``
+        [S*C] uint8 out or None.  Returns (hops_t, quota_why_t, quota_used_t)."""
+        self._need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
+        self._need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
+        self._need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
+        if domain_t is None or max_skew_t is None:
+            domain_t = max_skew_t = None
+        else:
+            self._need(domain_t.numel() == db.S * db.N and max_skew_t.numel() == db.S,
+                       "domain_t must hold S * N and max_skew_t S entries")
+        if relax_mask_t is None or n_hops_t is None:
+            relax_mask_t = n_hops_t = None
+        else:
+            self._need(relax_mask_t.numel() == db.S * _lib.FP_FALLBACK_MAX_HOPS and n_hops_t.numel() == db.S,
+                       "relax_mask_t must hold S * FP_FALLBACK_MAX_HOPS and n_hops_t S entries")
+        self._need(hops_t is None or (hops_t.numel() == db.S * db.C and hops_t.element_size() == 1),
+                   "hops_t must hold S * C bytes")
+        for t in (quota_t, quota_used_t):
+            self._need(t is None or (t.numel() == db.S * _lib.QUOTA_DIMS and t.element_size() == 4),
+                       "quota_t and quota_used_t must hold S * 3 32-bit entries")
+        self._need(quota_why_t is None or (quota_why_t.numel() == db.S * db.C and quota_why_t.element_size() == 1),
+                   "quota_why_t must hold S * C bytes")
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._dev(lambda: check(self._L.fp_dev_place_batch_policy_quota(
+            self._ctx, ct.byref(db.struct()), p(strategy_t), p(preferred_t), p(count_t), p(domain_t), p(max_skew_t),
+            p(relax_mask_t), p(n_hops_t), p(hops_t), p(quota_t), p(quota_used_t), p(quota_why_t)),
+            "fp_dev_place_batch_policy_quota"))
+        return hops_t, quota_why_t, quota_used_t
 
     def dev_argmin_cost(self, cost_t, out_t):
         self._dev(lambda: check(self._L.fp_dev_argmin_cost(self._ctx, cost_t.data_ptr(), cost_t.numel(),

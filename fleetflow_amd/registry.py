@@ -95,10 +95,13 @@ def placement_policy(tenant_row: dict | None) -> PlacementPolicy | None:
     """A tenant row's ``placement_policy`` (as JSON; model.rs:82-95) -> the planner's policy: its
     ``strategy`` constant, soft ``preferred_labels`` map, hard ``spread_constraint``
     (``topology_key``, ``max_skew``; SPEC.md 2.7) and ``fallback_policy`` (``relax_order``, ``max_hops``;
-    SPEC.md 2.8).  None when the row has no policy; a strategy that is none of the three constants, a
-    constraint with a key and a ``max_skew`` below 1, a ``relax_order`` that is no list of label keys, a
-    ``max_hops`` that is no integer >= 0, or a chain of more than four effective hops is a ValueError.
-    ``resource_quota`` is not read."""
+    SPEC.md 2.8) and ``resource_quota`` (SPEC.md 2.10): ``cpu_cores`` * 1000 millicores, ``memory_gb`` * 1024
+    MiB and ``max_services_per_stage`` as it is; a missing or null field is no cap, and a value past what a
+    u32 cap can say (0xFFFFFFFE) is no cap either.  The quota's ``max_stages`` is not read: it caps the
+    tenant's stage records, not a stage's placement.  None when the row has no policy; a strategy that is
+    none of the three constants, a constraint with a key and a ``max_skew`` below 1, a ``relax_order`` that
+    is no list of label keys, a ``max_hops`` that is no integer >= 0, a chain of more than four effective
+    hops, or a quota field that is negative or no integer is a ValueError."""
     pol = (tenant_row or {}).get("placement_policy")
     if pol is None:
         return None
@@ -120,7 +123,17 @@ def placement_policy(tenant_row: dict | None) -> PlacementPolicy | None:
     order, hops = fb.get("relax_order") or (), fb.get("max_hops")
     if isinstance(order, str) or not all(isinstance(k, str) for k in order):
         raise ValueError(f"fallback_policy: relax_order must be a list of label keys, got {order!r}")
-    return PlacementPolicy(strategy, {str(k): str(v) for k, v in pref.items()}, key, skew, tuple(order), hops)
+    rq = pol.get("resource_quota") or {}
+    if not isinstance(rq, dict):
+        raise ValueError(f"resource_quota must be an object, got {rq!r}")
+    caps = []
+    for name, scale in (("cpu_cores", 1000), ("memory_gb", 1024), ("max_services_per_stage", 1)):
+        v = rq.get(name)
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+            raise ValueError(f"resource_quota: {name} must be an integer >= 0 or null, got {v!r}")
+        # a cap too large for the u32 of the ABI cannot bind before the usage wraps: no cap
+        caps.append(None if v is None or v * scale >= U32_MAX else v * scale)
+    return PlacementPolicy(strategy, {str(k): str(v) for k, v in pref.items()}, key, skew, tuple(order), hops, *caps)
 
 
 def pool_required_labels(pool: dict | None) -> list[str]:

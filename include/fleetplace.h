@@ -20,6 +20,8 @@
  *                        crates/fleetflow-controlplane/src/model.rs:56-63
  *   fp_place_policy_fallback <- new: the same under the policy's FallbackPolicy{relax_order, max_hops}
  *                        crates/fleetflow-controlplane/src/model.rs:47-54
+ *   fp_place_policy_quota <- new: the same under the policy's ResourceQuota{max_services_per_stage, cpu_cores,
+ *                        memory_gb}  crates/fleetflow-controlplane/src/model.rs:38-45
  *   fp_feasibility    <- new: stage-2 containers x nodes feasibility/score sweep
  *   fp_dev_feasibility_batch <- new: the same sweep over many what-if scenarios
  *   fp_explain        <- new: per-cause diagnosis of unplaced containers (which 2.3 predicate fails where)
@@ -77,8 +79,9 @@ extern "C" {
 
 #define FP_NONE 0xFFFFFFFFu /* "no node" / "no level" (cycle)                    */
 
-/* FP_REASON_SKEW: only from the *_policy_spread entries (SPEC.md 2.7): some node fits, none within max_skew */
-enum fp_reason { FP_REASON_OK = 0, FP_REASON_NOFIT = 1, FP_REASON_CYCLE = 2, FP_REASON_SKEW = 3 };
+/* FP_REASON_SKEW: only from the *_policy_spread entries (SPEC.md 2.7): some node fits, none within max_skew
+ * FP_REASON_QUOTA: only from the *_policy_quota entries (SPEC.md 2.10): the tenant's quota refuses the request */
+enum fp_reason { FP_REASON_OK = 0, FP_REASON_NOFIT = 1, FP_REASON_CYCLE = 2, FP_REASON_SKEW = 3, FP_REASON_QUOTA = 4 };
 
 typedef struct fp_ctx fp_ctx;
 
@@ -267,6 +270,37 @@ int fp_place_batch_policy_fallback(fp_ctx *ctx, const fp_batch *b, const uint32_
                                    const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
                                    const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
                                    uint8_t *hops_out);
+/* Scored placement under a resource quota (SPEC.md 2.10), the PlacementPolicy's ResourceQuota (model.rs:38-45;
+ * the counterpart of a k8s ResourceQuota: admission before scheduling).  quota[d] caps what the tenant may hold
+ * in dimension d -- FP_QUOTA_CPU in millicores, FP_QUOTA_MEM in MiB, FP_QUOTA_SERVICES in containers --
+ * and FP_QUOTA_UNLIMITED is no cap there.  quota_used[d] (in/out, nullable: NULL starts at zero and returns
+ * nothing, as node_count) is what the tenant holds already.  Containers are visited in the FFD order; a CYCLE
+ * container is neither tested nor charged.  With r = (cpu_m, mem_mib, 1), dimension d blocks when
+ *   quota[d] != FP_QUOTA_UNLIMITED && r[d] != 0 && !(used[d] <= quota[d] && r[d] <= quota[d] - used[d])
+ * so a dimension the container asks nothing of is not tested, and a used above its cap blocks every
+ * non-zero request.  A blocked container is FP_REASON_QUOTA (assign FP_NONE, hop 0, counted as rejected in the
+ * cost) with the mask of the blocking dimensions (bit d) in quota_why_out; no node is searched and no state
+ * changes.  Any other container is placed exactly as fp_place_policy_fallback places it, its quota_why is 0,
+ * and when it is placed used[d] += r[d] in all three dimensions (u32, wraps; not under a finite cap).  NOFIT
+ * and SKEW leave the usage as it was.  A quota of three FP_QUOTA_UNLIMITED is no quota: that scenario is
+ * exactly fp_place_policy_fallback.  quota = NULL is no quota anywhere: the call is the _fallback entry, and
+ * quota_used and quota_why_out are neither read nor written.  quota_why_out is nullable.  Every u32 is a legal
+ * cap.  With no container to place quota_used stays as given.  ResourceQuota.max_stages is not a placement
+ * input (it caps the tenant's stage records) and has no counterpart here. */
+enum fp_quota_dim { FP_QUOTA_CPU = 0, FP_QUOTA_MEM = 1, FP_QUOTA_SERVICES = 2, FP_QUOTA_DIMS = 3 };
+#define FP_QUOTA_UNLIMITED 0xFFFFFFFFu
+/* quota, quota_used: [FP_QUOTA_DIMS]; quota_why_out: [C] */
+int fp_place_policy_quota(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32_t *level,
+                          uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                          const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                          uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out, const uint32_t *quota,
+                          uint32_t *quota_used, uint8_t *quota_why_out);
+/* quota, quota_used: [S][FP_QUOTA_DIMS]; quota_why_out: [S][C] */
+int fp_place_batch_policy_quota(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                                const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                                const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
+                                uint8_t *hops_out, const uint32_t *quota, uint32_t *quota_used,
+                                uint8_t *quota_why_out);
 /* Stage 2: first feasible node (FP_NONE) and feasible-node count per container on
  * the given node state; bitmap_out (nullable, ceil(C/64) * N words) holds
  * bit (c, n) at word [(c/64) * N + n], bit c % 64. */
@@ -366,6 +400,13 @@ int fp_dev_place_batch_policy_fallback(fp_ctx *ctx, const fp_batch *b, const uin
                                        const uint32_t *preferred_labels, uint32_t *node_count,
                                        const uint32_t *domain, const uint32_t *max_skew, const uint32_t *relax_mask,
                                        const uint32_t *n_hops, uint8_t *hops_out);
+/* As fp_place_batch_policy_quota on device pointers.  The errors are those of fp_dev_place_batch_policy_fallback
+ * (a quota has no illegal value): nothing is written, quota_used and quota_why_out included. */
+int fp_dev_place_batch_policy_quota(fp_ctx *ctx, const fp_batch *b, const uint32_t *strategy,
+                                    const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                                    const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
+                                    uint8_t *hops_out, const uint32_t *quota, uint32_t *quota_used,
+                                    uint8_t *quota_why_out);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

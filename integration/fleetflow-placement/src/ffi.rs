@@ -16,6 +16,7 @@ pub const FP_REASON_OK: u8 = 0;
 pub const FP_REASON_NOFIT: u8 = 1;
 pub const FP_REASON_CYCLE: u8 = 2;
 pub const FP_REASON_SKEW: u8 = 3;
+pub const FP_REASON_QUOTA: u8 = 4;
 pub const FP_STRATEGY_FIRST_FIT: u32 = 0;
 pub const FP_STRATEGY_SPREAD: u32 = 1;
 pub const FP_STRATEGY_PACK: u32 = 2;
@@ -23,6 +24,12 @@ pub const FP_STRATEGY_FILL_LOWEST: u32 = 3;
 pub const FP_POLICY_MAX_NODES: u32 = 8192;
 pub const FP_SPREAD_MAX_DOMAINS: u32 = 64;
 pub const FP_FALLBACK_MAX_HOPS: u32 = 4;
+// resource quota (SPEC.md 2.10): enum fp_quota_dim (the index in a quota row and the bit in quota_why)
+pub const FP_QUOTA_CPU: usize = 0;
+pub const FP_QUOTA_MEM: usize = 1;
+pub const FP_QUOTA_SERVICES: usize = 2;
+pub const FP_QUOTA_DIMS: usize = 3;
+pub const FP_QUOTA_UNLIMITED: u32 = 0xFFFF_FFFF;
 // rejection diagnosis (SPEC.md 2.9): enum fp_why, the word indices of a row and of a histogram
 pub const FP_WHY_CORDON: u32 = 1;
 pub const FP_WHY_CPU: u32 = 2;
@@ -182,6 +189,16 @@ unsafe extern "C" {
                                           preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
                                           max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
                                           hops_out: *mut u8) -> c_int;
+    pub fn fp_place_policy_quota(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
+                                 strategy: u32, preferred_labels: u32, node_count: *mut u32, domain: *const u32,
+                                 max_skew: u32, relax_mask: *const u32, n_hops: u32, assign_out: *mut u32,
+                                 reason_out: *mut u8, hops_out: *mut u8, quota: *const u32, quota_used: *mut u32,
+                                 quota_why_out: *mut u8) -> c_int;
+    pub fn fp_place_batch_policy_quota(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                       preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                       max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
+                                       hops_out: *mut u8, quota: *const u32, quota_used: *mut u32,
+                                       quota_why_out: *mut u8) -> c_int;
     pub fn fp_feasibility(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, first_out: *mut u32,
                           count_out: *mut u32, bitmap_out: *mut u64) -> c_int;
     pub fn fp_explain(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, sel: *const u32, n_sel: u32,
@@ -216,6 +233,11 @@ unsafe extern "C" {
                                               preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
                                               max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
                                               hops_out: *mut u8) -> c_int;
+    pub fn fp_dev_place_batch_policy_quota(ctx: *mut fp_ctx, b: *const fp_batch, strategy: *const u32,
+                                           preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                           max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
+                                           hops_out: *mut u8, quota: *const u32, quota_used: *mut u32,
+                                           quota_why_out: *mut u8) -> c_int;
     pub fn fp_dev_argmin_cost(ctx: *mut fp_ctx, cost: *const u64, n: u32, best_dev: *mut u32) -> c_int;
     pub fn fp_dev_gen_batch(ctx: *mut fp_ctx, seed: u64, b: *const fp_batch, flags: u32) -> c_int;
 }

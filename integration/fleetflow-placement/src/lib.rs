@@ -227,6 +227,47 @@ impl Planner {
         Ok((assign, reason, hops))
     }
 
+    /// Scored placement under a resource quota (SPEC.md 2.10, fleetplace.h `fp_place_policy_quota`), the
+    /// PlacementPolicy's `ResourceQuota { max_services_per_stage, cpu_cores, memory_gb }` in planner units:
+    /// `quota` = [cpu millicores, memory MiB, services], `ffi::FP_QUOTA_UNLIMITED` for no cap in a
+    /// dimension; `quota_used` is what the tenant holds already and is updated in place (None starts at
+    /// zero).  A container the quota refuses has reason `ffi::FP_REASON_QUOTA` and the mask of the blocking
+    /// dimensions (bit `ffi::FP_QUOTA_*`) in the last vector; it is tried on no node and charged nothing.
+    /// The other arguments are `place_policy_fallback`'s.  Returns (assign, reason, hops, quota_why).
+    /// `max_stages` has no counterpart: it caps the tenant's stage records, not a stage's placement.
+    pub fn place_policy_quota(&mut self, c: &Containers, nodes: &mut Nodes, level: Option<&[u32]>, strategy: u32,
+                              preferred_labels: u32, node_count: Option<&mut [u32]>, spread: Option<(&[u32], u32)>,
+                              relax_mask: &[u32], quota: &[u32; ffi::FP_QUOTA_DIMS],
+                              quota_used: Option<&mut [u32; ffi::FP_QUOTA_DIMS]>)
+                              -> Result<(Vec<u32>, Vec<u8>, Vec<u8>, Vec<u8>), PlanError> {
+        let n = c.cpu_m.len();
+        let nn = nodes.cpu_free.len();
+        if !c.all_len(n) || !nodes.all_len(nn) || level.map_or(false, |l| l.len() != n)
+            || node_count.as_ref().map_or(false, |k| k.len() != nn) || spread.map_or(false, |(d, _)| d.len() != nn)
+            || relax_mask.len() > ffi::FP_FALLBACK_MAX_HOPS as usize {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        let mut ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_mut_ptr(),
+                                     mem_free: nodes.mem_free.as_mut_ptr(), labels: nodes.labels.as_ptr(),
+                                     conflict_used: nodes.conflict_used.as_mut_ptr(),
+                                     schedulable: nodes.schedulable.as_ptr() };
+        let (mut assign, mut reason, mut hops, mut why) = (vec![0u32; n], vec![0u8; n], vec![0u8; n], vec![0u8; n]);
+        let count_ptr = node_count.map_or(std::ptr::null_mut(), |k| k.as_mut_ptr());
+        let used_ptr = quota_used.map_or(std::ptr::null_mut(), |u| u.as_mut_ptr());
+        let mut masks = [0u32; ffi::FP_FALLBACK_MAX_HOPS as usize];
+        masks[..relax_mask.len()].copy_from_slice(relax_mask);
+        let (domain, max_skew) = spread.map_or((std::ptr::null(), 0), |(d, k)| (d.as_ptr(), k));
+        check(unsafe {
+            ffi::fp_place_policy_quota(self.ctx, &cs, &mut ns, level.map_or(std::ptr::null(), |l| l.as_ptr()),
+                                       strategy, preferred_labels, count_ptr, domain, max_skew, masks.as_ptr(),
+                                       relax_mask.len() as u32, assign.as_mut_ptr(), reason.as_mut_ptr(),
+                                       hops.as_mut_ptr(), quota.as_ptr(), used_ptr, why.as_mut_ptr())
+        })?;
+        Ok((assign, reason, hops, why))
+    }
+
     /// One stage's whole dry-run plan in one call (fleetplace.h `fp_plan_stage`, the
     /// `fleet up --dry-run` path of up.rs:57-136): the legacy order, the Kahn levels and start
     /// order and, with `placement = Some((containers, nodes))` (container v = vertex v), the
@@ -617,6 +658,25 @@ pub fn place_stage_with_policy(flow: &Flow, stage_name: &str, c: &Containers, no
     }
     let (assign, _) = with_planner(|p| p.place_policy(c, nodes, None, strategy, preferred_labels, node_count))?;
     Ok(assign.iter().map(|&a| if a == ffi::FP_NONE { None } else { Some(stage.servers[a as usize].clone()) }).collect())
+}
+
+/// `place_stage_with_policy` under the tenant's resource quota (SPEC.md 2.10): `quota` and `quota_used` as
+/// in [`Planner::place_policy_quota`].  Per service: its server, or None with the reason
+/// (`ffi::FP_REASON_QUOTA` for a service the quota refused) and the mask of the blocking dimensions.
+pub fn place_stage_with_quota(flow: &Flow, stage_name: &str, c: &Containers, nodes: &mut Nodes, strategy: u32,
+                              preferred_labels: u32, node_count: Option<&mut [u32]>,
+                              quota: &[u32; ffi::FP_QUOTA_DIMS], quota_used: Option<&mut [u32; ffi::FP_QUOTA_DIMS]>)
+                              -> Result<Vec<(Option<String>, u8, u8)>, PlanError> {
+    let Some(stage) = flow.stages.get(stage_name) else { return Err(PlanError(ffi::FP_EINVAL)) };
+    if nodes.cpu_free.len() != stage.servers.len() || c.cpu_m.len() != stage.services.len() {
+        return Err(PlanError(ffi::FP_EINVAL));
+    }
+    let (assign, reason, _, why) = with_planner(|p| {
+        p.place_policy_quota(c, nodes, None, strategy, preferred_labels, node_count, None, &[], quota, quota_used)
+    })?;
+    Ok(assign.iter().zip(reason.iter().zip(why.iter()))
+        .map(|(&a, (&r, &w))| (if a == ffi::FP_NONE { None } else { Some(stage.servers[a as usize].clone()) }, r, w))
+        .collect())
 }
 
 /// What `fleet up --dry-run` prints for a stage (up.rs:57-136), planned in one call: the

@@ -32,6 +32,16 @@ process, and every call without a chain is held against the parent build: its me
 parent's maximum by at most the parent's own min-max range over the rounds (`within_margin`).  The
 calls with a chain have no target: their time, ns per placement and hop histogram are recorded.  Writes
 profiles/policy_fallback_timing.json.
+
+    python tools/policy_timing.py --quota [--rounds R] [--parent-tree DIR]
+
+The resource quota (SPEC.md 2.10) by the same method, per strategy: (a) the unconstrained call (`off`) and the
+fallback call (`fb_h2`) of this build against the same calls of the parent build's `--fallback-child` process,
+held to the same margin (`within_margin`): the kernels without a quota must not have moved; (b) `quota_unlimited`,
+fp_dev_place_batch_policy_quota over the fb_h2 chain with every cap FP_QUOTA_UNLIMITED, against this build's
+fb_h2: the price of the quota kernel itself (`vs_fb_h2`, the ratio of the medians); (c) `quota_half`, the same call
+with each scenario's caps at half of what its fb_h2 plan uses, where the refused containers skip the argmin.  (b)
+and (c) have no target.  Writes profiles/policy_quota_timing.json.
 """
 import argparse
 import json
@@ -159,6 +169,103 @@ def fallback_round(a):
     return out
 
 
+QUOTA_CHAIN = "fb_h2"
+
+
+def quota_round(a):
+    """One process's figures: per strategy the unconstrained call, the fallback call, and the quota call over the
+    same chain with every cap unlimited and with caps at half of each scenario's usage under the fallback call."""
+    S, C, N = a.scenarios, a.containers, a.nodes
+    dev = torch.device("cuda", 0)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    rounds = -(-S // cus) if N > 64 else None
+    out = {}
+    with Planner(0) as p:
+        db = DevBatch.allocate(S, C, N, dev)
+        p.dev_gen_batch(SEED4, db, 7)
+        p.sync()
+        snap = db.node_snapshot()
+        hops = torch.zeros(S * C, dtype=torch.uint8, device=dev)
+        why = torch.zeros(S * C, dtype=torch.uint8, device=dev)
+        masks = FALLBACK_CHAINS[QUOTA_CHAIN]
+        relax = torch.tensor((masks + [0] * (_lib.FP_FALLBACK_MAX_HOPS - len(masks))) * S, dtype=torch.int32, device=dev)
+        nh = torch.full((S,), len(masks), dtype=torch.int32, device=dev)
+        unlimited = torch.full((S * _lib.QUOTA_DIMS,), -1, dtype=torch.int32, device=dev)
+        for name, sid in STRATEGIES:
+            st = torch.full((S,), sid, dtype=torch.int32, device=dev)
+            half = unlimited.clone()  # filled in after the fallback call, from its plan
+
+            def fallback():
+                p.dev_place_batch_policy_fallback(db, st, relax_mask_t=relax, n_hops_t=nh, hops_t=hops)
+
+            def quota(caps):
+                p.dev_place_batch_policy_quota(db, st, caps, relax_mask_t=relax, n_hops_t=nh, hops_t=hops, quota_why_t=why)
+            calls = [("off", lambda: p.dev_place_batch_policy(db, st)), (QUOTA_CHAIN, fallback),
+                     ("quota_unlimited", lambda: quota(unlimited)), ("quota_half", lambda: quota(half))]
+            out[name] = {}
+            for label, call in calls:
+                wall, place_ms, sort_ms = timed(p, db, snap, call, a.steps, a.warmup)
+                reason = db.reason
+                rec = {"ms_per_call": wall, "place_kernel_ms": place_ms, "sort_ms": sort_ms,
+                       "rejected": int((reason != 0).sum().item()),
+                       "quota": int((reason == _lib.REASON_QUOTA).sum().item())}
+                if rounds:
+                    rec["ns_per_placement"] = 1e6 * place_ms / (rounds * C)
+                if label == QUOTA_CHAIN:  # each scenario's usage under this plan: cpu, memory, services
+                    placed = (db.assign.view(S, C) != -1).long()
+                    use = torch.stack([(db.cpu.view(S, C).long() * placed).sum(1), (db.mem.view(S, C).long() * placed).sum(1),
+                                       placed.sum(1)], 1)
+                    half.copy_((use // 2).to(torch.int32).reshape(-1))  # below 2^31 on this shape
+                out[name][label] = rec
+    return out
+
+
+def quota_main(a):
+    """The driver: starts every round as a child process and makes no GPU call itself."""
+    shape = ["--scenarios", str(a.scenarios), "--containers", str(a.containers), "--nodes", str(a.nodes), "--steps", str(a.steps),
+             "--warmup", str(a.warmup)]
+    new_rounds, parent_rounds = [], []
+    with tempfile.TemporaryDirectory() as tmp:
+        for r in range(a.rounds):
+            if a.parent_tree:
+                path = os.path.join(tmp, f"parent{r}.json")
+                tool = os.path.join(os.path.abspath(a.parent_tree), "tools", "policy_timing.py")
+                parent_rounds.append(_child([sys.executable, tool, *shape, "--fallback-child", "--out", path],
+                                            os.path.abspath(a.parent_tree), path))
+            path = os.path.join(tmp, f"new{r}.json")
+            new_rounds.append(_child([sys.executable, os.path.abspath(__file__), *shape, "--quota-child", "--out", path], ROOT, path))
+    held = ["off", QUOTA_CHAIN]
+    out = {"shape": {"scenarios": a.scenarios, "containers": a.containers, "nodes": a.nodes, "flags": 7, "seed": SEED4},
+           "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds,
+           "chain": {QUOTA_CHAIN: [hex(m) for m in FALLBACK_CHAINS[QUOTA_CHAIN]]},
+           "caps": {"quota_unlimited": "FP_QUOTA_UNLIMITED in every dimension",
+                    "quota_half": "per scenario, half of the cpu, memory and services its fb_h2 plan uses"},
+           "order": "each round: the parent build's process, then this build's",
+           "margin": "a call without a quota: this build's median <= the parent's max + (the parent's max - min)",
+           "strategies": {}}
+    for name, _ in STRATEGIES:
+        rec = {}
+        for label in held + ["quota_unlimited", "quota_half"]:
+            runs = [r[name][label] for r in new_rounds]
+            rec[label] = {"place_kernel_ms": _stats([x["place_kernel_ms"] for x in runs]),
+                          "ms_per_call": _stats([x["ms_per_call"] for x in runs]),
+                          "place_kernel_ms_rounds": [x["place_kernel_ms"] for x in runs],
+                          "rejected": runs[0]["rejected"], "quota": runs[0]["quota"]}
+            if "ns_per_placement" in runs[0]:
+                rec[label]["ns_per_placement"] = _stats([x["ns_per_placement"] for x in runs])
+        for label in ("quota_unlimited", "quota_half"):
+            rec[label]["vs_" + QUOTA_CHAIN] = rec[label]["place_kernel_ms"]["median"] / rec[QUOTA_CHAIN]["place_kernel_ms"]["median"]
+        for label in held if parent_rounds else []:
+            runs = [r[name][label] for r in parent_rounds]
+            st = _stats([x["place_kernel_ms"] for x in runs])
+            rec["parent_" + label] = {"place_kernel_ms": st, "ms_per_call": _stats([x["ms_per_call"] for x in runs]),
+                                      "place_kernel_ms_rounds": [x["place_kernel_ms"] for x in runs],
+                                      "rejected": runs[0]["rejected"]}
+            rec[label]["within_margin"] = rec[label]["place_kernel_ms"]["median"] <= st["max"] + (st["max"] - st["min"])
+        out["strategies"][name] = rec
+    return out
+
+
 def fallback_main(a):
     """The driver: starts every round as a child process and makes no GPU call itself."""
     shape = ["--scenarios", str(a.scenarios), "--containers", str(a.containers), "--nodes", str(a.nodes), "--steps", str(a.steps),
@@ -258,18 +365,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--spread", action="store_true", help="the topology spread on and off (see above)")
-    ap.add_argument("--rounds", type=int, default=3, help="--spread, --fallback: processes per build")
+    ap.add_argument("--rounds", type=int, default=3, help="--spread, --fallback, --quota: processes per build")
     ap.add_argument("--parent-tree", default=None,
-                    help="--spread, --fallback: a built checkout of the commit to compare with")
+                    help="--spread, --fallback, --quota: a built checkout of the commit to compare with")
     ap.add_argument("--spread-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--fallback", action="store_true", help="the fallback chain on and off (see above)")
     ap.add_argument("--fallback-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--quota", action="store_true", help="the resource quota on and off (see above)")
+    ap.add_argument("--quota-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "policy_fallback_timing.json" if a.fallback else
+        a.out = os.path.join(ROOT, "profiles", "policy_quota_timing.json" if a.quota else
+                             "policy_fallback_timing.json" if a.fallback else
                              "policy_spread_timing.json" if a.spread else "policy_timing.json")
-    if a.spread or a.spread_child or a.fallback or a.fallback_child:
+    if a.spread or a.spread_child or a.fallback or a.fallback_child or a.quota or a.quota_child:
         out = (spread_round(a) if a.spread_child else fallback_round(a) if a.fallback_child else
+               quota_round(a) if a.quota_child else quota_main(a) if a.quota else
                fallback_main(a) if a.fallback else spread_main(a))
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
