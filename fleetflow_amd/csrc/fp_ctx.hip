@@ -128,9 +128,14 @@ int fp_dev_done(fp_ctx *c, int rc) {
 // ---- arenas ----------------------------------------------------------------
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-void fp_ws_reset(fp_ctx *c) { c->ws_top = 0; }
+// c->last_rng points into the arena: whoever recycles or frees it forgets the pointer
+void fp_ws_reset(fp_ctx *c) {
+    c->ws_top = 0;
+    c->last_rng = nullptr;
+}
 int fp_ws_reserve(fp_ctx *c, size_t bytes) {
     if (bytes <= c->ws_cap) return FP_OK;
+    c->last_rng = nullptr;
     FP_HIP(hipStreamSynchronize(c->stream));
     if (c->ws) (void)hipFree(c->ws);
     c->ws = nullptr;
@@ -289,18 +294,22 @@ struct OutCopy {
     const void *d;
     size_t bytes;
 };
+// a pinned host buffer of at least `need` bytes: grown with headroom, the old content dropped
+static int grow_pinned(char **buf, size_t *cap, size_t need) {
+    if (need <= *cap) return FP_OK;
+    if (*buf) (void)hipHostFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const size_t grown = align256(need + need / 4 + 4096);
+    FP_HIP(hipHostMalloc(buf, grown, hipHostMallocDefault));
+    *cap = grown;
+    return FP_OK;
+}
 static int copy_back_all(fp_ctx *c, const OutCopy *o, int n) {
     size_t total = 0;
     for (int i = 0; i < n; ++i)
         if (o[i].h && o[i].bytes) total += align256(o[i].bytes);
-    if (total > c->h_stage_cap) {
-        if (c->h_stage) (void)hipHostFree(c->h_stage);
-        c->h_stage = nullptr;
-        c->h_stage_cap = 0;
-        const size_t cap = align256(total + total / 4 + 4096);
-        FP_HIP(hipHostMalloc(&c->h_stage, cap, hipHostMallocDefault));
-        c->h_stage_cap = cap;
-    }
+    if (int rc = grow_pinned(&c->h_stage, &c->h_stage_cap, total)) return rc;
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         if (!o[i].h || !o[i].bytes) continue;
@@ -337,14 +346,7 @@ static int stage_in_packed(fp_ctx *c, const InCopy *in, int n) {
         return FP_OK;
     }
     if (c->h_in_ev) FP_HIP(hipEventSynchronize(c->h_in_ev));  // the previous copy out of h_in is done
-    if (total > c->h_in_cap) {
-        if (c->h_in) (void)hipHostFree(c->h_in);
-        c->h_in = nullptr;
-        c->h_in_cap = 0;
-        const size_t cap = align256(total + total / 4 + 4096);
-        FP_HIP(hipHostMalloc(&c->h_in, cap, hipHostMallocDefault));
-        c->h_in_cap = cap;
-    }
+    if (int rc = grow_pinned(&c->h_in, &c->h_in_cap, total)) return rc;
     if (!c->h_in_ev) FP_HIP(hipEventCreateWithFlags(&c->h_in_ev, hipEventDisableTiming));
     char *d = (char *)fp_stage_take(c, total);
     if (!d) return FP_ENOMEM;
@@ -375,14 +377,7 @@ static int copy_back_span(fp_ctx *c, const OutCopy *o, int n) {
     if (!lo) lo = (const char *)slot;
     if ((const char *)slot < hi) return FP_EINVAL;  // not the layout this helper assumes
     const size_t span = (size_t)((const char *)slot + 4 - lo);
-    if (span > c->h_stage_cap) {
-        if (c->h_stage) (void)hipHostFree(c->h_stage);
-        c->h_stage = nullptr;
-        c->h_stage_cap = 0;
-        const size_t cap = align256(span + span / 4 + 4096);
-        FP_HIP(hipHostMalloc(&c->h_stage, cap, hipHostMallocDefault));
-        c->h_stage_cap = cap;
-    }
+    if (int rc = grow_pinned(&c->h_stage, &c->h_stage_cap, span)) return rc;
     FP_HIP(hipMemcpyAsync(slot, c->d_err, 4, hipMemcpyDeviceToDevice, c->stream));
     FP_HIP(hipMemcpyAsync(c->h_stage, lo, span, hipMemcpyDeviceToHost, c->stream));
     FP_HIP(hipStreamSynchronize(c->stream));
@@ -457,42 +452,105 @@ extern "C" int fp_levelize(fp_ctx *c, const fp_graph *g, uint32_t *level_out, ui
     return copy_back_span(c, o, 3);
 }
 
+// ---- placement: fp_place*, fp_place*_policy* --------------------------------------
+static bool batch_has_tables(const fp_batch *b) {
+    if (b->n_scen && b->n_containers &&
+        (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign || !b->reason))
+        return false;
+    if (b->n_scen && b->n_nodes &&
+        (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable))
+        return false;
+    return true;
+}
+
+// one scenario's tables as a batch of one (no cost)
+static fp_batch single_batch(const fp_containers *cs, const fp_nodes *ns, const uint32_t *level, uint32_t *assign_out,
+                             uint8_t *reason_out) {
+    fp_batch b = {};
+    b.n_scen = 1;
+    b.n_containers = cs->n;
+    b.n_nodes = ns->n;
+    b.cpu_m = cs->cpu_m;
+    b.mem_mib = cs->mem_mib;
+    b.req_labels = cs->req_labels;
+    b.conflict = cs->conflict;
+    b.level = level;
+    b.cpu_free = ns->cpu_free;
+    b.mem_free = ns->mem_free;
+    b.labels = ns->labels;
+    b.conflict_used = ns->conflict_used;
+    b.schedulable = ns->schedulable;
+    b.assign = assign_out;
+    b.reason = reason_out;
+    return b;
+}
+
+// The device copy of a host batch: its ten input arrays, then (scored placement: `o` and `dopt` non-null)
+// the policy inputs, then assign / reason / cost and the policy outputs the caller asked for.  The order
+// of the takes is the layout of the staging arena and the order of the copies.
+static fp_batch stage_batch(fp_ctx *c, const fp_batch *b, const fp_policy_opts *o, fp_policy_opts *dopt, int *rc) {
+    const size_t S = b->n_scen, SC = S * b->n_containers, SN = S * b->n_nodes;
+    fp_batch d = *b;
+    d.cpu_m = stage_in(c, b->cpu_m, SC, rc);
+    d.mem_mib = stage_in(c, b->mem_mib, SC, rc);
+    d.req_labels = stage_in(c, b->req_labels, SC, rc);
+    d.conflict = stage_in(c, b->conflict, SC, rc);
+    d.level = b->level ? stage_in(c, b->level, SC, rc) : nullptr;
+    d.cpu_free = stage_in(c, b->cpu_free, SN, rc);
+    d.mem_free = stage_in(c, b->mem_free, SN, rc);
+    d.labels = stage_in(c, b->labels, SN, rc);
+    d.conflict_used = stage_in(c, b->conflict_used, SN, rc);
+    d.schedulable = stage_in(c, b->schedulable, SN, rc);
+    if (o) {
+        dopt->strategy = stage_in(c, o->strategy, S, rc);
+        dopt->preferred = stage_in(c, o->preferred, S, rc);
+        dopt->node_count = stage_in(c, o->node_count, SN, rc);
+        dopt->domain = stage_in(c, o->domain, SN, rc);
+        dopt->max_skew = stage_in(c, o->max_skew, S, rc);
+        dopt->relax_mask = stage_in(c, o->relax_mask, S * FP_FALLBACK_MAX_HOPS, rc);
+        dopt->n_hops = stage_in(c, o->n_hops, S, rc);
+        dopt->quota = stage_in(c, o->quota, S * FP_QUOTA_DIMS, rc);
+        dopt->quota_used = stage_in(c, o->quota_used, S * FP_QUOTA_DIMS, rc);
+    }
+    d.assign = stage_out<uint32_t>(c, SC, rc);
+    d.reason = stage_out<uint8_t>(c, SC, rc);
+    d.cost = stage_out<uint64_t>(c, S, rc);
+    if (o) {
+        dopt->hops = o->hops ? stage_out<uint8_t>(c, SC, rc) : nullptr;
+        dopt->quota_why = o->quota_why ? stage_out<uint8_t>(c, SC, rc) : nullptr;
+    }
+    return d;
+}
+
+// the plan and the updated node state of staged batch `d` into the caller's `b`, with the policy outputs
+static int batch_copy_back(fp_ctx *c, const fp_batch *b, const fp_batch &d, const fp_policy_opts *o,
+                           const fp_policy_opts *dopt) {
+    const size_t S = b->n_scen, SC = S * b->n_containers, SN = S * b->n_nodes;
+    OutCopy out[10] = {{b->assign, d.assign, SC * 4},    {b->reason, d.reason, SC},
+                       {b->cost, d.cost, S * 8},         {b->cpu_free, d.cpu_free, SN * 4},
+                       {b->mem_free, d.mem_free, SN * 4}, {b->conflict_used, d.conflict_used, SN * 4}};
+    if (!o) return copy_back_all(c, out, 6);
+    out[6] = {o->node_count, dopt->node_count, SN * 4};
+    out[7] = {o->hops, dopt->hops, SC};
+    out[8] = {o->quota_used, dopt->quota_used, S * FP_QUOTA_DIMS * 4};
+    out[9] = {o->quota_why, dopt->quota_why, SC};
+    return copy_back_all(c, out, 10);
+}
+
 static int batch_host(fp_ctx *c, const fp_batch *b) {
-    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
-    const size_t SC = S * C, SN = S * N;
-    if (S && C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign ||
-                   !b->reason))
-        return FP_EINVAL;
-    if (S && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used ||
-                   !b->schedulable))
-        return FP_EINVAL;
+    const size_t S = b->n_scen, SC = S * b->n_containers, SN = S * b->n_nodes;
+    if (!batch_has_tables(b)) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
     int rc = fp_stage_reserve(c, SC * (4 * 6 + 1) + SN * (4 * 4 + 1) + S * 8 + 16 * 256);
     if (rc) return rc;
     fp_stage_reset(c);
-    fp_batch d = *b;
-    d.cpu_m = stage_in(c, b->cpu_m, SC, &rc);
-    d.mem_mib = stage_in(c, b->mem_mib, SC, &rc);
-    d.req_labels = stage_in(c, b->req_labels, SC, &rc);
-    d.conflict = stage_in(c, b->conflict, SC, &rc);
-    d.level = b->level ? stage_in(c, b->level, SC, &rc) : nullptr;
-    d.cpu_free = stage_in(c, b->cpu_free, SN, &rc);
-    d.mem_free = stage_in(c, b->mem_free, SN, &rc);
-    d.labels = stage_in(c, b->labels, SN, &rc);
-    d.conflict_used = stage_in(c, b->conflict_used, SN, &rc);
-    d.schedulable = stage_in(c, b->schedulable, SN, &rc);
-    d.assign = stage_out<uint32_t>(c, SC, &rc);
-    d.reason = stage_out<uint8_t>(c, SC, &rc);
-    d.cost = stage_out<uint64_t>(c, S, &rc);
+    const fp_batch d = stage_batch(c, b, nullptr, nullptr, &rc);
     if (rc) return rc;
     rc = fp_dev_place_batch_impl(c, &d);
     if (rc) return rc;
-    const OutCopy o[] = {{b->assign, d.assign, SC * 4},          {b->reason, d.reason, SC},
-                         {b->cost, d.cost, S * 8},                {b->cpu_free, d.cpu_free, SN * 4},
-                         {b->mem_free, d.mem_free, SN * 4},       {b->conflict_used, d.conflict_used, SN * 4}};
-    return copy_back_all(c, o, 6);
+    return batch_copy_back(c, b, d, nullptr, nullptr);
 }
 
 extern "C" int fp_place_batch(fp_ctx *c, const fp_batch *b) {
@@ -503,25 +561,7 @@ extern "C" int fp_place_batch(fp_ctx *c, const fp_batch *b) {
 extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
                         uint32_t *assign_out, uint8_t *reason_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
-    fp_batch b;
-    memset(&b, 0, sizeof(b));
-    b.n_scen = 1;
-    b.scen_base = 0;
-    b.n_containers = cs->n;
-    b.n_nodes = ns->n;
-    b.cpu_m = cs->cpu_m;
-    b.mem_mib = cs->mem_mib;
-    b.req_labels = cs->req_labels;
-    b.conflict = cs->conflict;
-    b.level = level;
-    b.cpu_free = ns->cpu_free;
-    b.mem_free = ns->mem_free;
-    b.labels = ns->labels;
-    b.conflict_used = ns->conflict_used;
-    b.schedulable = ns->schedulable;
-    b.assign = assign_out;
-    b.reason = reason_out;
-    b.cost = nullptr;
+    const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
     return batch_host(c, &b);
 }
 
@@ -531,35 +571,27 @@ extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const 
 // domain / max_skew (SPEC.md 2.7; either null = no constraint) are host memory too: a domain id out of
 // range in a constrained scenario is refused here as well.
 // relax_mask / n_hops (SPEC.md 2.8; either null = no fallback) likewise: an n_hops above
-// FP_FALLBACK_MAX_HOPS is refused here.  hops_out (nullable) receives the winners' hops.
-// quota (SPEC.md 2.10; null = no quota, and then quota_used and quota_why_out are not touched) has no
-// illegal value.  quota_used (nullable) goes in and comes back; quota_why_out (nullable) comes back.
-static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                             uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
-                             const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out,
-                             const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why_out) {
+// FP_FALLBACK_MAX_HOPS is refused here.  hops (nullable) receives the winners' hops.
+// quota (SPEC.md 2.10; null = no quota, and then quota_used and quota_why are not touched) has no
+// illegal value.  quota_used (nullable) goes in and comes back; quota_why (nullable) comes back.
+static int batch_policy_host(fp_ctx *c, const fp_batch *b, fp_policy_opts o) {
     const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
     const size_t SC = S * C, SN = S * N;
-    if (S && !strategy) return FP_EINVAL;
+    if (S && !o.strategy) return FP_EINVAL;
     for (size_t s = 0; s < S; ++s)
-        if (strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
-    if (!domain || !max_skew) domain = max_skew = nullptr;
-    for (size_t s = 0; max_skew && s < S; ++s) {
-        if (max_skew[s] == 0u) continue;
+        if (o.strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (!o.domain || !o.max_skew) o.domain = o.max_skew = nullptr;
+    for (size_t s = 0; o.max_skew && s < S; ++s) {
+        if (o.max_skew[s] == 0u) continue;
         for (size_t n = 0; n < N; ++n)
-            if (domain[s * N + n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
+            if (o.domain[s * N + n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
     }
-    if (!relax_mask || !n_hops) relax_mask = n_hops = nullptr;
-    for (size_t s = 0; n_hops && s < S; ++s)
-        if (n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
-    if (!quota) quota_used = nullptr, quota_why_out = nullptr;
+    if (!o.relax_mask || !o.n_hops) o.relax_mask = o.n_hops = nullptr;
+    for (size_t s = 0; o.n_hops && s < S; ++s)
+        if (o.n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (!o.quota) o.quota_used = nullptr, o.quota_why = nullptr;
     if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
-    if (S && C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign ||
-                   !b->reason))
-        return FP_EINVAL;
-    if (S && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used ||
-                   !b->schedulable))
-        return FP_EINVAL;
+    if (!batch_has_tables(b)) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
@@ -567,41 +599,48 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *strat
                                      S * (8 + 4 + 4 + 4 + 4 * FP_FALLBACK_MAX_HOPS + 4 + 2 * 4 * FP_QUOTA_DIMS) + 28 * 256);
     if (rc) return rc;
     fp_stage_reset(c);
-    fp_batch d = *b;
-    d.cpu_m = stage_in(c, b->cpu_m, SC, &rc);
-    d.mem_mib = stage_in(c, b->mem_mib, SC, &rc);
-    d.req_labels = stage_in(c, b->req_labels, SC, &rc);
-    d.conflict = stage_in(c, b->conflict, SC, &rc);
-    d.level = b->level ? stage_in(c, b->level, SC, &rc) : nullptr;
-    d.cpu_free = stage_in(c, b->cpu_free, SN, &rc);
-    d.mem_free = stage_in(c, b->mem_free, SN, &rc);
-    d.labels = stage_in(c, b->labels, SN, &rc);
-    d.conflict_used = stage_in(c, b->conflict_used, SN, &rc);
-    d.schedulable = stage_in(c, b->schedulable, SN, &rc);
-    const uint32_t *dstrat = stage_in(c, strategy, S, &rc);
-    const uint32_t *dpref = stage_in(c, preferred, S, &rc);
-    uint32_t *dcount = stage_in(c, node_count, SN, &rc);
-    const uint32_t *ddom = stage_in(c, domain, SN, &rc);
-    const uint32_t *dskew = stage_in(c, max_skew, S, &rc);
-    const uint32_t *drelax = stage_in(c, relax_mask, S * FP_FALLBACK_MAX_HOPS, &rc);
-    const uint32_t *dhops_n = stage_in(c, n_hops, S, &rc);
-    const uint32_t *dquota = stage_in(c, quota, S * FP_QUOTA_DIMS, &rc);
-    uint32_t *dqused = stage_in(c, quota_used, S * FP_QUOTA_DIMS, &rc);
-    d.assign = stage_out<uint32_t>(c, SC, &rc);
-    d.reason = stage_out<uint8_t>(c, SC, &rc);
-    d.cost = stage_out<uint64_t>(c, S, &rc);
-    uint8_t *dhops = hops_out ? stage_out<uint8_t>(c, SC, &rc) : nullptr;
-    uint8_t *dqwhy = quota_why_out ? stage_out<uint8_t>(c, SC, &rc) : nullptr;
+    fp_policy_opts dopt;
+    const fp_batch d = stage_batch(c, b, &o, &dopt, &rc);
     if (rc) return rc;
-    rc = fp_dev_place_batch_policy_impl(c, &d, dstrat, dpref, dcount, ddom, dskew, drelax, dhops_n, dhops, dquota,
-                                        dqused, dqwhy);
+    rc = fp_dev_place_batch_policy_impl(c, &d, dopt);
     if (rc) return rc;
-    const OutCopy o[] = {{b->assign, d.assign, SC * 4},          {b->reason, d.reason, SC},
-                         {b->cost, d.cost, S * 8},                {b->cpu_free, d.cpu_free, SN * 4},
-                         {b->mem_free, d.mem_free, SN * 4},       {b->conflict_used, d.conflict_used, SN * 4},
-                         {node_count, dcount, SN * 4},             {hops_out, dhops, SC},
-                         {quota_used, dqused, S * FP_QUOTA_DIMS * 4}, {quota_why_out, dqwhy, SC}};
-    return copy_back_all(c, o, 10);
+    return batch_copy_back(c, b, d, &o, &dopt);
+}
+
+// The twelve exports set the fields their signature has.  A single-scenario export points the per-scenario
+// words at its scalar arguments; one that has no domain (or no relax_mask) leaves both of the pair null.
+static fp_policy_opts policy_opts(const uint32_t *strategy, const uint32_t *preferred, uint32_t *node_count) {
+    fp_policy_opts o;
+    o.strategy = strategy;
+    o.preferred = preferred;
+    o.node_count = node_count;
+    return o;
+}
+
+extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                     const uint32_t *preferred_labels, uint32_t *node_count) {
+    if (!c || !b) return FP_EINVAL;
+    return batch_policy_host(c, b, policy_opts(strategy, preferred_labels, node_count));
+}
+
+extern "C" int fp_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                            const uint32_t *preferred_labels, uint32_t *node_count,
+                                            const uint32_t *domain, const uint32_t *max_skew) {
+    if (!c || !b) return FP_EINVAL;
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    return batch_policy_host(c, b, o);
+}
+
+extern "C" int fp_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
+                                              const uint32_t *preferred_labels, uint32_t *node_count,
+                                              const uint32_t *domain, const uint32_t *max_skew,
+                                              const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
+    if (!c || !b) return FP_EINVAL;
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    o.relax_mask = relax_mask; o.n_hops = n_hops; o.hops = hops_out;
+    return batch_policy_host(c, b, o);
 }
 
 extern "C" int fp_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
@@ -610,28 +649,42 @@ extern "C" int fp_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, const u
                                            const uint32_t *n_hops, uint8_t *hops_out, const uint32_t *quota,
                                            uint32_t *quota_used, uint8_t *quota_why_out) {
     if (!c || !b) return FP_EINVAL;
-    return batch_policy_host(c, b, strategy, preferred_labels, node_count, domain, max_skew, relax_mask, n_hops, hops_out,
-                             quota, quota_used, quota_why_out);
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    o.relax_mask = relax_mask; o.n_hops = n_hops; o.hops = hops_out;
+    o.quota = quota; o.quota_used = quota_used; o.quota_why = quota_why_out;
+    return batch_policy_host(c, b, o);
 }
 
-extern "C" int fp_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
-                                              const uint32_t *preferred_labels, uint32_t *node_count,
-                                              const uint32_t *domain, const uint32_t *max_skew,
-                                              const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
-    return fp_place_batch_policy_quota(c, b, strategy, preferred_labels, node_count, domain, max_skew, relax_mask, n_hops,
-                                       hops_out, nullptr, nullptr, nullptr);
+extern "C" int fp_place_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                               uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                               uint32_t *assign_out, uint8_t *reason_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
+    return batch_policy_host(c, &b, policy_opts(&strategy, &preferred_labels, node_count));
 }
 
-extern "C" int fp_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
-                                            const uint32_t *preferred_labels, uint32_t *node_count,
-                                            const uint32_t *domain, const uint32_t *max_skew) {
-    return fp_place_batch_policy_fallback(c, b, strategy, preferred_labels, node_count, domain, max_skew, nullptr, nullptr,
-                                          nullptr);
+extern "C" int fp_place_policy_spread(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                      uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                      const uint32_t *domain, uint32_t max_skew, uint32_t *assign_out,
+                                      uint8_t *reason_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
+    fp_policy_opts o = policy_opts(&strategy, &preferred_labels, node_count);
+    o.domain = domain; o.max_skew = &max_skew;
+    return batch_policy_host(c, &b, o);
 }
 
-extern "C" int fp_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
-                                     const uint32_t *preferred_labels, uint32_t *node_count) {
-    return fp_place_batch_policy_spread(c, b, strategy, preferred_labels, node_count, nullptr, nullptr);
+extern "C" int fp_place_policy_fallback(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                        uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                        const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
+                                        uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
+    fp_policy_opts o = policy_opts(&strategy, &preferred_labels, node_count);
+    o.domain = domain; o.max_skew = &max_skew;
+    o.relax_mask = relax_mask; o.n_hops = &n_hops; o.hops = hops_out;
+    return batch_policy_host(c, &b, o);
 }
 
 extern "C" int fp_place_policy_quota(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
@@ -640,75 +693,41 @@ extern "C" int fp_place_policy_quota(fp_ctx *c, const fp_containers *cs, fp_node
                                      uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
                                      const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
-    fp_batch b;
-    memset(&b, 0, sizeof(b));
-    b.n_scen = 1;
-    b.n_containers = cs->n;
-    b.n_nodes = ns->n;
-    b.cpu_m = cs->cpu_m;
-    b.mem_mib = cs->mem_mib;
-    b.req_labels = cs->req_labels;
-    b.conflict = cs->conflict;
-    b.level = level;
-    b.cpu_free = ns->cpu_free;
-    b.mem_free = ns->mem_free;
-    b.labels = ns->labels;
-    b.conflict_used = ns->conflict_used;
-    b.schedulable = ns->schedulable;
-    b.assign = assign_out;
-    b.reason = reason_out;
-    return batch_policy_host(c, &b, &strategy, &preferred_labels, node_count, domain, &max_skew, relax_mask, &n_hops,
-                             hops_out, quota, quota_used, quota_why_out);
+    const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
+    fp_policy_opts o = policy_opts(&strategy, &preferred_labels, node_count);
+    o.domain = domain; o.max_skew = &max_skew;
+    o.relax_mask = relax_mask; o.n_hops = &n_hops; o.hops = hops_out;
+    o.quota = quota; o.quota_used = quota_used; o.quota_why = quota_why_out;
+    return batch_policy_host(c, &b, o);
 }
 
-extern "C" int fp_place_policy_fallback(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
-                                        uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
-                                        const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
-                                        uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out) {
-    return fp_place_policy_quota(c, cs, ns, level, strategy, preferred_labels, node_count, domain, max_skew, relax_mask,
-                                 n_hops, assign_out, reason_out, hops_out, nullptr, nullptr, nullptr);
-}
-
-extern "C" int fp_place_policy_spread(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
-                                      uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
-                                      const uint32_t *domain, uint32_t max_skew, uint32_t *assign_out,
-                                      uint8_t *reason_out) {
-    return fp_place_policy_fallback(c, cs, ns, level, strategy, preferred_labels, node_count, domain, max_skew, nullptr, 0u,
-                                    assign_out, reason_out, nullptr);
-}
-
-extern "C" int fp_place_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
-                               uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
-                               uint32_t *assign_out, uint8_t *reason_out) {
-    return fp_place_policy_spread(c, cs, ns, level, strategy, preferred_labels, node_count, nullptr, 0u, assign_out,
-                                  reason_out);
+static int dev_policy(fp_ctx *c, const fp_batch *b, const fp_policy_opts &o) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, o));
 }
 
 extern "C" int fp_dev_place_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
                                          const uint32_t *preferred_labels, uint32_t *node_count) {
-    if (!c || !b) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, nullptr, nullptr,
-                                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    return dev_policy(c, b, policy_opts(strategy, preferred_labels, node_count));
 }
 
 extern "C" int fp_dev_place_batch_policy_spread(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
                                                 const uint32_t *preferred_labels, uint32_t *node_count,
                                                 const uint32_t *domain, const uint32_t *max_skew) {
-    if (!c || !b) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
-                                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    return dev_policy(c, b, o);
 }
 
 extern "C" int fp_dev_place_batch_policy_fallback(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
                                                   const uint32_t *preferred_labels, uint32_t *node_count,
                                                   const uint32_t *domain, const uint32_t *max_skew,
                                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out) {
-    if (!c || !b) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
-                                                         relax_mask, n_hops, hops_out, nullptr, nullptr, nullptr));
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    o.relax_mask = relax_mask; o.n_hops = n_hops; o.hops = hops_out;
+    return dev_policy(c, b, o);
 }
 
 extern "C" int fp_dev_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, const uint32_t *strategy,
@@ -716,10 +735,29 @@ extern "C" int fp_dev_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, con
                                                const uint32_t *domain, const uint32_t *max_skew,
                                                const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops_out,
                                                const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why_out) {
-    if (!c || !b) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    return fp_dev_done(c, fp_dev_place_batch_policy_impl(c, b, strategy, preferred_labels, node_count, domain, max_skew,
-                                                         relax_mask, n_hops, hops_out, quota, quota_used, quota_why_out));
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    o.relax_mask = relax_mask; o.n_hops = n_hops; o.hops = hops_out;
+    o.quota = quota; o.quota_used = quota_used; o.quota_why = quota_why_out;
+    return dev_policy(c, b, o);
+}
+
+// ---- feasibility and rejection diagnosis -----------------------------------------
+// the device copies of one scenario's container and node tables (nine arrays, in this order)
+static void stage_tables(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, fp_containers *dc, fp_nodes *dn,
+                         int *rc) {
+    const size_t C = cs->n, N = ns->n;
+    *dc = *cs;
+    *dn = *ns;
+    dc->cpu_m = stage_in(c, cs->cpu_m, C, rc);
+    dc->mem_mib = stage_in(c, cs->mem_mib, C, rc);
+    dc->req_labels = stage_in(c, cs->req_labels, C, rc);
+    dc->conflict = stage_in(c, cs->conflict, C, rc);
+    dn->cpu_free = stage_in(c, ns->cpu_free, N, rc);
+    dn->mem_free = stage_in(c, ns->mem_free, N, rc);
+    dn->labels = stage_in(c, ns->labels, N, rc);
+    dn->conflict_used = stage_in(c, ns->conflict_used, N, rc);
+    dn->schedulable = stage_in(c, ns->schedulable, N, rc);
 }
 
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,
@@ -738,17 +776,9 @@ extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes
     int rc = fp_stage_reserve(c, C * 24 + N * 17 + (bitmap_out ? WC * N * 8 : 0) + 16 * 256);
     if (rc) return rc;
     fp_stage_reset(c);
-    fp_containers dc = *cs;
-    fp_nodes dn = *ns;
-    dc.cpu_m = stage_in(c, cs->cpu_m, C, &rc);
-    dc.mem_mib = stage_in(c, cs->mem_mib, C, &rc);
-    dc.req_labels = stage_in(c, cs->req_labels, C, &rc);
-    dc.conflict = stage_in(c, cs->conflict, C, &rc);
-    dn.cpu_free = stage_in(c, ns->cpu_free, N, &rc);
-    dn.mem_free = stage_in(c, ns->mem_free, N, &rc);
-    dn.labels = stage_in(c, ns->labels, N, &rc);
-    dn.conflict_used = stage_in(c, ns->conflict_used, N, &rc);
-    dn.schedulable = stage_in(c, ns->schedulable, N, &rc);
+    fp_containers dc;
+    fp_nodes dn;
+    stage_tables(c, cs, ns, &dc, &dn, &rc);
     uint32_t *dfirst = stage_out<uint32_t>(c, C, &rc);
     uint32_t *dcount = stage_out<uint32_t>(c, C, &rc);
     uint64_t *dbits = bitmap_out ? stage_out<uint64_t>(c, WC * N, &rc) : nullptr;
@@ -759,7 +789,7 @@ extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes
     return copy_back_all(c, o, 3);
 }
 
-// ---- rejection diagnosis (SPEC.md 2.9, fp_explain.hip) ---------------------------
+// rejection diagnosis (SPEC.md 2.9, fp_explain.hip)
 extern "C" int fp_dev_explain(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *sel,
                               uint32_t n_sel, uint32_t ignore_labels, uint32_t *rows_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
@@ -792,17 +822,9 @@ extern "C" int fp_explain(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns
     int rc = fp_stage_reserve(c, C * 16 + N * 17 + M * (4 + FP_EXPLAIN_WORDS * 4) + 16 * 256);
     if (rc) return rc;
     fp_stage_reset(c);
-    fp_containers dc = *cs;
-    fp_nodes dn = *ns;
-    dc.cpu_m = stage_in(c, cs->cpu_m, C, &rc);
-    dc.mem_mib = stage_in(c, cs->mem_mib, C, &rc);
-    dc.req_labels = stage_in(c, cs->req_labels, C, &rc);
-    dc.conflict = stage_in(c, cs->conflict, C, &rc);
-    dn.cpu_free = stage_in(c, ns->cpu_free, N, &rc);
-    dn.mem_free = stage_in(c, ns->mem_free, N, &rc);
-    dn.labels = stage_in(c, ns->labels, N, &rc);
-    dn.conflict_used = stage_in(c, ns->conflict_used, N, &rc);
-    dn.schedulable = stage_in(c, ns->schedulable, N, &rc);
+    fp_containers dc;
+    fp_nodes dn;
+    stage_tables(c, cs, ns, &dc, &dn, &rc);
     const uint32_t *dsel = stage_in(c, sel, M, &rc);
     uint32_t *drows = stage_out<uint32_t>(c, M * FP_EXPLAIN_WORDS, &rc);  // 256-byte aligned
     if (rc) return rc;

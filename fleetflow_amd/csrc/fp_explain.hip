@@ -281,8 +281,6 @@ int fp_dev_explain_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, 
     hipStream_t st = c->stream;
     uint32_t *bad = nullptr;
     if (sel) {
-        // the check word lives in the arena the last first-fit call's range words live in (fp_ctx_place_path)
-        c->last_rng = nullptr;
         if (int rc = fp_ws_reserve(c, 256)) return rc;
         fp_ws_reset(c);
         bad = (uint32_t *)fp_ws_take(c, 4);
@@ -338,7 +336,6 @@ int fp_dev_explain_batch_impl(fp_ctx *c, const fp_batch *b, uint32_t reason_mask
     // (4 bytes per container, split grids only) and one count per scenario
     uint32_t *list = nullptr, *cnt = nullptr, *dig = nullptr;
     if (reason_mask || split) {
-        c->last_rng = nullptr;  // this call resets the arena those words live in (fp_ctx_place_path)
         if (int rc = fp_ws_reserve(c, (reason_mask ? SC * 4 + (size_t)S * 4 : 0) + (split ? SC * 4 : 0) + 4 * 256))
             return rc;
         fp_ws_reset(c);

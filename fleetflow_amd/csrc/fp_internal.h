@@ -70,8 +70,9 @@ struct fp_ctx {
     // the asynchronous levelizer's work queues (fp_order.hip), kept between calls: a clean finish
     // leaves them empty, and the flag in their last 256 bytes tells the next call whether to refill
     void *lvl_q = nullptr;
-    // the last placement's range words (CN_ORC.. of its workspace: OR cpu, OR mem, kernel path),
-    // read by fp_ctx_place_path
+    // the last placement's range words (CN_ORC.. of its workspace: OR cpu, OR mem, kernel path), read by
+    // fp_ctx_place_path.  They live in the workspace arena: fp_ws_reset and fp_ws_reserve clear the
+    // pointer, so it is never read after another call reused or freed the arena
     uint32_t *last_rng = nullptr;
     size_t lvl_q_cap = 0;
     // profiling
@@ -84,7 +85,7 @@ struct fp_ctx {
 };
 
 // arena helpers (return nullptr on failure; callers map to FP_ENOMEM)
-void fp_ws_reset(fp_ctx *c);
+void fp_ws_reset(fp_ctx *c);                 // also forgets last_rng, which points into the arena
 int fp_ws_reserve(fp_ctx *c, size_t bytes);  // ensure capacity (may sync + realloc)
 void *fp_ws_take(fp_ctx *c, size_t bytes);   // 256-B aligned slice
 void fp_stage_reset(fp_ctx *c);
@@ -141,15 +142,25 @@ int fp_dev_explain_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, 
                         uint32_t ignore_labels, uint32_t *rows);
 int fp_dev_explain_batch_impl(fp_ctx *c, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
                               uint32_t *hist);
-// scored placement (fp_policy.hip, SPEC.md 2.6 and 2.7); every pointer is device memory.  domain [S][N]
-// and max_skew [S] are the topology spread of 2.7; either one null = no constraint.  relax_mask [S][4] and
-// n_hops [S] are the fallback chain of 2.8; either one null = no fallback.  hops [S][C] (nullable) receives
-// the winner's hop: all zero when the call has no chain.  quota [S][3] is the resource quota of 2.10, null =
-// no quota; quota_used [S][3] (in/out) and quota_why [S][C] are nullable and untouched without quota
-int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                                   uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
-                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops,
-                                   const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why);
+// scored placement (fp_policy.hip, SPEC.md 2.6 to 2.10): what a call has besides its batch.  Not ABI: the
+// exports of fp_ctx.hip fill in the fields their signature has.  Only strategy [S] is required.
+struct fp_policy_opts {
+    const uint32_t *strategy = nullptr, *preferred = nullptr;  // [S] each
+    uint32_t *node_count = nullptr;                            // [S][N], in/out
+    // topology spread (2.7): domain [S][N], max_skew [S]; either one null = no constraint
+    const uint32_t *domain = nullptr, *max_skew = nullptr;
+    // fallback chain (2.8): relax_mask [S][4], n_hops [S]; either one null = no fallback.  hops [S][C]
+    // receives the winner's hop: all zero when the call has no chain
+    const uint32_t *relax_mask = nullptr, *n_hops = nullptr;
+    uint8_t *hops = nullptr;
+    // resource quota (2.10): quota [S][3], null = no quota; quota_used [S][3] (in/out) and quota_why
+    // [S][C] are untouched without quota
+    const uint32_t *quota = nullptr;
+    uint32_t *quota_used = nullptr;
+    uint8_t *quota_why = nullptr;
+};
+// every pointer is device memory
+int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy_opts &o);
 
 // tile-pipeline FFD (fp_pipe.hip)
 bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint32_t *W_out, uint32_t *B_out,

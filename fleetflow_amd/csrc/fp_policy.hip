@@ -636,15 +636,11 @@ int policy_sort_tmp(hipStream_t st, uint32_t S, size_t SC, size_t *bytes) {
 
 }  // namespace
 
-int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *strategy, const uint32_t *preferred,
-                                   uint32_t *node_count, const uint32_t *domain, const uint32_t *max_skew,
-                                   const uint32_t *relax_mask, const uint32_t *n_hops, uint8_t *hops,
-                                   const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why) {
+int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy_opts &o) {
     const uint32_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
-    // this call resets the arena the last first-fit call's range words live in (fp_ctx_place_path)
-    c->last_rng = nullptr;
+    c->last_rng = nullptr;  // a placement call starts with nothing run (fp_ctx_place_path)
     if (S == 0) return FP_OK;
-    if (!strategy) return FP_EINVAL;
+    if (!o.strategy) return FP_EINVAL;
     if ((uint64_t)b->scen_base + S > 65536ull) return FP_EOVERFLOW;  // SPEC.md 2.4: 16-bit scenario id
     if (N > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
     const size_t SC = (size_t)S * C;
@@ -652,9 +648,9 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     if (C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign || !b->reason)) return FP_EINVAL;
     if (C && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable)) return FP_EINVAL;
     hipStream_t st = c->stream;
-    const bool sp = domain && max_skew;  // SPEC.md 2.7: either pointer null = no constraint anywhere
-    const bool fb = relax_mask && n_hops;  // SPEC.md 2.8: either pointer null = no fallback anywhere
-    const bool qt = quota != nullptr;      // SPEC.md 2.10: null = no quota anywhere; any u32 is a legal cap
+    const bool sp = o.domain && o.max_skew;  // SPEC.md 2.7: either pointer null = no constraint anywhere
+    const bool fb = o.relax_mask && o.n_hops;  // SPEC.md 2.8: either pointer null = no fallback anywhere
+    const bool qt = o.quota != nullptr;    // SPEC.md 2.10: null = no quota anywhere; any u32 is a legal cap
 
     size_t sort_tmp = 0;
     if (C)
@@ -664,14 +660,15 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     fp_ws_reset(c);
     uint32_t *bad = (uint32_t *)fp_ws_take(c, 4);
     if (!bad) return FP_ENOMEM;
-    k_policy_check<<<1, 256, 0, st>>>(strategy, S, bad, c->d_err);
+    k_policy_check<<<1, 256, 0, st>>>(o.strategy, S, bad, c->d_err);
     FP_HIP(hipGetLastError());
     if (sp && N) {
-        k_policy_check_domain<<<grid_for((size_t)S * N, 256), 256, 0, st>>>(domain, max_skew, (size_t)S * N, N, bad, c->d_err);
+        k_policy_check_domain<<<grid_for((size_t)S * N, 256), 256, 0, st>>>(o.domain, o.max_skew, (size_t)S * N, N, bad,
+                                                                            c->d_err);
         FP_HIP(hipGetLastError());
     }
     if (fb) {
-        k_policy_check_hops<<<1, 256, 0, st>>>(n_hops, S, bad, c->d_err);
+        k_policy_check_hops<<<1, 256, 0, st>>>(o.n_hops, S, bad, c->d_err);
         FP_HIP(hipGetLastError());
     }
     if (C == 0) {  // nothing to place: every scenario costs (0 rejected, 0 nodes used)
@@ -712,21 +709,21 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t 
     a.level = b->level;
     a.cpu_free = b->cpu_free; a.mem_free = b->mem_free; a.conflict_used = b->conflict_used;
     a.labels = b->labels; a.schedulable = b->schedulable;
-    a.node_count = node_count;
-    a.strategy = strategy; a.preferred = preferred;
-    a.domain = sp ? domain : nullptr; a.max_skew = sp ? max_skew : nullptr;
-    a.relax_mask = fb ? relax_mask : nullptr; a.n_hops = fb ? n_hops : nullptr;
+    a.node_count = o.node_count;
+    a.strategy = o.strategy; a.preferred = o.preferred;
+    a.domain = sp ? o.domain : nullptr; a.max_skew = sp ? o.max_skew : nullptr;
+    a.relax_mask = fb ? o.relax_mask : nullptr; a.n_hops = fb ? o.n_hops : nullptr;
     a.assign = b->assign; a.reason = b->reason; a.cost = b->cost;
-    a.hops = fb ? hops : nullptr;
-    a.quota = quota; a.quota_used = qt ? quota_used : nullptr; a.quota_why = qt ? quota_why : nullptr;
+    a.hops = fb ? o.hops : nullptr;
+    a.quota = o.quota; a.quota_used = qt ? o.quota_used : nullptr; a.quota_why = qt ? o.quota_why : nullptr;
     a.bad = bad;
     fp_prof_begin(c, FP_K_PLACE, &ev);
     if (qt) launch_policy_by<true>(sp, fb, a, S, N, st);
     else launch_policy_by<false>(sp, fb, a, S, N, st);
     FP_HIP(hipGetLastError());
     fp_prof_end(c, FP_K_PLACE, ev);
-    if (hops && !fb) {
-        k_policy_zero_hops<<<grid_for(SC, 256), 256, 0, st>>>(hops, SC, bad);
+    if (o.hops && !fb) {
+        k_policy_zero_hops<<<grid_for(SC, 256), 256, 0, st>>>(o.hops, SC, bad);
         FP_HIP(hipGetLastError());
     }
     return FP_OK;

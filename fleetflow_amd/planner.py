@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as ct
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -27,7 +28,158 @@ def _u8(a):
 
 
 def _ptr(a):
+    """A numpy array's address for a pointer field of a struct (None = NULL); the caller keeps the array."""
     return None if a is None else a.ctypes.data
+
+
+_POINTER = {1: _lib.u8p, 4: _lib.u32p, 8: _lib.u64p}
+
+
+def _arg(a):
+    """A pointer argument of an export: None (NULL), a device tensor's address, or a typed pointer into a
+    numpy array (which it keeps alive)."""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        return a.data_ptr()
+    return a.ctypes.data_as(_POINTER[a.itemsize])
+
+
+# Every array is read (or written) for the length the call's sizes imply, so a shorter one would be
+# read out of bounds by the library: refused with ValueError first, as lib.rs returns FP_EINVAL.
+def _need(cond, what):
+    if not cond:
+        raise ValueError(what)
+
+
+def _tables(cont, nodes, n_cont, n_node, copy_mutable, names=("C", "N")):
+    """The container table (cpu_m, mem_mib, req_labels, conflict) and the node table (cpu_free, mem_free,
+    labels, conflict_used, schedulable) as contiguous arrays of ``n_cont`` and ``n_node`` entries (None = as
+    many as the first array holds); ``names`` is how the messages call the two sizes.  ``copy_mutable``
+    copies the node fields a placement updates, so the caller's stay as they were."""
+    cont = tuple(_u32(x) for x in cont)
+    cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
+    if copy_mutable:
+        cf, mf, cu = cf.copy(), mf.copy(), cu.copy()
+    nodes = (cf, mf, lab, cu, _u8(nodes[4]))
+    C = cont[0].size if n_cont is None else n_cont
+    N = cf.size if n_node is None else n_node
+    _need(all(x.size == C for x in cont), f"every container array must hold {names[0]} entries")
+    _need(all(x.size == N for x in nodes), f"every node array must hold {names[1]} entries")
+    return cont, nodes
+
+
+def _pair(cont, nodes):
+    return (FpContainers(cont[0].size, *(_ptr(x) for x in cont)), FpNodes(nodes[0].size, *(_ptr(x) for x in nodes)))
+
+
+def _batch(S, scen_base, C, N, cont, level, nodes, assign, reason, cost):
+    return FpBatch(S, scen_base, C, N, *(_ptr(x) for x in cont + (level,) + nodes + (assign, reason, cost)))
+
+
+def _relax_row(relax_mask):
+    """One scenario's relax masks as the FP_FALLBACK_MAX_HOPS words of the ABI (zero-padded)."""
+    row = [int(m) & 0xFFFFFFFF for m in relax_mask]
+    if len(row) > _lib.FP_FALLBACK_MAX_HOPS:
+        raise ValueError(f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+    return row + [0] * (_lib.FP_FALLBACK_MAX_HOPS - len(row))
+
+
+def _quota_rows(quota, S):
+    """[S * 3] u32 caps from S rows of (cpu_m, mem_mib, services); None in a row = QUOTA_UNLIMITED."""
+    rows = np.asarray([[_lib.QUOTA_UNLIMITED if x is None else int(x) for x in row]
+                       for row in np.asarray(quota, dtype=object).reshape(-1, _lib.QUOTA_DIMS)], dtype=np.int64)
+    if rows.shape[0] != S or rows.min(initial=0) < 0 or rows.max(initial=0) > 0xFFFFFFFF:
+        raise ValueError(f"quota must hold {S} rows of {_lib.QUOTA_DIMS} u32 caps")
+    return rows.astype(np.uint32).reshape(-1)
+
+
+def _policy_call(dims, cont, nodes, strategy, preferred, level, node_count, domain=None, max_skew=None,
+                 relax_mask=None, n_hops=None, quota=None, quota_used=None, want_hops=False, want_why=False,
+                 want_used=False):
+    """Everything a host scored-placement call sends, checked: ``dims`` is (S, C, N, scen_base) for the batch
+    methods and None for the single-scenario ones (S = 1, sizes from the tables, strategy / preferred /
+    max_skew / n_hops scalars, one relax row).  Returns a namespace: the converted inputs, the outputs
+    (hops / why / qu None unless wanted) and, as the export's arguments, ``head`` = the tables up to
+    node_count, ``spread`` = (domain, max_skew) and ``chain`` = (relax_mask, n_hops).  In a batch either one
+    of a pair None means both None."""
+    o = SimpleNamespace()
+    batch = dims is not None
+    S, C, N, scen_base = dims if batch else (1, None, None, 0)
+    by = "S * " if batch else ""
+    o.cont, o.nodes = _tables(cont, nodes, S * C if batch else None, S * N if batch else None, True,
+                              (by + "C", by + "N"))
+    if not batch:
+        C, N = o.cont[0].size, o.nodes[0].size
+    o.lv = _u32(level) if level is not None else None
+    o.nc = _u32(node_count).copy() if node_count is not None else None
+    _need(o.lv is None or o.lv.size == S * C, f"level must hold {by}C entries")
+    o.dom = o.sk = o.rm = o.nh = None
+    if batch:
+        o.st = _u32([strategy_id(x) for x in strategy])
+        o.pf = _u32(preferred) if preferred is not None else None
+        _need(o.st.size == S and (o.pf is None or o.pf.size == S), "strategy and preferred must hold S entries")
+        _need(o.nc is None or o.nc.size == S * N, "node_count must hold S * N entries")
+        if domain is not None and max_skew is not None:
+            o.dom, o.sk = _u32(domain), _u32(max_skew)
+            _need(o.dom.size == S * N and o.sk.size == S, "domain must hold S * N and max_skew S entries")
+        if relax_mask is not None and n_hops is not None:
+            o.rm, o.nh = _u32(relax_mask).reshape(-1), _u32(n_hops)
+            _need(o.rm.size == S * _lib.FP_FALLBACK_MAX_HOPS and o.nh.size == S,
+                  "relax_mask must hold S * FP_FALLBACK_MAX_HOPS and n_hops S entries")
+        o.spread, o.chain = (_arg(o.dom), _arg(o.sk)), (_arg(o.rm), _arg(o.nh))
+    else:
+        _need(o.nc is None or o.nc.size == N, "node_count must hold N entries")
+        o.dom = _u32(domain) if domain is not None else None
+        _need(o.dom is None or o.dom.size == N, "domain must hold N entries")
+        o.sk = int(max_skew)
+        _need(0 <= o.sk <= 0xFFFFFFFF, "max_skew must be a u32")
+        if relax_mask is not None:
+            o.rm = _u32(_relax_row(relax_mask))
+            o.nh = len(relax_mask) if n_hops is None else int(n_hops)
+            _need(0 <= o.nh <= 0xFFFFFFFF, "n_hops must be a u32")
+        o.spread, o.chain = (_arg(o.dom), o.sk), (_arg(o.rm), o.nh)
+    o.qt = _quota_rows(quota, S) if quota is not None else None
+    o.qu = None
+    if want_used:
+        o.qu = (np.zeros(S * _lib.QUOTA_DIMS, np.uint32) if quota_used is None
+                else _u32(quota_used).reshape(-1).copy())
+        _need(o.qu.size == S * _lib.QUOTA_DIMS, f"quota_used must hold {by}3 entries")
+    o.assign = np.empty(S * C, np.uint32)
+    o.reason = np.empty(S * C, np.uint8)
+    o.hops = np.empty(S * C, np.uint8) if want_hops else None
+    o.why = np.zeros(S * C, np.uint8) if want_why else None
+    if batch:
+        o.cost = np.empty(S, np.uint64)
+        o.b = _batch(S, scen_base, C, N, o.cont, o.lv, o.nodes, o.assign, o.reason, o.cost)
+        o.head = (ct.byref(o.b), _arg(o.st), _arg(o.pf), _arg(o.nc))
+    else:
+        o.cs, o.ns = _pair(o.cont, o.nodes)
+        o.head = (ct.byref(o.cs), ct.byref(o.ns), _arg(o.lv), strategy_id(strategy), int(preferred) & 0xFFFFFFFF,
+                  _arg(o.nc))
+    return o
+
+
+def _dev_policy_checks(db, strategy_t, preferred_t, count_t, domain_t, max_skew_t, relax_mask_t=None, n_hops_t=None,
+                       hops_t=None):
+    """The tensor sizes of a dev_place_batch_policy* call; returns (domain_t, max_skew_t, relax_mask_t,
+    n_hops_t) with either one of a pair None made both None."""
+    _need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
+    _need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
+    _need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
+    if domain_t is None or max_skew_t is None:
+        domain_t = max_skew_t = None
+    else:
+        _need(domain_t.numel() == db.S * db.N and max_skew_t.numel() == db.S,
+              "domain_t must hold S * N and max_skew_t S entries")
+    if relax_mask_t is None or n_hops_t is None:
+        relax_mask_t = n_hops_t = None
+    else:
+        _need(relax_mask_t.numel() == db.S * _lib.FP_FALLBACK_MAX_HOPS and n_hops_t.numel() == db.S,
+              "relax_mask_t must hold S * FP_FALLBACK_MAX_HOPS and n_hops_t S entries")
+    _need(hops_t is None or (hops_t.numel() == db.S * db.C and hops_t.element_size() == 1),
+          "hops_t must hold S * C bytes")
+    return domain_t, max_skew_t, relax_mask_t, n_hops_t
 
 
 def strategy_id(strategy) -> int:
@@ -59,6 +211,7 @@ class Planner:
                 self._tstream = None
             self._L.fp_ctx_destroy(self._ctx)
             self._ctx = None
+            self._fs = None  # plan_stage_lists' prebuilt call holds the handle
 
     def __del__(self):
         try:
@@ -140,12 +293,9 @@ class Planner:
         return ms.value, n.value
 
     # -- host-pointer API ------------------------------------------------------------
-    # Every array is read (or written) for the length the call's sizes imply, so a shorter one would be
-    # read out of bounds by the library: refused with ValueError first, as lib.rs returns FP_EINVAL.
-    @staticmethod
-    def _need(cond, what):
-        if not cond:
-            raise ValueError(what)
+    _need = staticmethod(_need)
+    _relax_row = staticmethod(_relax_row)
+    _quota_rows = staticmethod(_quota_rows)
 
     def legacy_order(self, has_deps):
         """engine.rs:67-85 on indices: has_deps[i] = known && depends_on non-empty."""
@@ -176,7 +326,7 @@ class Planner:
         V, E = len(has_deps), len(col)
         self._need(V == 0 or len(row_ptr) == V + 1, "row_ptr must hold V + 1 entries")
         fs = getattr(self, "_fs", None)
-        if fs is None or V > fs["V"] or E > fs["E"]:
+        if fs is None or V > fs["V"] or E > fs["E"] or fs["args"][0] is not self._ctx:
             cv, ce = max(64, V), max(256, E)
             rp, cl, hd = (ct.c_uint32 * (cv + 1))(), (ct.c_uint32 * ce)(), (ct.c_uint8 * cv)()
             out, ncyc = (ct.c_uint32 * (3 * cv))(), ct.c_uint32()
@@ -217,60 +367,43 @@ class Planner:
             check(self._L.fp_plan_stage(self._ctx, ct.byref(g), None, None, o, o + 4 * V, o + 8 * V, ct.byref(ncyc),
                                         None, None, None, None), "fp_plan_stage")
             return perm, level, order, ncyc.value, None
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        self._need(all(x.size == V for x in (cpu, mem, req, conf)), "every container array must hold V entries")
-        self._need(all(x.size == cf.size for x in (mf, lab, cu, sched)), "every node array must hold N entries")
+        cont, nodes = _tables(cont, nodes, V, None, True, ("V", "N"))
         first = np.empty(V, np.uint32)
         count = np.empty(V, np.uint32)
         assign = np.empty(V, np.uint32)
         reason = np.empty(V, np.uint8)
-        cs = FpContainers(V, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
-        ns = FpNodes(cf.size, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
+        cs, ns = _pair(cont, nodes)
         check(self._L.fp_plan_stage(self._ctx, ct.byref(g), ct.byref(cs), ct.byref(ns), o, o + 4 * V, o + 8 * V,
                                     ct.byref(ncyc), first.ctypes.data, count.ctypes.data, assign.ctypes.data,
                                     reason.ctypes.data), "fp_plan_stage")
-        return perm, level, order, ncyc.value, (first, count, assign, reason, (cf, mf, lab, cu, sched))
+        return perm, level, order, ncyc.value, (first, count, assign, reason, nodes)
 
     def place(self, cont, nodes, level=None):
         """cont = (cpu_m, mem_mib, req_labels, conflict); nodes = (cpu_free, mem_free,
         labels, conflict_used, schedulable).  Inputs are not mutated; the updated node
         state is returned.  Returns (assign, reason, nodes_after)."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        C, N = cpu.size, cf.size
+        cont, nodes = _tables(cont, nodes, None, None, True)
+        C = cont[0].size
         lv = _u32(level) if level is not None else None
-        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
-        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
         self._need(lv is None or lv.size == C, "level must hold C entries")
         assign = np.empty(C, np.uint32)
         reason = np.empty(C, np.uint8)
-        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
-        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
-        check(self._L.fp_place(self._ctx, ct.byref(cs), ct.byref(ns),
-                               lv.ctypes.data_as(_lib.u32p) if lv is not None else None,
-                               assign.ctypes.data_as(_lib.u32p), reason.ctypes.data_as(_lib.u8p)), "fp_place")
-        return assign, reason, (cf, mf, lab, cu, sched)
+        cs, ns = _pair(cont, nodes)
+        check(self._L.fp_place(self._ctx, ct.byref(cs), ct.byref(ns), _arg(lv), _arg(assign), _arg(reason)), "fp_place")
+        return assign, reason, nodes
 
     def place_batch(self, S, C, N, cont, nodes, level=None, scen_base=0):
         """Scenario-major arrays ([S*C] containers, [S*N] nodes).  Returns
         (assign, reason, cost, nodes_after)."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
+        cont, nodes = _tables(cont, nodes, S * C, S * N, True, ("S * C", "S * N"))
         lv = _u32(level) if level is not None else None
-        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
-        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
         self._need(lv is None or lv.size == S * C, "level must hold S * C entries")
         assign = np.empty(S * C, np.uint32)
         reason = np.empty(S * C, np.uint8)
         cost = np.empty(S, np.uint64)
-        b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
-                    _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
+        b = _batch(S, scen_base, C, N, cont, lv, nodes, assign, reason, cost)
         check(self._L.fp_place_batch(self._ctx, ct.byref(b)), "fp_place_batch")
-        return assign, reason, cost, (cf, mf, lab, cu, sched)
+        return assign, reason, cost, nodes
 
     def place_policy(self, cont, nodes, strategy, preferred=0, level=None, node_count=None, *, domain=None,
                      max_skew=0):
@@ -282,33 +415,13 @@ class Planner:
         back with reason REASON_SKEW.  No domain, or max_skew = 0, is no constraint.  Inputs are not
         mutated.  Returns (assign, reason, nodes_after, node_count_after); the last is None without
         node_count."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        C, N = cpu.size, cf.size
-        lv = _u32(level) if level is not None else None
-        nc = _u32(node_count).copy() if node_count is not None else None
-        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
-        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
-        self._need(lv is None or lv.size == C, "level must hold C entries")
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        dom = _u32(domain) if domain is not None else None
-        self._need(dom is None or dom.size == N, "domain must hold N entries")
-        self._need(0 <= int(max_skew) <= 0xFFFFFFFF, "max_skew must be a u32")
-        assign = np.empty(C, np.uint32)
-        reason = np.empty(C, np.uint8)
-        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
-        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
-        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
-        if dom is not None:
-            check(self._L.fp_place_policy_spread(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
-                                                 int(preferred) & 0xFFFFFFFF, p32(nc), p32(dom), int(max_skew),
-                                                 p32(assign), reason.ctypes.data_as(_lib.u8p)), "fp_place_policy_spread")
-            return assign, reason, (cf, mf, lab, cu, sched), nc
-        check(self._L.fp_place_policy(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
-                                      int(preferred) & 0xFFFFFFFF, p32(nc), p32(assign),
-                                      reason.ctypes.data_as(_lib.u8p)), "fp_place_policy")
-        return assign, reason, (cf, mf, lab, cu, sched), nc
+        o = _policy_call(None, cont, nodes, strategy, preferred, level, node_count, domain, max_skew)
+        if o.dom is not None:
+            check(self._L.fp_place_policy_spread(self._ctx, *o.head, *o.spread, _arg(o.assign), _arg(o.reason)),
+                  "fp_place_policy_spread")
+        else:
+            check(self._L.fp_place_policy(self._ctx, *o.head, _arg(o.assign), _arg(o.reason)), "fp_place_policy")
+        return o.assign, o.reason, o.nodes, o.nc
 
     def place_batch_policy(self, S, C, N, cont, nodes, strategy, preferred=None, level=None, node_count=None,
                            scen_base=0, *, domain=None, max_skew=None):
@@ -316,40 +429,13 @@ class Planner:
         ([S] or None) and node counts ([S*N] or None).  ``domain`` ([S*N]) with ``max_skew`` ([S], 0 = no
         constraint in that scenario) is the topology spread of SPEC.md 2.7; either one None is no
         constraint anywhere.  Returns (assign, reason, cost, nodes_after, node_count_after)."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        lv = _u32(level) if level is not None else None
-        st = _u32([strategy_id(x) for x in strategy])
-        pf = _u32(preferred) if preferred is not None else None
-        nc = _u32(node_count).copy() if node_count is not None else None
-        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
-        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
-        self._need(lv is None or lv.size == S * C, "level must hold S * C entries")
-        self._need(st.size == S and (pf is None or pf.size == S), "strategy and preferred must hold S entries")
-        self._need(nc is None or nc.size == S * N, "node_count must hold S * N entries")
-        assign = np.empty(S * C, np.uint32)
-        reason = np.empty(S * C, np.uint8)
-        cost = np.empty(S, np.uint64)
-        b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
-                    _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
-        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
-        if domain is not None and max_skew is not None:
-            dom, sk = _u32(domain), _u32(max_skew)
-            self._need(dom.size == S * N and sk.size == S, "domain must hold S * N and max_skew S entries")
-            check(self._L.fp_place_batch_policy_spread(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc), p32(dom),
-                                                       p32(sk)), "fp_place_batch_policy_spread")
-            return assign, reason, cost, (cf, mf, lab, cu, sched), nc
-        check(self._L.fp_place_batch_policy(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc)), "fp_place_batch_policy")
-        return assign, reason, cost, (cf, mf, lab, cu, sched), nc
-
-    @staticmethod
-    def _relax_row(relax_mask):
-        """One scenario's relax masks as the FP_FALLBACK_MAX_HOPS words of the ABI (zero-padded)."""
-        row = [int(m) & 0xFFFFFFFF for m in relax_mask]
-        if len(row) > _lib.FP_FALLBACK_MAX_HOPS:
-            raise ValueError(f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
-        return row + [0] * (_lib.FP_FALLBACK_MAX_HOPS - len(row))
+        o = _policy_call((S, C, N, scen_base), cont, nodes, strategy, preferred, level, node_count, domain,
+                         max_skew)
+        if o.dom is not None:
+            check(self._L.fp_place_batch_policy_spread(self._ctx, *o.head, *o.spread), "fp_place_batch_policy_spread")
+        else:
+            check(self._L.fp_place_batch_policy(self._ctx, *o.head), "fp_place_batch_policy")
+        return o.assign, o.reason, o.cost, o.nodes, o.nc
 
     def place_policy_fallback(self, cont, nodes, strategy, relax_mask, preferred=0, level=None, node_count=None, *,
                               domain=None, max_skew=0, n_hops=None, want_hops=True):
@@ -360,34 +446,11 @@ class Planner:
         no node of an earlier hop is feasible.  ``domain`` / ``max_skew`` as in place_policy.  Returns
         (assign, reason, hops, nodes_after, node_count_after): hops[c] is the winner's hop (0 when rejected),
         or None with ``want_hops`` False."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        C, N = cpu.size, cf.size
-        lv = _u32(level) if level is not None else None
-        nc = _u32(node_count).copy() if node_count is not None else None
-        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
-        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
-        self._need(lv is None or lv.size == C, "level must hold C entries")
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        dom = _u32(domain) if domain is not None else None
-        self._need(dom is None or dom.size == N, "domain must hold N entries")
-        self._need(0 <= int(max_skew) <= 0xFFFFFFFF, "max_skew must be a u32")
-        rm = _u32(self._relax_row(relax_mask))
-        nh = len(relax_mask) if n_hops is None else int(n_hops)
-        self._need(0 <= nh <= 0xFFFFFFFF, "n_hops must be a u32")
-        assign = np.empty(C, np.uint32)
-        reason = np.empty(C, np.uint8)
-        hops = np.empty(C, np.uint8) if want_hops else None
-        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
-        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
-        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
-        check(self._L.fp_place_policy_fallback(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
-                                               int(preferred) & 0xFFFFFFFF, p32(nc), p32(dom), int(max_skew), p32(rm),
-                                               nh, p32(assign), reason.ctypes.data_as(_lib.u8p),
-                                               hops.ctypes.data_as(_lib.u8p) if want_hops else None),
-              "fp_place_policy_fallback")
-        return assign, reason, hops, (cf, mf, lab, cu, sched), nc
+        o = _policy_call(None, cont, nodes, strategy, preferred, level, node_count, domain, max_skew,
+                         relax_mask, n_hops, want_hops=want_hops)
+        check(self._L.fp_place_policy_fallback(self._ctx, *o.head, *o.spread, *o.chain, _arg(o.assign), _arg(o.reason),
+                                               _arg(o.hops)), "fp_place_policy_fallback")
+        return o.assign, o.reason, o.hops, o.nodes, o.nc
 
     def place_batch_policy_fallback(self, S, C, N, cont, nodes, strategy, preferred=None, level=None, node_count=None,
                                     scen_base=0, *, domain=None, max_skew=None, relax_mask=None, n_hops=None,
@@ -396,47 +459,11 @@ class Planner:
         ([S * FP_FALLBACK_MAX_HOPS], scenario-major) with ``n_hops`` ([S], 0 = no fallback in that scenario);
         either one None is no fallback anywhere.  Returns (assign, reason, hops, cost, nodes_after,
         node_count_after); hops is [S*C] u8, or None with ``want_hops`` False."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        lv = _u32(level) if level is not None else None
-        st = _u32([strategy_id(x) for x in strategy])
-        pf = _u32(preferred) if preferred is not None else None
-        nc = _u32(node_count).copy() if node_count is not None else None
-        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
-        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
-        self._need(lv is None or lv.size == S * C, "level must hold S * C entries")
-        self._need(st.size == S and (pf is None or pf.size == S), "strategy and preferred must hold S entries")
-        self._need(nc is None or nc.size == S * N, "node_count must hold S * N entries")
-        dom = sk = rm = nh = None
-        if domain is not None and max_skew is not None:
-            dom, sk = _u32(domain), _u32(max_skew)
-            self._need(dom.size == S * N and sk.size == S, "domain must hold S * N and max_skew S entries")
-        if relax_mask is not None and n_hops is not None:
-            rm, nh = _u32(relax_mask).reshape(-1), _u32(n_hops)
-            self._need(rm.size == S * _lib.FP_FALLBACK_MAX_HOPS and nh.size == S,
-                       "relax_mask must hold S * FP_FALLBACK_MAX_HOPS and n_hops S entries")
-        assign = np.empty(S * C, np.uint32)
-        reason = np.empty(S * C, np.uint8)
-        hops = np.empty(S * C, np.uint8) if want_hops else None
-        cost = np.empty(S, np.uint64)
-        b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
-                    _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
-        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
-        check(self._L.fp_place_batch_policy_fallback(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc), p32(dom), p32(sk),
-                                                     p32(rm), p32(nh),
-                                                     hops.ctypes.data_as(_lib.u8p) if want_hops else None),
+        o = _policy_call((S, C, N, scen_base), cont, nodes, strategy, preferred, level, node_count, domain,
+                         max_skew, relax_mask, n_hops, want_hops=want_hops)
+        check(self._L.fp_place_batch_policy_fallback(self._ctx, *o.head, *o.spread, *o.chain, _arg(o.hops)),
               "fp_place_batch_policy_fallback")
-        return assign, reason, hops, cost, (cf, mf, lab, cu, sched), nc
-
-    @staticmethod
-    def _quota_rows(quota, S):
-        """[S * 3] u32 caps from S rows of (cpu_m, mem_mib, services); None in a row = QUOTA_UNLIMITED."""
-        rows = np.asarray([[_lib.QUOTA_UNLIMITED if x is None else int(x) for x in row]
-                           for row in np.asarray(quota, dtype=object).reshape(-1, _lib.QUOTA_DIMS)], dtype=np.int64)
-        if rows.shape[0] != S or rows.min(initial=0) < 0 or rows.max(initial=0) > 0xFFFFFFFF:
-            raise ValueError(f"quota must hold {S} rows of {_lib.QUOTA_DIMS} u32 caps")
-        return rows.astype(np.uint32).reshape(-1)
+        return o.assign, o.reason, o.hops, o.cost, o.nodes, o.nc
 
     def place_policy_quota(self, cont, nodes, strategy, quota, quota_used=None, relax_mask=(), preferred=0, level=None,
                            node_count=None, *, domain=None, max_skew=0, n_hops=None, want_hops=True, want_why=True,
@@ -449,40 +476,11 @@ class Planner:
         (assign, reason, hops, nodes_after, node_count_after, quota_why, quota_used_after); quota_why is None
         with ``want_why`` False, and with ``want_used`` False the library gets no quota_used (usage starts at
         zero whatever was passed) and None comes back."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        C, N = cpu.size, cf.size
-        lv = _u32(level) if level is not None else None
-        nc = _u32(node_count).copy() if node_count is not None else None
-        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
-        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
-        self._need(lv is None or lv.size == C, "level must hold C entries")
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        dom = _u32(domain) if domain is not None else None
-        self._need(dom is None or dom.size == N, "domain must hold N entries")
-        self._need(0 <= int(max_skew) <= 0xFFFFFFFF, "max_skew must be a u32")
-        rm = _u32(self._relax_row(relax_mask))
-        nh = len(relax_mask) if n_hops is None else int(n_hops)
-        self._need(0 <= nh <= 0xFFFFFFFF, "n_hops must be a u32")
-        qt = self._quota_rows(quota, 1) if quota is not None else None
-        qu = None
-        if want_used:
-            qu = _u32([0] * _lib.QUOTA_DIMS if quota_used is None else quota_used).copy()
-            self._need(qu.size == _lib.QUOTA_DIMS, "quota_used must hold 3 entries")
-        assign = np.empty(C, np.uint32)
-        reason = np.empty(C, np.uint8)
-        hops = np.empty(C, np.uint8) if want_hops else None
-        why = np.zeros(C, np.uint8) if want_why else None
-        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
-        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
-        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
-        p8 = lambda a: a.ctypes.data_as(_lib.u8p) if a is not None else None  # noqa: E731
-        check(self._L.fp_place_policy_quota(self._ctx, ct.byref(cs), ct.byref(ns), p32(lv), strategy_id(strategy),
-                                            int(preferred) & 0xFFFFFFFF, p32(nc), p32(dom), int(max_skew), p32(rm), nh,
-                                            p32(assign), p8(reason), p8(hops), p32(qt), p32(qu), p8(why)),
-              "fp_place_policy_quota")
-        return assign, reason, hops, (cf, mf, lab, cu, sched), nc, why, qu
+        o = _policy_call(None, cont, nodes, strategy, preferred, level, node_count, domain, max_skew,
+                         relax_mask, n_hops, quota, quota_used, want_hops, want_why, want_used)
+        check(self._L.fp_place_policy_quota(self._ctx, *o.head, *o.spread, *o.chain, _arg(o.assign), _arg(o.reason),
+                                            _arg(o.hops), _arg(o.qt), _arg(o.qu), _arg(o.why)), "fp_place_policy_quota")
+        return o.assign, o.reason, o.hops, o.nodes, o.nc, o.why, o.qu
 
     def place_batch_policy_quota(self, S, C, N, cont, nodes, strategy, quota, quota_used=None, preferred=None,
                                  level=None, node_count=None, scen_base=0, *, domain=None, max_skew=None,
@@ -491,58 +489,21 @@ class Planner:
         cpu, memory, services; QUOTA_UNLIMITED = no cap), ``quota_used`` [S * 3] or None = zeros; ``quota``
         None is no quota anywhere.  Returns (assign, reason, hops, cost, nodes_after, node_count_after,
         quota_why [S*C], quota_used_after [S*3]); the ``want_*`` switches as in place_policy_quota."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf = _u32(nodes[0]).copy(), _u32(nodes[1]).copy()
-        lab, cu, sched = _u32(nodes[2]), _u32(nodes[3]).copy(), _u8(nodes[4])
-        lv = _u32(level) if level is not None else None
-        st = _u32([strategy_id(x) for x in strategy])
-        pf = _u32(preferred) if preferred is not None else None
-        nc = _u32(node_count).copy() if node_count is not None else None
-        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
-        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
-        self._need(lv is None or lv.size == S * C, "level must hold S * C entries")
-        self._need(st.size == S and (pf is None or pf.size == S), "strategy and preferred must hold S entries")
-        self._need(nc is None or nc.size == S * N, "node_count must hold S * N entries")
-        dom = sk = rm = nh = None
-        if domain is not None and max_skew is not None:
-            dom, sk = _u32(domain), _u32(max_skew)
-            self._need(dom.size == S * N and sk.size == S, "domain must hold S * N and max_skew S entries")
-        if relax_mask is not None and n_hops is not None:
-            rm, nh = _u32(relax_mask).reshape(-1), _u32(n_hops)
-            self._need(rm.size == S * _lib.FP_FALLBACK_MAX_HOPS and nh.size == S,
-                       "relax_mask must hold S * FP_FALLBACK_MAX_HOPS and n_hops S entries")
-        qt = self._quota_rows(quota, S) if quota is not None else None
-        qu = None
-        if want_used:
-            qu = (np.zeros(S * _lib.QUOTA_DIMS, np.uint32) if quota_used is None else _u32(quota_used).reshape(-1).copy())
-            self._need(qu.size == S * _lib.QUOTA_DIMS, "quota_used must hold S * 3 entries")
-        assign = np.empty(S * C, np.uint32)
-        reason = np.empty(S * C, np.uint8)
-        hops = np.empty(S * C, np.uint8) if want_hops else None
-        why = np.zeros(S * C, np.uint8) if want_why else None
-        cost = np.empty(S, np.uint64)
-        b = FpBatch(S, scen_base, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), _ptr(lv), _ptr(cf),
-                    _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched), _ptr(assign), _ptr(reason), _ptr(cost))
-        p32 = lambda a: a.ctypes.data_as(_lib.u32p) if a is not None else None  # noqa: E731
-        p8 = lambda a: a.ctypes.data_as(_lib.u8p) if a is not None else None  # noqa: E731
-        check(self._L.fp_place_batch_policy_quota(self._ctx, ct.byref(b), p32(st), p32(pf), p32(nc), p32(dom), p32(sk),
-                                                  p32(rm), p32(nh), p8(hops), p32(qt), p32(qu), p8(why)),
-              "fp_place_batch_policy_quota")
-        return assign, reason, hops, cost, (cf, mf, lab, cu, sched), nc, why, qu
+        o = _policy_call((S, C, N, scen_base), cont, nodes, strategy, preferred, level, node_count, domain,
+                         max_skew, relax_mask, n_hops, quota, quota_used, want_hops, want_why, want_used)
+        check(self._L.fp_place_batch_policy_quota(self._ctx, *o.head, *o.spread, *o.chain, _arg(o.hops), _arg(o.qt),
+                                                  _arg(o.qu), _arg(o.why)), "fp_place_batch_policy_quota")
+        return o.assign, o.reason, o.hops, o.cost, o.nodes, o.nc, o.why, o.qu
 
     def feasibility(self, cont, nodes, bitmap=True):
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
-        sched = _u8(nodes[4])
-        C, N = cpu.size, cf.size
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
         first = np.empty(C, np.uint32)
         count = np.empty(C, np.uint32)
         bm = np.empty(((C + 63) // 64) * N, np.uint64) if bitmap else None
-        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
-        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
-        check(self._L.fp_feasibility(self._ctx, ct.byref(cs), ct.byref(ns), first.ctypes.data_as(_lib.u32p),
-                                     count.ctypes.data_as(_lib.u32p),
-                                     bm.ctypes.data_as(_lib.u64p) if bm is not None else None), "fp_feasibility")
+        cs, ns = _pair(cont, nodes)
+        check(self._L.fp_feasibility(self._ctx, ct.byref(cs), ct.byref(ns), _arg(first), _arg(count), _arg(bm)),
+              "fp_feasibility")
         return first, count, bm
 
     def explain(self, cont, nodes, sel=None, ignore_labels=0):
@@ -550,22 +511,15 @@ class Planner:
         container on the given node table -- ``sel`` container indices (repeats allowed) or None = every
         container in order; ``ignore_labels`` the required-label bits given up.  Nothing is placed.
         Returns an ndarray [M, 16] (word indices: _lib.EXPLAIN_*)."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
-        sched = _u8(nodes[4])
-        C, N = cpu.size, cf.size
-        self._need(all(x.size == C for x in (mem, req, conf)), "every container array must hold C entries")
-        self._need(all(x.size == N for x in (mf, lab, cu, sched)), "every node array must hold N entries")
+        cont, nodes = _tables(cont, nodes, None, None, False)
         sl = _u32(sel).reshape(-1) if sel is not None else None
-        M = C if sl is None else sl.size
+        M = cont[0].size if sl is None else sl.size
         rows = np.empty((M, _lib.EXPLAIN_WORDS), np.uint32)
         if M == 0:  # an empty sel must not reach the library as NULL (= every container)
             return rows
-        cs = FpContainers(C, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf))
-        ns = FpNodes(N, _ptr(cf), _ptr(mf), _ptr(lab), _ptr(cu), _ptr(sched))
-        check(self._L.fp_explain(self._ctx, ct.byref(cs), ct.byref(ns),
-                                 sl.ctypes.data_as(_lib.u32p) if sl is not None else None, M,
-                                 int(ignore_labels) & 0xFFFFFFFF, rows.ctypes.data_as(_lib.u32p)), "fp_explain")
+        cs, ns = _pair(cont, nodes)
+        check(self._L.fp_explain(self._ctx, ct.byref(cs), ct.byref(ns), _arg(sl), M, int(ignore_labels) & 0xFFFFFFFF,
+                                 _arg(rows)), "fp_explain")
         return rows
 
     def explain_batch(self, S, C, N, cont, nodes, reason, reason_mask, ignore_labels=None):
@@ -573,21 +527,15 @@ class Planner:
         ``reason_mask`` bit r selects the containers with reason r (0 = every container, ``reason`` may be
         None), ``ignore_labels`` [S] or None.  Returns an ndarray [S, 8] (word indices 0..4 = the causes,
         _lib.EXPLAIN_HIST_*)."""
-        cpu, mem, req, conf = (_u32(x) for x in cont)
-        cf, mf, lab, cu = (_u32(x) for x in nodes[:4])
-        sched = _u8(nodes[4])
+        cont, nodes = _tables(cont, nodes, S * C, S * N, False, ("S * C", "S * N"))
         rs = _u8(reason) if reason is not None else None
         ig = _u32(ignore_labels) if ignore_labels is not None else None
-        self._need(all(x.size == S * C for x in (cpu, mem, req, conf)), "every container array must hold S * C entries")
-        self._need(all(x.size == S * N for x in (cf, mf, lab, cu, sched)), "every node array must hold S * N entries")
         self._need(int(reason_mask) == 0 or (rs is not None and rs.size == S * C), "reason must hold S * C entries")
         self._need(ig is None or ig.size == S, "ignore_labels must hold S entries")
         hist = np.empty((S, _lib.EXPLAIN_HIST_WORDS), np.uint32)
-        b = FpBatch(S, 0, C, N, _ptr(cpu), _ptr(mem), _ptr(req), _ptr(conf), None, _ptr(cf), _ptr(mf), _ptr(lab),
-                    _ptr(cu), _ptr(sched), None, _ptr(rs), None)
-        check(self._L.fp_explain_batch(self._ctx, ct.byref(b), int(reason_mask) & 0xFFFFFFFF,
-                                       ig.ctypes.data_as(_lib.u32p) if ig is not None else None,
-                                       hist.ctypes.data_as(_lib.u32p)), "fp_explain_batch")
+        b = _batch(S, 0, C, N, cont, None, nodes, None, rs, None)
+        check(self._L.fp_explain_batch(self._ctx, ct.byref(b), int(reason_mask) & 0xFFFFFFFF, _arg(ig), _arg(hist)),
+              "fp_explain_batch")
         return hist
 
     # -- device-pointer API -------------------------------------------------------------
@@ -629,20 +577,13 @@ class Planner:
         ``preferred_t`` [S] or None, ``count_t`` [S*N] in/out or None -- device tensors.  ``domain_t``
         [S*N] with ``max_skew_t`` [S] (int32 storage of u32 values) is the topology spread of SPEC.md 2.7
         (fp_dev_place_batch_policy_spread); either one None is no constraint."""
-        self._need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
-        self._need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
-        self._need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        if domain_t is not None and max_skew_t is not None:
-            self._need(domain_t.numel() == db.S * db.N and max_skew_t.numel() == db.S,
-                       "domain_t must hold S * N and max_skew_t S entries")
-            self._dev(lambda: check(self._L.fp_dev_place_batch_policy_spread(
-                self._ctx, ct.byref(db.struct()), p(strategy_t), p(preferred_t), p(count_t), p(domain_t), p(max_skew_t)),
-                "fp_dev_place_batch_policy_spread"))
-            return
-        self._dev(lambda: check(self._L.fp_dev_place_batch_policy(self._ctx, ct.byref(db.struct()), p(strategy_t),
-                                                                  p(preferred_t), p(count_t)),
-                                "fp_dev_place_batch_policy"))
+        domain_t, max_skew_t, _, _ = _dev_policy_checks(db, strategy_t, preferred_t, count_t, domain_t, max_skew_t)
+        head = (self._ctx, ct.byref(db.struct()), _arg(strategy_t), _arg(preferred_t), _arg(count_t))
+        if domain_t is not None:
+            self._dev(lambda: check(self._L.fp_dev_place_batch_policy_spread(*head, _arg(domain_t), _arg(max_skew_t)),
+                                    "fp_dev_place_batch_policy_spread"))
+        else:
+            self._dev(lambda: check(self._L.fp_dev_place_batch_policy(*head), "fp_dev_place_batch_policy"))
 
     def dev_place_batch_policy_fallback(self, db: "DevBatch", strategy_t, preferred_t=None, count_t=None, *,
                                         domain_t=None, max_skew_t=None, relax_mask_t=None, n_hops_t=None, hops_t=None):
@@ -651,25 +592,11 @@ class Planner:
         values; either one None is no fallback), ``hops_t`` [S*C] uint8 out or None.  An n_hops above
         FP_FALLBACK_MAX_HOPS is found on the device: nothing is written and sync() raises FP_EINVAL.
         Returns hops_t."""
-        self._need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
-        self._need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
-        self._need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
-        if domain_t is None or max_skew_t is None:
-            domain_t = max_skew_t = None
-        else:
-            self._need(domain_t.numel() == db.S * db.N and max_skew_t.numel() == db.S,
-                       "domain_t must hold S * N and max_skew_t S entries")
-        if relax_mask_t is None or n_hops_t is None:
-            relax_mask_t = n_hops_t = None
-        else:
-            self._need(relax_mask_t.numel() == db.S * _lib.FP_FALLBACK_MAX_HOPS and n_hops_t.numel() == db.S,
-                       "relax_mask_t must hold S * FP_FALLBACK_MAX_HOPS and n_hops_t S entries")
-        self._need(hops_t is None or (hops_t.numel() == db.S * db.C and hops_t.element_size() == 1),
-                   "hops_t must hold S * C bytes")
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._dev(lambda: check(self._L.fp_dev_place_batch_policy_fallback(
-            self._ctx, ct.byref(db.struct()), p(strategy_t), p(preferred_t), p(count_t), p(domain_t), p(max_skew_t),
-            p(relax_mask_t), p(n_hops_t), p(hops_t)), "fp_dev_place_batch_policy_fallback"))
+        pairs = _dev_policy_checks(db, strategy_t, preferred_t, count_t, domain_t, max_skew_t, relax_mask_t, n_hops_t,
+                                   hops_t)
+        args = [_arg(t) for t in (strategy_t, preferred_t, count_t, *pairs, hops_t)]
+        self._dev(lambda: check(self._L.fp_dev_place_batch_policy_fallback(self._ctx, ct.byref(db.struct()), *args),
+                                "fp_dev_place_batch_policy_fallback"))
         return hops_t
 
     def dev_place_batch_policy_quota(self, db: "DevBatch", strategy_t, quota_t, quota_used_t=None, preferred_t=None,
@@ -679,31 +606,16 @@ class Planner:
         -- ``quota_t`` [S * 3] (int32 storage of u32 caps, -1 = QUOTA_UNLIMITED; None = no quota anywhere),
         ``quota_used_t`` [S * 3] in/out or None (usage starts at zero and is not returned), ``quota_why_t``
         [S*C] uint8 out or None.  Returns (hops_t, quota_why_t, quota_used_t)."""
-        self._need(strategy_t.numel() == db.S, "strategy_t must hold S entries")
-        self._need(preferred_t is None or preferred_t.numel() == db.S, "preferred_t must hold S entries")
-        self._need(count_t is None or count_t.numel() == db.S * db.N, "count_t must hold S * N entries")
-        if domain_t is None or max_skew_t is None:
-            domain_t = max_skew_t = None
-        else:
-            self._need(domain_t.numel() == db.S * db.N and max_skew_t.numel() == db.S,
-                       "domain_t must hold S * N and max_skew_t S entries")
-        if relax_mask_t is None or n_hops_t is None:
-            relax_mask_t = n_hops_t = None
-        else:
-            self._need(relax_mask_t.numel() == db.S * _lib.FP_FALLBACK_MAX_HOPS and n_hops_t.numel() == db.S,
-                       "relax_mask_t must hold S * FP_FALLBACK_MAX_HOPS and n_hops_t S entries")
-        self._need(hops_t is None or (hops_t.numel() == db.S * db.C and hops_t.element_size() == 1),
-                   "hops_t must hold S * C bytes")
+        pairs = _dev_policy_checks(db, strategy_t, preferred_t, count_t, domain_t, max_skew_t, relax_mask_t, n_hops_t,
+                                   hops_t)
         for t in (quota_t, quota_used_t):
             self._need(t is None or (t.numel() == db.S * _lib.QUOTA_DIMS and t.element_size() == 4),
                        "quota_t and quota_used_t must hold S * 3 32-bit entries")
         self._need(quota_why_t is None or (quota_why_t.numel() == db.S * db.C and quota_why_t.element_size() == 1),
                    "quota_why_t must hold S * C bytes")
-        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._dev(lambda: check(self._L.fp_dev_place_batch_policy_quota(
-            self._ctx, ct.byref(db.struct()), p(strategy_t), p(preferred_t), p(count_t), p(domain_t), p(max_skew_t),
-            p(relax_mask_t), p(n_hops_t), p(hops_t), p(quota_t), p(quota_used_t), p(quota_why_t)),
-            "fp_dev_place_batch_policy_quota"))
+        args = [_arg(t) for t in (strategy_t, preferred_t, count_t, *pairs, hops_t, quota_t, quota_used_t, quota_why_t)]
+        self._dev(lambda: check(self._L.fp_dev_place_batch_policy_quota(self._ctx, ct.byref(db.struct()), *args),
+                                "fp_dev_place_batch_policy_quota"))
         return hops_t, quota_why_t, quota_used_t
 
     def dev_argmin_cost(self, cost_t, out_t):

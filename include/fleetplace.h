@@ -149,7 +149,8 @@ int fp_ctx_profile(fp_ctx *ctx, int enable);
 int fp_ctx_kernel_stats(fp_ctx *ctx, int kernel_id, double *total_ms, uint64_t *launches);
 /* The FFD kernel the last placement call on this context ran (waits for the stream): out[0] / out[1]
  * = the OR of every cpu / mem value of its batch (containers and schedulable nodes), out[2] = 1 for
- * the u32 records, 2 for the packed (cpu, mem) records (FP_OPT_PACKED), 0 if nothing ran. */
+ * the u32 records, 2 for the packed (cpu, mem) records (FP_OPT_PACKED), 0 if nothing ran.  All zero
+ * also when a later call on the context has reused the workspace. */
 int fp_ctx_place_path(fp_ctx *ctx, uint32_t *out3);
 
 /* Per-context tuning / test options.  FP_OPT_AUTO (-1) = the production choice (the

@@ -250,6 +250,29 @@ def test_place_path_after_a_policy_call(planner, O):
     assert planner.place_path()["ran"]
 
 
+def test_place_path_after_the_workspace_is_reused(planner, O):
+    """The last placement's range words live in the workspace arena, and the arena's reset forgets them:
+    after a levelize or a plan_stage that reuses the arena, place_path() reports that nothing ran instead of
+    reading recycled memory, and the next placement is unchanged.  FP_OPT_LEVEL_SMALL = 0 keeps both on the
+    general path: the one-launch kernels of a 20-vertex graph take no workspace."""
+    S, C, N = 1, 130, 65
+    cont, nodes = _scenario(C, N, 7)
+    rp, col, hd = O.gen_dag(SEED, 20, 10, 5, 40, 3)
+    first = planner.place_batch(S, C, N, cont, nodes)
+    assert planner.place_path()["ran"]
+    planner.set_option("level_small", 0)
+    try:
+        for reuse, level_at in ((planner.levelize, 0), (planner.plan_stage, 1)):
+            assert np.array_equal(reuse(rp, col, hd)[level_at], O.levelize(rp, col, hd)[0])
+            assert not planner.place_path()["ran"]
+            again = planner.place_batch(S, C, N, cont, nodes)
+            assert planner.place_path()["ran"]
+            for x, y in zip(first[:3] + first[3], again[:3] + again[3]):
+                assert np.array_equal(x, y)
+    finally:
+        planner.set_option("level_small")
+
+
 STAGE_KDL = """
 project "demo"
 %(servers)s
