@@ -168,6 +168,11 @@ __device__ __forceinline__ void g_st(uint32_t *p, uint32_t v) {
 __device__ __forceinline__ void g_touch(const uint32_t *p) {
     (void)__hip_atomic_load(const_cast<uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
+// an early request: the same plain global_load, which the optimiser leaves where it is written (an
+// ordinary load of a loop-carried value may be sunk towards its use)
+__device__ __forceinline__ uint32_t g_ld_w(const uint32_t *p) {
+    return __hip_atomic_load(const_cast<uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
 
 // Spin on an LDS word until pred holds; bounded, with a workgroup abort flag.
 template <class Pred>
@@ -311,11 +316,26 @@ constexpr uint32_t PF_MAX_NARROW = FPP_PF_MAX_NARROW, PF_MAX_WIDE = FPP_PF_MAX_W
 //     round trip (the gathers) instead of two (slot, then gathers).  Only slots below a head
 //     already seen are looked at (an unpublished slot holds stale positions); no extra poll
 //  2  1, and the sorted SoA lines the next batch will read are touched (loads nothing reads)
+//  3  the packed one-wave kernels (bigp, w12p) double-buffer the batch's fields in registers: right
+//     after a batch's demands are packed, the NEXT batch's cpu / mem / req / conf (segment 0: and idx)
+//     are requested into loop-carried registers -- the gathers at the looked-ahead positions, and the
+//     slot words one slot further on (two slots deep) -- and waited for once, after the group loop and
+//     ahead of the batch's stores.  Every other kernel compiles as with 1
+//  4  the same registers, requested after the group loop (still ahead of the batch's stores) and
+//     waited for at the next top: nothing new is live across the group loop
 // Config-4 FFD, 0 against 1: 11.32-11.34 against 11.19-11.21 ms (seven alternating runs), 2048 scenarios
 // 7.66-7.72 against 7.57-7.64 ms; 0 against 2, in another call: 11.17-11.21 against 12.37-12.41 ms, 2048
 // scenarios 7.64-7.67 against 8.30-8.32 ms (profiles/r10b_lookahead_ab.jsonl).
+// 1 against 3, both with direct tickets: 10.57-10.58 against 10.18-10.20 ms, 2048 scenarios 7.26-7.29 against
+// 6.90-6.94 ms; 1 against 4: 10.57-10.58 against 10.76-10.77 ms, 2048 scenarios 7.26-7.29 against 7.33-7.35 ms
+// (five alternating runs each, profiles/r11b_lookahead3_ab.jsonl call c).
 #ifndef FPP_LOOKAHEAD
-#define FPP_LOOKAHEAD 1
+#define FPP_LOOKAHEAD 3
+#endif
+// Workgroup tickets with lag == S mapped directly (the kernel's start-up); 0: every lag draws tickets
+// in a loop until one names a scenario (config-4 FFD 11.05-11.07 against 10.57-10.58 ms with them, same file)
+#ifndef FPP_DIRECT_TICKETS
+#define FPP_DIRECT_TICKETS 1
 #endif
 // the systolic group fill (fp_pipe_sys.h) is compiled for stages of at most this many groups
 constexpr uint32_t SYS_MAX_G = 4;
@@ -555,11 +575,19 @@ k_ffd_pipe(const PipeArgs a_arg) {
     if (threadIdx.x == 0) {
         const uint32_t total = (a.S + (B - 1) * a.lag) * B;
         uint32_t t;
-        while (true) {
-            t = atomicAdd(a.ticket, 1u);
-            if (t >= total) { t = 0xFFFFFFFFu; break; }
-            const uint32_t r = t / B, bb = t % B;
-            if (r >= bb * a.lag && r - bb * a.lag < a.S) break;
+        if (FPP_DIRECT_TICKETS && a.lag == a.S) {
+            // phased segments: round r holds exactly one valid ticket, segment r / S of scenario r % S,
+            // so the v-th workgroup to draw takes round v -- the start order of the loop below, without
+            // its B - 1 skipped tickets (dependent atomics on one address) per workgroup
+            const uint32_t v = atomicAdd(a.ticket, 1u);
+            t = v < a.S * B ? v * B + v / a.S : 0xFFFFFFFFu;
+        } else {
+            while (true) {
+                t = atomicAdd(a.ticket, 1u);
+                if (t >= total) { t = 0xFFFFFFFFu; break; }
+                const uint32_t r = t / B, bb = t % B;
+                if (r >= bb * a.lag && r - bb * a.lag < a.S) break;
+            }
         }
         CNT[4] = t;
     }
@@ -668,9 +696,55 @@ k_ffd_pipe(const PipeArgs a_arg) {
     uint32_t ihead_seen = 0;  // last head read from the upstream link
     // look-ahead on the input link (FPP_LOOKAHEAD): slot itail's count and position words, requested
     // one batch early (la_ok: they were; else the loop top loads them as without look-ahead)
-    constexpr uint32_t LA = BLK == 64 ? FPP_LOOKAHEAD : 0;
+    constexpr uint32_t LA = BLK == 64 ? (FPP_LOOKAHEAD >= 3 ? 1 : FPP_LOOKAHEAD) : 0;
     [[maybe_unused]] uint32_t la_n = 0, la_pos = 0;
     [[maybe_unused]] bool la_ok = false;
+    // register double buffer of the packed one-wave kernels (FPP_LOOKAHEAD 3 / 4): the next batch's
+    // fields, requested one batch early into nf_* (nf_ok: they were; else the loop top loads them as
+    // before).  DB_EARLY (3): requested after the pack, and the look-ahead pair describes the slot
+    // AFTER the next one; else (4) requested after the group loop, the pair as with look-ahead 1.
+    // nf_n is the next slot's count.  Only the 12-group kernels (bigp, w12p): the wider ones were not
+    // measured
+    constexpr bool DB = BLK == 64 && G == 12 && PK && FPP_LOOKAHEAD >= 3, DB_EARLY = DB && FPP_LOOKAHEAD == 3;
+    [[maybe_unused]] uint32_t nf_cpu = 0, nf_mem = 0, nf_req = 0, nf_conf = 0, nf_idx = 0, nf_n = 0;
+    [[maybe_unused]] bool nf_ok = false;
+    // DB_EARLY: the pair's next values, in flight across the group loop.  Loading them into the pair
+    // itself, behind a copy of its positions into nf_idx, made bigp wait for the first two gathers
+    // right after their issue (s_waitcnt vmcnt(4)); the pair moves on after the wait instead
+    [[maybe_unused]] uint32_t la2_n = 0, la2_pos = 0;
+    constexpr int VMCNT0 = 0x0F70;  // s_waitcnt vmcnt(0) alone (gfx9 encoding: expcnt 7, lgkmcnt 15)
+    // Request the next batch.  Branch-free but for the uniform link / segment-0 choice, with selects
+    // for the addresses, so that the loads write the carried registers themselves; a
+    // macro, because as a lambda (variables captured by reference) nf_idx ended up in scratch.
+    // A link segment gathers at the looked-ahead positions; END, a lane past the count or a pair that
+    // was not covered reads position 0 of the scenario's own rows, which nothing uses.  Segment 0
+    // requests rows k0 + lane (k0 already advanced), clamped at C.
+#define FPP_REQUEST_NEXT()                                                                              \
+    do {                                                                                                \
+        uint32_t off_;                                                                                  \
+        if (g_in) {                                                                                     \
+            const uint32_t tn_ = __builtin_amdgcn_readfirstlane(la_n);                                  \
+            off_ = (la_ok && !(tn_ & END) && lane < tn_) ? la_pos & pmask : 0u;                         \
+            nf_n = tn_;                                                                                 \
+            nf_ok = la_ok;                                                                              \
+        } else {                                                                                        \
+            off_ = min(k0 + lane, C - 1u);                                                              \
+            nf_ok = true;                                                                               \
+        }                                                                                               \
+        const size_t o_ = cb + off_;                                                                    \
+        nf_cpu = g_ld_w(a.s_cpu + o_);                                                                  \
+        nf_mem = g_ld_w(a.s_mem + o_);                                                                  \
+        nf_req = g_ld_w(a.s_req + o_);                                                                  \
+        nf_conf = g_ld_w(a.s_conf + o_);                                                                \
+        if (!g_in) nf_idx = g_ld_w(a.s_idx + o_);                                                       \
+        else if (!DB_EARLY) nf_idx = la_pos;                                                            \
+        if (DB_EARLY && g_in) { /* two slots deep: the pair held slot itail's words, the next batch's */ \
+            la_ok = itail + 1u < ihead_seen;                                                            \
+            const uint32_t *sn_ = la_ok ? gin_data + (size_t)GSLOT(itail + 1u) * LSLOT : a.s_idx + cb;  \
+            la2_n = g_ld(sn_);                                                                          \
+            la2_pos = g_ld(sn_ + (la_ok ? 64u + lane : 0u));                                            \
+        }                                                                                               \
+    } while (0)
     // full slots written but not yet published (global link): the head store and the wait for
     // the slot stores before it (s_waitcnt vmcnt(0)) are paid once per a.publish slots; the end
     // of the stream publishes the rest
@@ -686,6 +760,8 @@ k_ffd_pipe(const PipeArgs a_arg) {
     unsigned long long sp_first = 0;
 #endif
     bool alive = true;
+    // nothing of the tile set-up stays pending into the loop
+    if constexpr (DB) __builtin_amdgcn_s_waitcnt(VMCNT0);
     while (alive) {
         if (prio == 2u) __builtin_amdgcn_s_setprio(0);  // polls / spins at the lowest priority
         ck_a = STAT_CLK();
@@ -734,7 +810,10 @@ k_ffd_pipe(const PipeArgs a_arg) {
             // the count is wave-uniform: say so, or the loop exit below reads as divergent and every
             // loop-carried counter of the kernel is kept (and spilled) in VGPRs
             uint32_t n, pos;
-            if (LA && la_ok) {  // requested with the previous batch's gathers
+            if (DB && nf_ok) {  // the whole batch was requested one batch early
+                n = nf_n;
+                pos = nf_idx;
+            } else if (LA && !DB_EARLY && la_ok) {  // requested with the previous batch's gathers
                 n = __builtin_amdgcn_readfirstlane(la_n);
                 pos = la_pos;
             } else {
@@ -743,25 +822,45 @@ k_ffd_pipe(const PipeArgs a_arg) {
             }
             if (n & END) break;
             valid = lane < n;
-            if (valid) {
-                idx = pos;  // the packed s_idx word (position | buckets)
-                const uint32_t p = pos & pmask;
-                cpu = a.s_cpu[cb + p];
-                mem = a.s_mem[cb + p];
-                req = a.s_req[cb + p];
-                conf = a.s_conf[cb + p];
+            if (DB && nf_ok) {  // lanes past the count hold position 0's fields: zero, as below
+                idx = valid ? pos : 0u;
+                cpu = valid ? nf_cpu : 0u;
+                mem = valid ? nf_mem : 0u;
+                req = valid ? nf_req : 0u;
+                conf = valid ? nf_conf : 0u;
+            } else {
+                if (valid) {
+                    idx = pos;  // the packed s_idx word (position | buckets)
+                    const uint32_t p = pos & pmask;
+                    cpu = a.s_cpu[cb + p];
+                    mem = a.s_mem[cb + p];
+                    req = a.s_req[cb + p];
+                    conf = a.s_conf[cb + p];
+                }
+                // the rare path drains here: a load left pending on it (no valid lane) would make the
+                // compiler wait with vmcnt(0), behind the previous batch's stores, on the carried path too
+                if constexpr (DB) __builtin_amdgcn_s_waitcnt(VMCNT0);
             }
             itail++;
         } else if (w == 0) {
             if (k0 >= C) break;
             const uint32_t i = k0 + lane;
             valid = i < C;
-            if (valid) {
-                cpu = a.s_cpu[cb + i];
-                mem = a.s_mem[cb + i];
-                req = a.s_req[cb + i];
-                conf = a.s_conf[cb + i];
-                idx = a.s_idx[cb + i];
+            if (DB && nf_ok) {  // rows requested one batch early (clamped at C: zero past it, as below)
+                cpu = valid ? nf_cpu : 0u;
+                mem = valid ? nf_mem : 0u;
+                req = valid ? nf_req : 0u;
+                conf = valid ? nf_conf : 0u;
+                idx = valid ? nf_idx : 0u;
+            } else {
+                if (valid) {
+                    cpu = a.s_cpu[cb + i];
+                    mem = a.s_mem[cb + i];
+                    req = a.s_req[cb + i];
+                    conf = a.s_conf[cb + i];
+                    idx = a.s_idx[cb + i];
+                }
+                if constexpr (DB) __builtin_amdgcn_s_waitcnt(VMCNT0);  // as in the link branch
             }
             const bool cyc = valid && (idx & CYC);
             if (cyc) {  // CYCLE member, or screened out by stage 2 (NOFIT): s_req holds the reason
@@ -806,7 +905,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
             itail++;
             lds_rel(&ictl[1], itail);
         }
-        if constexpr (LA != 0) {
+        if constexpr (LA != 0 && !DB_EARLY) {
             // The next slot of the input link, requested in the same burst as the gathers above and not
             // waited for before the next loop top.  Only if a head already seen covers it: an
             // unpublished slot holds stale words, and nothing here polls (the next top does, as without
@@ -864,6 +963,13 @@ k_ffd_pipe(const PipeArgs a_arg) {
         // packed demands (this batch's values are multiples of the shifts: exact)
         const uint32_t cw = PK ? pk_pack(cpu, mem, sc_c, sc_m) : 0u;
         const uint32_t qw = PK ? pk_pack(qc, qm, sc_c, sc_m) : 0u;
+        // cpu and mem are dead from here on in a packed kernel (the all-zero test is taken first): the
+        // next batch is requested into registers that stay live across the prescan and the group loop
+        [[maybe_unused]] bool zero_early = false;
+        if constexpr (DB_EARLY) {
+            zero_early = valid && (cpu | mem | req | conf) == 0u;
+            FPP_REQUEST_NEXT();
+        }
         // every mask load is issued before the first use (no per-group LDS round trip)
         const uint32_t oc = kc * 2, om = km * 2 + 1;
         constexpr bool prescan_skip = G > SYS_MAX_G;
@@ -897,7 +1003,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
                 }
             }
         }
-        const bool zero = valid && (cpu | mem | req | conf) == 0u;
+        const bool zero = DB_EARLY ? zero_early : valid && (cpu | mem | req | conf) == 0u;
         uint64_t todo = __builtin_amdgcn_ballot_w64(cand != 0 && !zero);
         uint64_t placed = 0;
         uint32_t my_assign = FP_NONE;
@@ -958,6 +1064,19 @@ k_ffd_pipe(const PipeArgs a_arg) {
         // a placed container's reason is OK by definition: k_unsort derives it from the assignment, so
         // the pipeline stores only the node (reasons are written for the unplaced: CYCLE / screened
         // NOFIT in segment 0, NOFIT at the last stage)
+        if constexpr (DB_EARLY) {
+            // the one wait for the next batch's fields, ahead of this batch's stores: the requests are a
+            // prescan and a group loop old, and only the pair's two loads are younger
+            asm volatile("" : "+v"(nf_cpu), "+v"(nf_mem), "+v"(nf_req), "+v"(nf_conf), "+v"(nf_idx), "+v"(la2_n),
+                         "+v"(la2_pos));
+            if (g_in) {  // the next batch's positions are the pair's, and the pair moves on
+                nf_idx = la_pos;
+                la_n = la2_n;
+                la_pos = la2_pos;
+            }
+        } else if constexpr (DB) {
+            FPP_REQUEST_NEXT();  // ahead of the stores, waited for at the next top
+        }
         if ((placed >> lane) & 1ull) a.assign[cb + (idx & pmask)] = my_assign;
 #ifdef FP_PIPE_STATS
         if (s == 0 && lane == 0 && tl_idx < (uint32_t)TL_B && b * W + w < 16) {
