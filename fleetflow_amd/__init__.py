@@ -4,8 +4,8 @@ The product is libfleetplace.so (HIP, gfx950) behind include/fleetplace.h;
 this package is its host-side mirror of the reference interface.
 """
 from .planner import NONE, DevBatch, Planner  # noqa: F401
-from .flow import (Flow, PlacementPolicy, Plan, Server, Service, Stage, order_by_dependencies,  # noqa: F401
-                   plan_stage, resolve_target_server)
+from .flow import (DrainReport, Flow, PlacementPolicy, Plan, Server, Service, Stage, drain_stage,  # noqa: F401
+                   order_by_dependencies, plan_stage, resolve_target_server)
 
-__all__ = ["NONE", "DevBatch", "Planner", "Flow", "PlacementPolicy", "Plan", "Server", "Service", "Stage",
-           "order_by_dependencies", "plan_stage", "resolve_target_server"]
+__all__ = ["NONE", "DevBatch", "Planner", "DrainReport", "Flow", "PlacementPolicy", "Plan", "Server", "Service", "Stage",
+           "drain_stage", "order_by_dependencies", "plan_stage", "resolve_target_server"]

@@ -38,6 +38,10 @@ WHY_CORDON, WHY_CPU, WHY_MEM, WHY_LABEL, WHY_CONFLICT = 1, 2, 4, 8, 16
 EXPLAIN_FAIL, EXPLAIN_ONLY, EXPLAIN_FEASIBLE, EXPLAIN_ALL, EXPLAIN_MISSING, EXPLAIN_NEAR = 0, 5, 10, 11, 12, 13
 EXPLAIN_WORDS = 16
 EXPLAIN_HIST_MIXED, EXPLAIN_HIST_FITS, EXPLAIN_HIST_SELECTED, EXPLAIN_HIST_WORDS = 5, 6, 7, 8
+# drain what-if sweep (SPEC.md 2.11): the word indices of a candidate's summary row, and their names in order
+DRAIN_EVICTED, DRAIN_STRANDED, DRAIN_STRANDED_CPU, DRAIN_STRANDED_MEM = 0, 1, 2, 3
+DRAIN_TARGETS, DRAIN_FIRST_STRANDED, DRAIN_NODES, DRAIN_WORDS = 4, 5, 6, 8
+DRAIN_FIELDS = ("evicted", "stranded", "stranded_cpu", "stranded_mem", "targets", "first_stranded", "nodes")
 # context options (fleetplace.h enum fp_option); FP_OPT_AUTO = the production default
 # ("segsort" is ignored by the library and kept for ABI stability)
 FP_OPT_AUTO = -1
@@ -139,6 +143,10 @@ SIGNATURES = {
     "fp_explain_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), ct.c_uint32, u32p, u32p]),
     "fp_dev_explain": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, ct.c_uint32, ct.c_uint32, vp]),
     "fp_dev_explain_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), ct.c_uint32, vp, vp]),
+    "fp_drain_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, u32p, ct.c_uint32,
+                                  ct.c_uint32, ct.c_uint32, u32p, u32p, u8p, u32p]),
+    "fp_dev_drain_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, vp, ct.c_uint32,
+                                      ct.c_uint32, ct.c_uint32, vp, vp, vp, vp]),
     "fp_dev_argmin_cost": (ct.c_int, [vp, vp, ct.c_uint32, vp]),
     "fp_dev_gen_batch": (ct.c_int, [vp, ct.c_uint64, ct.POINTER(FpBatch), ct.c_uint32]),
 }

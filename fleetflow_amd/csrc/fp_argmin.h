@@ -1,0 +1,47 @@
+// fp_argmin.h -- the block argmin over 64-bit placement keys that the scored placer (fp_policy.hip,
+// SPEC.md 2.6) and the drain sweep (fp_drain.hip, SPEC.md 2.11) share: the 2.6 key layout and the
+// cross-lane helpers.  Device code only; every function is forced inline.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace fpd {
+
+constexpr uint64_t KEY_NONE = ~0ull;    // an infeasible node
+constexpr uint32_t KEY_NODE_BITS = 26;  // key = pref_miss << 58 | primary << 26 | node
+
+__device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+// wave-uniform value of lane `l` (l uniform): the record broadcast
+__device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t l) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
+}
+
+// Cross-lane min of the 64-bit keys on the VALU (DPP), not through the LDS crossbar: with 16 waves a
+// block, 12 ds_bpermute a wave and container kept the LDS pipe busier than the key evaluation.
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+    return ((uint64_t)hi << 32) | lo;
+}
+// the min over each row of 16 lanes, in every lane of the row (all 64 lanes active).  min is idempotent,
+// so the mirrors serve as butterflies: quads, then the two quads of a half row, then the two halves
+__device__ __forceinline__ uint64_t row_min64(uint64_t v) {
+    v = min64(v, dpp64<0xB1>(v));   // quad_perm [1, 0, 3, 2]
+    v = min64(v, dpp64<0x4E>(v));   // quad_perm [2, 3, 0, 1]
+    v = min64(v, dpp64<0x141>(v));  // row_half_mirror
+    v = min64(v, dpp64<0x140>(v));  // row_mirror
+    return v;
+}
+__device__ __forceinline__ uint64_t lane64(uint64_t v, int l) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+}
+// the min over the wave, uniform: the four row mins meet in scalar registers
+__device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
+    v = row_min64(v);
+    return min64(min64(lane64(v, 0), lane64(v, 16)), min64(lane64(v, 32), lane64(v, 48)));
+}
+
+}  // namespace fpd

@@ -872,3 +872,56 @@ extern "C" int fp_explain_batch(fp_ctx *c, const fp_batch *b, uint32_t reason_ma
     const OutCopy o[] = {{hist_out, dhist, S * FP_EXPLAIN_HIST_WORDS * 4}};
     return copy_back_all(c, o, 1);
 }
+
+// drain what-if sweep (SPEC.md 2.11, fp_drain.hip)
+extern "C" int fp_dev_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                  const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
+                                  const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
+                                  uint32_t *summary_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_drain_sweep_impl(c, cs, ns, assign, group, n_cand, strategy, preferred_labels,
+                                                  node_count, assign_out, reason_out, summary_out));
+}
+
+extern "C" int fp_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                              const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
+                              const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
+                              uint32_t *summary_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const size_t C = cs->n, N = ns->n, R = (size_t)n_cand * FP_DRAIN_WORDS;
+    if (N > FP_POLICY_MAX_NODES || n_cand > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
+    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out || !reason_out))
+        return FP_EINVAL;
+    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !group))
+        return FP_EINVAL;
+    if (n_cand && !summary_out) return FP_EINVAL;
+    if (C && assign_out == assign) return FP_EINVAL;
+    for (size_t n = 0; n < N; ++n)
+        if (group[n] >= n_cand && group[n] != FP_NONE) return FP_EINVAL;
+    for (size_t i = 0; i < C; ++i)
+        if (assign[i] >= N && assign[i] != FP_NONE) return FP_EINVAL;
+    if (C == 0 && n_cand == 0) return FP_OK;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    int rc = fp_stage_reserve(c, C * 25 + N * 25 + R * 4 + 20 * 256);
+    if (rc) return rc;
+    fp_stage_reset(c);
+    fp_containers dc;
+    fp_nodes dn;
+    stage_tables(c, cs, ns, &dc, &dn, &rc);
+    const uint32_t *dassign = stage_in(c, assign, C, &rc);
+    const uint32_t *dgroup = stage_in(c, group, N, &rc);
+    const uint32_t *dcount = stage_in(c, node_count, N, &rc);
+    uint32_t *dout = stage_out<uint32_t>(c, C, &rc);
+    uint8_t *dreason = stage_out<uint8_t>(c, C, &rc);
+    uint32_t *drows = stage_out<uint32_t>(c, R, &rc);
+    if (rc) return rc;
+    rc = fp_dev_drain_sweep_impl(c, &dc, &dn, dassign, dgroup, n_cand, strategy, preferred_labels, dcount, dout, dreason,
+                                 drows);
+    if (rc) return rc;
+    const OutCopy o[] = {{assign_out, dout, C * 4}, {reason_out, dreason, C}, {summary_out, drows, R * 4}};
+    return copy_back_all(c, o, 3);
+}

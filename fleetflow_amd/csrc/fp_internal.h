@@ -162,6 +162,13 @@ struct fp_policy_opts {
 // every pointer is device memory
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy_opts &o);
 
+// drain what-if sweep (fp_drain.hip, SPEC.md 2.11); every pointer is device memory.  group and assign values
+// out of range are found on the device (FP_EINVAL in the context's error word, nothing written)
+int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                            const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred,
+                            const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
+                            uint32_t *summary_out);
+
 // tile-pipeline FFD (fp_pipe.hip)
 bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint32_t *W_out, uint32_t *B_out,
                   size_t *lds_out);

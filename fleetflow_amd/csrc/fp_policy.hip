@@ -76,14 +76,20 @@
 // N <= FP_POLICY_MAX_NODES (1024 threads x 8 nodes): past one workgroup the argmin per dependent
 // container would need a grid-wide synchronisation per placement.
 #include "fp_internal.h"
+#include "fp_argmin.h"
 #include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace {
 
-constexpr uint64_t KEY_NONE = ~0ull;
-constexpr uint32_t KEY_NODE_BITS = 26;  // key = pref_miss << 58 | primary << 26 | node
+// the 2.6 key layout and the 64-bit cross-lane min, shared with the drain sweep (fp_drain.hip)
+using fpd::KEY_NONE;
+using fpd::KEY_NODE_BITS;  // key = pref_miss << 58 | primary << 26 | node
+using fpd::bcast;
+using fpd::min64;
+using fpd::row_min64;
+using fpd::wave_min64;
 // SPEC.md 2.8, the FB variants: key = hop << 61 | pref_miss << 55 | primary << 23 | node
 constexpr uint32_t KEY_NODE_BITS_FB = 23;
 constexpr uint32_t KEY_HOP_SHIFT = 61;
@@ -189,41 +195,7 @@ struct PolicyArgs {
     uint8_t *quota_why;                           // [S][C] or null: the mask of the blocking dimensions
 };
 
-__device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
-// wave-uniform value of lane `l` (l uniform): the record broadcast
-__device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
-
-// Cross-lane min of the 64-bit keys on the VALU (DPP), not through the LDS crossbar: with 16 waves a
-// block, 12 ds_bpermute a wave and container kept the LDS pipe busier than the key evaluation.
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp64(uint64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
-    return ((uint64_t)hi << 32) | lo;
-}
-// the min over each row of 16 lanes, in every lane of the row (all 64 lanes active).  min is idempotent,
-// so the mirrors serve as butterflies: quads, then the two quads of a half row, then the two halves
-__device__ __forceinline__ uint64_t row_min64(uint64_t v) {
-    v = min64(v, dpp64<0xB1>(v));   // quad_perm [1, 0, 3, 2]
-    v = min64(v, dpp64<0x4E>(v));   // quad_perm [2, 3, 0, 1]
-    v = min64(v, dpp64<0x141>(v));  // row_half_mirror
-    v = min64(v, dpp64<0x140>(v));  // row_mirror
-    return v;
-}
-__device__ __forceinline__ uint64_t lane64(uint64_t v, int l) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-}
-// the min over the wave, uniform: the four row mins meet in scalar registers
-__device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
-    v = row_min64(v);
-    return min64(min64(lane64(v, 0), lane64(v, 16)), min64(lane64(v, 32), lane64(v, 48)));
-}
-
-// the same over 32-bit values (the domain counts of SPEC.md 2.7)
+// the min of fp_argmin.h over 32-bit values (the domain counts of SPEC.md 2.7)
 template <int CTRL>
 __device__ __forceinline__ uint32_t dpp32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);

@@ -13,6 +13,8 @@ the same:
   computed by GPU FFD placement over the stage's servers with unconstrained
   capacity (every container lands on node 0 == ``servers.first()``).
 * ``levelize_stage`` / ``plan_stage``: the new planner outputs (SPEC.md 2).
+* ``drain_stage``: which servers, or zones, of a stage that runs as a plan says can be taken out
+  (SPEC.md 2.11; the `drain` scheduling state of controlplane model.rs:435-442).
 
 Strings never cross the C ABI: names are mapped to u32 ids in stage order here.
 """
@@ -188,6 +190,9 @@ class Server:
     schedulable: bool = True
     provider: str = ""
     plan: str | None = None
+    # scheduling == "drain" (model.rs:435-442): existing placements are to leave as well.  Such a server is
+    # unschedulable like a cordoned one; ``drain_stage`` evacuates the servers that carry the flag
+    draining: bool = False
 
 
 @dataclass
@@ -572,6 +577,126 @@ def plan_stage(flow: Flow, stage_name: str, planner: Planner | None = None,
         if pol.quota is not None:
             plan.quota, plan.quota_used, plan.quota_why = pol.quota, quota_after, quota_why
     return plan
+
+
+@dataclass
+class DrainCandidate:
+    """One candidate of a drain sweep (SPEC.md 2.11): the servers taken out together, where their services
+    go and which are left without a server."""
+    name: str                              # the server's slug, "key=value" of a topology domain, or slugs joined by ","
+    servers: list[str]                     # the candidate's servers (slugs, node order)
+    moves: list[tuple[str, str, str]]      # (service, from, to) in visiting order (cpu desc, mem desc, stage order)
+    stranded: list[str]                    # services no remaining server takes, in visiting order
+    evicted: int = 0                       # services running on the candidate
+    stranded_cpu_m: int = 0                # what the stranded services ask for in sum
+    stranded_mem_mib: int = 0
+    targets: int = 0                       # distinct servers that receive a service
+
+
+@dataclass
+class DrainReport:
+    """``drain_stage``'s answer: one DrainCandidate per candidate, every one computed independently from the
+    same live state, under the strategy and preferred labels named here."""
+    stage: str
+    by: str | None = None                  # the topology key the candidates are the values of; None = servers
+    strategy: str | None = None
+    preferred: list[str] = field(default_factory=list)
+    candidates: list[DrainCandidate] = field(default_factory=list)
+
+
+def live_tables(flow: Flow, stage_name: str, plan: Plan, policy: PlacementPolicy | None = None):
+    """The live state ``plan`` describes, as the inputs of a drain sweep (SPEC.md 2.11): the stage's tables
+    rebuilt as ``plan_stage`` builds them, with every assigned service's request deducted on its server.
+    Returns (names, nodes, cont, live, assign, node_count, strategy, preferred_mask): ``live`` = (cpu_free,
+    mem_free, labels, conflict_used, schedulable) lists, ``assign[v]`` the node index of service ``names[v]``
+    or NONE, ``node_count[n]`` the services on server n.  Strategy and preferred labels are ``policy``'s, or
+    without one those the plan was made under.  A plan that names a server the stage does not have is a
+    ValueError."""
+    stage = flow.stages[stage_name]
+    names = list(dict.fromkeys(stage.services))
+    nodes = _server_nodes(flow, stage.servers)
+    strategy = policy.strategy if policy is not None else plan.strategy
+    preferred = policy.preferred if policy is not None else list(plan.preferred)
+    cont, (cf, mf, lab, cu, sch) = _stage_tables(names, flow, nodes, preferred)
+    pmask = _stage_labels(names, flow, nodes, preferred).mask(preferred)
+    index = {nd.slug: n for n, nd in enumerate(nodes)}
+    assign, count = [NONE] * len(names), [0] * len(nodes)
+    for v, name in enumerate(names):
+        slug = plan.assignment.get(name)
+        if slug is None:
+            continue
+        if slug not in index:
+            raise ValueError(f"plan for stage '{stage_name}' runs '{name}' on '{slug}', which is no server of the stage")
+        n = index[slug]
+        assign[v] = n
+        cf[n] = (cf[n] - cont[0][v]) & U32_MAX
+        mf[n] = (mf[n] - cont[1][v]) & U32_MAX
+        cu[n] |= cont[3][v]
+        count[n] += 1
+    return names, nodes, cont, (cf, mf, lab, cu, sch), assign, count, strategy, pmask
+
+
+def drain_stage(flow: Flow, stage_name: str, plan: Plan, by: str | None = None, servers: list[str] | None = None,
+                planner: Planner | None = None, policy: PlacementPolicy | None = None) -> DrainReport:
+    """"Can this server, or this whole zone, be taken out?" for a stage that runs as ``plan`` says (SPEC.md
+    2.11; the `drain` scheduling state of model.rs:435-442): one ``Planner.drain_sweep`` over the live
+    tables of ``live_tables``.  The candidates are
+
+    * ``servers=[slugs]``: those servers together, one candidate;
+    * ``by="region"`` (any topology key): one candidate per value of the key among the stage's servers
+      (``spread_domains``; a server without the key belongs to none);
+    * neither: the servers flagged ``draining`` together when the stage has any (what the registry says is
+      leaving), otherwise each server on its own.
+
+    Every candidate is computed independently from the same live state: its services are visited in the
+    order (cpu desc, mem desc, stage order) and go to the remaining schedulable servers under the strategy
+    and preferred labels of ``policy`` or, without one, of the policy the plan was made under.  The policy's
+    spread constraint, fallback chain and quota are not applied to moves."""
+    p = planner or default_planner()
+    names, nodes, cont, live, assign, count, strategy, pmask = live_tables(flow, stage_name, plan, policy)
+    pol_pref = policy.preferred if policy is not None else list(plan.preferred)
+    report = DrainReport(stage_name, None, strategy, pol_pref)
+    if not nodes:
+        return report
+    slugs = [nd.slug for nd in nodes]
+    if servers is None and by is None and any(nd.draining for nd in nodes):
+        servers = [nd.slug for nd in nodes if nd.draining]
+    if servers is not None:
+        unknown = [s for s in servers if s not in slugs]
+        if unknown:
+            raise ValueError(f"drain: {unknown} are no servers of stage '{stage_name}'")
+        chosen = set(servers)
+        group = [0 if s in chosen else NONE for s in slugs]
+        cand_names = [",".join(s for s in slugs if s in chosen)]
+    elif by is not None:
+        report.by = by
+        domain, has_key = spread_domains(nodes, by)
+        group = [d if k else NONE for d, k in zip(domain, has_key)]
+        cand_names = [""] * (max((g for g in group if g != NONE), default=-1) + 1)
+        prefix = by + "="
+        for nd, g in zip(nodes, group):
+            if g != NONE and not cand_names[g]:
+                cand_names[g] = next(lab for lab in nd.labels if lab.startswith(prefix))
+    else:
+        group = list(range(len(nodes)))
+        cand_names = slugs
+    n_cand = len(cand_names)
+    out, _, summary = p.drain_sweep(cont, live, assign, group, n_cand, strategy if strategy is not None else 0, pmask,
+                                    count)
+    from ._lib import DRAIN_EVICTED, DRAIN_STRANDED_CPU, DRAIN_STRANDED_MEM, DRAIN_TARGETS
+    evictees: list[list[int]] = [[] for _ in range(n_cand)]
+    for v, n in enumerate(assign):
+        if n != NONE and group[n] != NONE:
+            evictees[group[n]].append(v)
+    for k, name in enumerate(cand_names):
+        evictees[k].sort(key=lambda v: (-cont[0][v], -cont[1][v], v))  # the visiting order
+        moves = [(names[v], slugs[assign[v]], slugs[int(out[v])]) for v in evictees[k] if int(out[v]) != NONE]
+        stranded = [names[v] for v in evictees[k] if int(out[v]) == NONE]
+        row = [int(x) for x in summary[k]]
+        report.candidates.append(DrainCandidate(name, [s for s, g in zip(slugs, group) if g == k], moves, stranded,
+                                                row[DRAIN_EVICTED], row[DRAIN_STRANDED_CPU], row[DRAIN_STRANDED_MEM],
+                                                row[DRAIN_TARGETS]))
+    return report
 
 
 def resolve_target_server(flow: Flow, stage_name: str, planner: Planner | None = None) -> str | None:

@@ -11,6 +11,10 @@ rejected NOFIT or SKEW; the key is absent when there is none.  A plan made under
 cap is none) and ``quota_why``: the dimensions that refused each service rejected QUOTA.  Both keys are
 absent without a quota.
 
+``format_drain_report`` prints a drain sweep (SPEC.md 2.11, ``flow.drain_stage``), one block per candidate,
+and ``drain_report_to_json`` / ``drain_report_from_json`` carry it as
+``{stage, by, placement: {strategy, preferred}, candidates: [{name, servers, moves, stranded, ...}]}``.
+
 ``format_up_dry_run`` / ``format_deploy_dry_run`` reproduce the reference's
 ``fleet up --dry-run`` (crates/fleetflow/src/commands/up.rs:57-136) and
 ``fleet deploy --dry-run`` (crates/fleetflow/src/commands/deploy.rs:14-100)
@@ -28,7 +32,7 @@ import json
 from dataclasses import asdict
 
 from ._lib import QUOTA_NAMES
-from .flow import U32_MAX, WHY_NAMES, Flow, Plan, Why
+from .flow import U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, Plan, Why
 from .parser import FlowError
 
 
@@ -79,6 +83,33 @@ def plan_from_json(text: str) -> Plan:
         plan.quota_used = tuple(q["used"][n] for n in QUOTA_NAMES) if q.get("used") is not None else None
         plan.quota_why = {k: list(v) for k, v in (d.get("quota_why") or {}).items()}
     return plan
+
+
+def format_drain_report(report: DrainReport) -> str:
+    """One line per candidate, ``drain <name>: <m> services move to <t> servers, <s> stranded``, with the
+    moves (``service: from -> to``) and the stranded services indented under it, in visiting order."""
+    lines = []
+    for c in report.candidates:
+        lines.append(f"drain {c.name}: {len(c.moves)} services move to {c.targets} servers, {len(c.stranded)} stranded")
+        lines += [f"  {svc}: {src} -> {dst}" for svc, src, dst in c.moves]
+        lines += [f"  {svc}: stranded" for svc in c.stranded]
+    return "\n".join(lines)
+
+
+def drain_report_to_json(report: DrainReport, indent: int | None = None) -> str:
+    d = {"stage": report.stage, "by": report.by,
+         "placement": {"strategy": report.strategy, "preferred": report.preferred},
+         "candidates": [asdict(c) for c in report.candidates]}
+    return json.dumps(d, ensure_ascii=False, indent=indent)
+
+
+def drain_report_from_json(text: str) -> DrainReport:
+    d = json.loads(text)
+    pol = d.get("placement") or {}
+    cands = [DrainCandidate(c["name"], list(c["servers"]), [tuple(m) for m in c["moves"]], list(c["stranded"]),
+                            c.get("evicted", 0), c.get("stranded_cpu_m", 0), c.get("stranded_mem_mib", 0),
+                            c.get("targets", 0)) for c in d.get("candidates") or []]
+    return DrainReport(d["stage"], d.get("by"), pol.get("strategy"), list(pol.get("preferred") or []), cands)
 
 
 def get_network_name(project: str, stage: str) -> str:

@@ -538,7 +538,89 @@ class Planner:
               "fp_explain_batch")
         return hist
 
+    def drain_sweep(self, cont, nodes, assign, group, n_cand, strategy=0, preferred=0, node_count=None):
+        """Drain what-if sweep (SPEC.md 2.11, fp_drain_sweep): ``nodes`` is the live table, ``assign`` [C] the
+        node each container runs on (NONE = not running), ``group`` [N] the candidate each node belongs to
+        (< ``n_cand``, NONE = none).  Every candidate's evictees are re-placed, independently and from the
+        same base state, on the schedulable nodes outside the candidate under ``strategy`` / ``preferred``
+        (SPEC.md 2.6) and ``node_count`` ([N] or None = zeros).  Inputs are not mutated.  Returns
+        (assign_out [C], reason [C], summary [n_cand, 8]); summary's word indices are _lib.DRAIN_*."""
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
+        asg, grp = _u32(assign), _u32(group)
+        nc = _u32(node_count) if node_count is not None else None
+        n_cand, strategy = int(n_cand), strategy_id(strategy)
+        self._need(asg.size == C, "assign must hold C entries")
+        self._need(grp.size == N, "group must hold N entries")
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
+        out = np.empty(C, np.uint32)
+        reason = np.empty(C, np.uint8)
+        summary = np.empty((n_cand, _lib.DRAIN_WORDS), np.uint32)
+        cs, ns = _pair(cont, nodes)
+        check(self._L.fp_drain_sweep(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(grp), n_cand,
+                                     strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(out), _arg(reason),
+                                     _arg(summary)), "fp_drain_sweep")
+        return out, reason, summary
+
+    def drain(self, cont, nodes, assign, drain_mask, strategy=0, preferred=0, node_count=None):
+        """Evacuate the nodes of ``drain_mask`` ([N], non-zero = drained) from a live plan: one drain_sweep
+        with a single candidate, and its moves applied on the host to copies of the node table and of the
+        counts (a move deducts the request on its target as SPEC.md 2.6 does; nothing is returned to the
+        drained nodes).  Returns (assign_after, reason, nodes_after, node_count_after, summary_row);
+        node_count_after starts from zeros without ``node_count``."""
+        cont, nodes = _tables(cont, nodes, None, None, True)
+        C, N = cont[0].size, nodes[0].size
+        asg = _u32(assign)
+        mask = np.ascontiguousarray(drain_mask).reshape(-1) != 0
+        self._need(asg.size == C, "assign must hold C entries")
+        self._need(mask.size == N, "drain_mask must hold N entries")
+        nc = _u32(node_count).copy() if node_count is not None else np.zeros(N, np.uint32)
+        self._need(nc.size == N, "node_count must hold N entries")
+        group = np.where(mask, 0, NONE).astype(np.uint32)
+        out, reason, summary = self.drain_sweep(cont, nodes, asg, group, 1, strategy, preferred, nc)
+        cf, mf, _, cu, _ = nodes
+        running = asg != NONE
+        moved = np.flatnonzero(running & mask[np.where(running, asg, 0)] & (out != NONE)) if N else np.empty(0, np.int64)
+        for c in moved:  # u32, wraps as the library's own update does
+            n = int(out[c])
+            cf[n:n + 1] -= cont[0][c]
+            mf[n:n + 1] -= cont[1][c]
+            cu[n] |= cont[3][c]
+            nc[n:n + 1] += np.uint32(1)
+        return out, reason, nodes, nc, summary[0]
+
     # -- device-pointer API -------------------------------------------------------------
+    def dev_drain_sweep(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t, strategy=0,
+                        preferred=0, count_t=None):
+        """fp_dev_drain_sweep on device tensors: ``cont_t`` = (cpu, mem, req, conf) [C] each and ``nodes_t`` =
+        (cpu_free, mem_free, labels, conflict_used [N] int32 storage, schedulable [N] uint8), ``assign_t``
+        [C], ``group_t`` [N], ``count_t`` [N] or None; out: ``assign_out_t`` [C], ``reason_t`` [C] uint8,
+        ``summary_t`` [n_cand * 8].  A group or assign value out of range is found on the device: nothing is
+        written and sync() raises FP_EINVAL."""
+        C, N, n_cand, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_cand), strategy_id(strategy)
+        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
+                   "every container tensor must hold C 32-bit entries")
+        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
+                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
+                   "every node tensor must hold N entries (schedulable N bytes)")
+        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
+        self._need(group_t.numel() == N and group_t.element_size() == 4, "group_t must hold N 32-bit entries")
+        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
+                   "count_t must hold N 32-bit entries")
+        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
+        self._need(assign_out_t.numel() == C and assign_out_t.element_size() == 4,
+                   "assign_out_t must hold C 32-bit entries")
+        self._need(reason_t.numel() == C and reason_t.element_size() == 1, "reason_t must hold C bytes")
+        self._need(summary_t.numel() == n_cand * _lib.DRAIN_WORDS and summary_t.element_size() == 4,
+                   "summary_t must hold n_cand * 8 32-bit entries")
+        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
+        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
+        self._dev(lambda: check(self._L.fp_dev_drain_sweep(
+            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(group_t), n_cand, strategy,
+            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(assign_out_t), _arg(reason_t), _arg(summary_t)),
+            "fp_dev_drain_sweep"))
+
     def dev_explain(self, db: "DevBatch", rows_t, sel_t=None, ignore_labels=0, scenario=0):
         """fp_dev_explain on one scenario of ``db`` (offset pointers, as dev_feasibility): ``rows_t``
         [M * 16] int32 storage, ``sel_t`` [M] container indices or None = every container.  A sel index

@@ -13,7 +13,8 @@ that slug order. The conversion is SPEC.md 4:
   crates/fleetflow-cloud-sakura/src/provider.rs:15-30), and a row with neither is
   unconstrained;
 * ``scheduling`` other than "schedulable" (cordon, drain) makes the node
-  unschedulable; None means schedulable (model.rs:516-518);
+  unschedulable; None means schedulable (model.rs:516-518); "drain" also sets
+  ``Server.draining``, which ``flow.drain_stage`` reads (SPEC.md 2.11);
 * labels become ``key=value`` strings (tier, region, class, arch, then the
   ``extras`` object), mapped to bits by ``flow.LabelDict``.
 """
@@ -82,7 +83,7 @@ def server_from_row(row: dict) -> Server:
     sched = row.get("scheduling")
     return Server(slug=row["slug"], cpu_m=cpu, mem_mib=mem, labels=server_labels(row.get("labels")),
                   schedulable=sched is None or sched == SCHEDULABLE, provider=row.get("provider", ""),
-                  plan=row.get("plan"))
+                  plan=row.get("plan"), draining=sched == DRAIN)
 
 
 def node_table(rows: list[dict]) -> list[Server]:

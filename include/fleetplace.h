@@ -26,6 +26,9 @@
  *   fp_dev_feasibility_batch <- new: the same sweep over many what-if scenarios
  *   fp_explain        <- new: per-cause diagnosis of unplaced containers (which 2.3 predicate fails where)
  *   fp_explain_batch  <- new: the same as one cause histogram per what-if scenario
+ *   fp_drain_sweep    <- new: evacuate each server, or each topology domain, from a live plan: the `drain`
+ *                        scheduling state, under which existing placements leave as well (`cordon` only
+ *                        stops new ones)  crates/fleetflow-controlplane/src/model.rs:435-442
  *
  * Conventions
  *   - All buffers are caller-owned; no allocation crosses the ABI.
@@ -338,6 +341,32 @@ int fp_explain(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const
  * state and reason; writes only hist_out.  n_scen <= 65535. */
 int fp_explain_batch(fp_ctx *ctx, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
                      uint32_t *hist_out);
+/* Drain what-if sweep (SPEC.md 2.11): "can this server, or this whole zone, be taken out?", asked of every
+ * candidate at once.  nodes is the LIVE table (every running container's request already deducted on its node),
+ * assign[c] the node container c runs on (FP_NONE = not running), group[n] < n_cand the candidate node n belongs
+ * to (FP_NONE = none): group[n] = n with n_cand = nodes->n drains each server alone, group = topology domain asks
+ * about each zone's outage.  Every candidate k is computed independently from the same base state: its evictees
+ * (the containers with group[assign[c]] == k) are visited in fp_place's order (cpu desc, mem desc, index asc)
+ * and each goes to the feasible node with the smallest fp_place_policy key among the targets (schedulable and
+ * group[n] != k), on the state the candidate's earlier moves left (cpu_free, mem_free, conflict_used and
+ * node_count updated as fp_place_policy updates them).  Nothing is returned to the drained nodes and no input is
+ * written.  assign_out[c] = the new node of a moved evictee, FP_NONE for a stranded one (reason_out
+ * FP_REASON_NOFIT) and assign[c] for every other container (reason_out 0); the groups partition the nodes, so
+ * the one array holds every candidate's plan.  summary_out holds one row of FP_DRAIN_WORDS u32 per candidate:
+ *   EVICTED  its evictees        STRANDED  those left without a node      STRANDED_CPU, STRANDED_MEM  their sums
+ *   TARGETS  the distinct nodes that received an evictee                  (u32, wrap)
+ *   FIRST_STRANDED  the stranded container that comes first in the visiting order, else FP_NONE
+ *   NODES    the nodes of the candidate;  word 7 is written as 0.
+ * A candidate without evictees gets a row of zeros with FIRST_STRANDED = FP_NONE.  node_count is nullable
+ * (zeros).  nodes->n or n_cand above FP_POLICY_MAX_NODES is FP_EOVERFLOW; a strategy above
+ * FP_STRATEGY_FILL_LOWEST, assign_out == assign, a group[n] that is neither < n_cand nor FP_NONE and an
+ * assign[c] that is neither < nodes->n nor FP_NONE are FP_EINVAL; on any error nothing is written.  The
+ * policy's spread constraint, fallback chain and quota are not applied to moves. */
+enum { FP_DRAIN_EVICTED = 0, FP_DRAIN_STRANDED = 1, FP_DRAIN_STRANDED_CPU = 2, FP_DRAIN_STRANDED_MEM = 3,
+       FP_DRAIN_TARGETS = 4, FP_DRAIN_FIRST_STRANDED = 5, FP_DRAIN_NODES = 6, FP_DRAIN_WORDS = 8 };
+int fp_drain_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                   const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
+                   const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out, uint32_t *summary_out);
 /* One stage's whole plan, the `fleet up --dry-run` path (crates/fleetflow/src/commands/up.rs:57-136):
  *   perm_out                 A1 legacy start order (engine.rs:64-85, as fp_legacy_order)
  *   level_out, order_out, n_cycle_out   A2 levels and start order (as fp_levelize)
@@ -408,6 +437,13 @@ int fp_dev_place_batch_policy_quota(fp_ctx *ctx, const fp_batch *b, const uint32
                                     const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
                                     uint8_t *hops_out, const uint32_t *quota, uint32_t *quota_used,
                                     uint8_t *quota_why_out);
+/* As fp_drain_sweep on device pointers (summary_out included).  A group or assign value out of range is found
+ * on the device before any store: nothing is written and fp_ctx_sync() reports FP_EINVAL.  The call takes 24
+ * bytes per container plus the sorts' scratch from the context's workspace. */
+int fp_dev_drain_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                       const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
+                       const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
+                       uint32_t *summary_out);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

@@ -47,6 +47,15 @@ pub const FP_EXPLAIN_HIST_MIXED: usize = 5;
 pub const FP_EXPLAIN_HIST_FITS: usize = 6;
 pub const FP_EXPLAIN_HIST_SELECTED: usize = 7;
 pub const FP_EXPLAIN_HIST_WORDS: usize = 8;
+// drain what-if sweep (SPEC.md 2.11): the word indices of a candidate's summary row
+pub const FP_DRAIN_EVICTED: usize = 0;
+pub const FP_DRAIN_STRANDED: usize = 1;
+pub const FP_DRAIN_STRANDED_CPU: usize = 2;
+pub const FP_DRAIN_STRANDED_MEM: usize = 3;
+pub const FP_DRAIN_TARGETS: usize = 4;
+pub const FP_DRAIN_FIRST_STRANDED: usize = 5;
+pub const FP_DRAIN_NODES: usize = 6;
+pub const FP_DRAIN_WORDS: usize = 8;
 pub const FP_K_PLACE: c_int = 0;
 pub const FP_K_SORT: c_int = 1;
 pub const FP_K_FEAS: c_int = 2;
@@ -205,6 +214,10 @@ unsafe extern "C" {
                       ignore_labels: u32, rows_out: *mut u32) -> c_int;
     pub fn fp_explain_batch(ctx: *mut fp_ctx, b: *const fp_batch, reason_mask: u32, ignore_labels: *const u32,
                             hist_out: *mut u32) -> c_int;
+    pub fn fp_drain_sweep(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, assign: *const u32,
+                          group: *const u32, n_cand: u32, strategy: u32, preferred_labels: u32,
+                          node_count: *const u32, assign_out: *mut u32, reason_out: *mut u8,
+                          summary_out: *mut u32) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,
                          perm_out: *mut u32, level_out: *mut u32, order_out: *mut u32, n_cycle_out: *mut u32,
                          first_out: *mut u32, count_out: *mut u32, assign_out: *mut u32, reason_out: *mut u8)
@@ -238,6 +251,10 @@ unsafe extern "C" {
                                            max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
                                            hops_out: *mut u8, quota: *const u32, quota_used: *mut u32,
                                            quota_why_out: *mut u8) -> c_int;
+    pub fn fp_dev_drain_sweep(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, assign: *const u32,
+                              group: *const u32, n_cand: u32, strategy: u32, preferred_labels: u32,
+                              node_count: *const u32, assign_out: *mut u32, reason_out: *mut u8,
+                              summary_out: *mut u32) -> c_int;
     pub fn fp_dev_argmin_cost(ctx: *mut fp_ctx, cost: *const u64, n: u32, best_dev: *mut u32) -> c_int;
     pub fn fp_dev_gen_batch(ctx: *mut fp_ctx, seed: u64, b: *const fp_batch, flags: u32) -> c_int;
 }

@@ -131,6 +131,37 @@ impl Planner {
         Ok(rows)
     }
 
+    /// Drain what-if sweep (SPEC.md 2.11, fleetplace.h `fp_drain_sweep`): `nodes` is the live table, `assign`
+    /// the node each container runs on (`ffi::FP_NONE` = not running), `group` the candidate of each node
+    /// (< `n_cand`, `ffi::FP_NONE` = none).  Every candidate's evictees are re-placed, independently and from
+    /// the same base state, under `strategy` / `preferred_labels`; no input is changed.  Returns (the new node
+    /// per container, the reason per container, one row of `ffi::FP_DRAIN_WORDS` words per candidate).
+    #[allow(clippy::too_many_arguments)]
+    pub fn drain_sweep(&mut self, c: &Containers, nodes: &Nodes, assign: &[u32], group: &[u32], n_cand: u32,
+                       strategy: u32, preferred_labels: u32, node_count: Option<&[u32]>)
+                       -> Result<(Vec<u32>, Vec<u8>, Vec<[u32; ffi::FP_DRAIN_WORDS]>), PlanError> {
+        let (n, nn) = (c.cpu_m.len(), nodes.cpu_free.len());
+        if !c.all_len(n) || !nodes.all_len(nn) || assign.len() != n || group.len() != nn
+            || node_count.map_or(false, |k| k.len() != nn) {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        // fp_drain_sweep reads the node table only: the mutable pointers of fp_nodes are never written through
+        let ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_ptr() as *mut u32,
+                                 mem_free: nodes.mem_free.as_ptr() as *mut u32, labels: nodes.labels.as_ptr(),
+                                 conflict_used: nodes.conflict_used.as_ptr() as *mut u32,
+                                 schedulable: nodes.schedulable.as_ptr() };
+        let (mut out, mut reason) = (vec![0u32; n], vec![0u8; n]);
+        let mut rows = vec![[0u32; ffi::FP_DRAIN_WORDS]; n_cand as usize];
+        check(unsafe {
+            ffi::fp_drain_sweep(self.ctx, &cs, &ns, assign.as_ptr(), group.as_ptr(), n_cand, strategy, preferred_labels,
+                                node_count.map_or(std::ptr::null(), |k| k.as_ptr()), out.as_mut_ptr(),
+                                reason.as_mut_ptr(), rows.as_mut_ptr() as *mut u32)
+        })?;
+        Ok((out, reason, rows))
+    }
+
     /// Scored placement (SPEC.md 2.6, fleetplace.h `fp_place_policy`): `strategy` is one of
     /// `ffi::FP_STRATEGY_*`, `preferred_labels` the soft preferred-label mask, `node_count` the
     /// containers already on each node (updated in place; None starts at zero).  `nodes` is
@@ -632,6 +663,43 @@ pub fn explain_stage(flow: &Flow, stage_name: &str, c: &Containers, nodes: &Node
     }
     let rows = with_planner(|p| p.explain(c, nodes, Some(&sel), 0))?;
     Ok(sel.iter().map(|&i| i as usize).zip(rows).collect())
+}
+
+/// "Can this server be taken out?" for every server of a stage (SPEC.md 2.11; the `drain` scheduling state of
+/// crates/fleetflow-controlplane/src/model.rs:435-442): `assign` is the running plan ([`place_stage`]'s result)
+/// and `nodes` the live table it left.  Each server is drained on its own, from the same live state.  Returns,
+/// per server in `stage.servers` order, its slug, the moves `(service, new server)` of the services it runs
+/// (`None` = stranded, in stage order) and its row of `ffi::FP_DRAIN_WORDS` words (`ffi::FP_DRAIN_*`).
+#[allow(clippy::type_complexity)]
+pub fn drain_sweep(flow: &Flow, stage_name: &str, c: &Containers, nodes: &Nodes, assign: &[Option<String>],
+                   strategy: u32, preferred_labels: u32, node_count: Option<&[u32]>)
+                   -> Result<Vec<(String, Vec<(String, Option<String>)>, [u32; ffi::FP_DRAIN_WORDS])>, PlanError> {
+    let Some(stage) = flow.stages.get(stage_name) else { return Err(PlanError(ffi::FP_EINVAL)) };
+    if nodes.cpu_free.len() != stage.servers.len() || c.cpu_m.len() != stage.services.len()
+        || assign.len() != stage.services.len() {
+        return Err(PlanError(ffi::FP_EINVAL));
+    }
+    let mut running = Vec::with_capacity(assign.len());
+    for a in assign {
+        running.push(match a {
+            None => ffi::FP_NONE,
+            Some(slug) => match stage.servers.iter().position(|s| s == slug) {
+                Some(n) => n as u32,
+                None => return Err(PlanError(ffi::FP_EINVAL)),
+            },
+        });
+    }
+    let group: Vec<u32> = (0..stage.servers.len() as u32).collect();
+    let (out, _, rows) = with_planner(|p| {
+        p.drain_sweep(c, nodes, &running, &group, group.len() as u32, strategy, preferred_labels, node_count)
+    })?;
+    Ok(stage.servers.iter().enumerate().map(|(k, slug)| {
+        let moves = running.iter().enumerate().filter(|(_, &n)| n == k as u32).map(|(v, _)| {
+            let to = if out[v] == ffi::FP_NONE { None } else { Some(stage.servers[out[v] as usize].clone()) };
+            (stage.services[v].clone(), to)
+        }).collect();
+        (slug.clone(), moves, rows[k])
+    }).collect())
 }
 
 /// `fp_strategy` of a tenant `PlacementPolicy.strategy` string
