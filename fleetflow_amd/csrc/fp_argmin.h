@@ -1,6 +1,10 @@
 // fp_argmin.h -- the block argmin over 64-bit placement keys that the scored placer (fp_policy.hip,
 // SPEC.md 2.6) and the drain sweep (fp_drain.hip, SPEC.md 2.11) share: the 2.6 key layout and the
 // cross-lane helpers.  Device code only; every function is forced inline.
+// This header is where sharing between k_policy and k_drain_sweep stops: moving any more of them into shared
+// functions (the strategy's primary score, the block min with its slots and parity, the winner's update)
+// changes the code of k_policy's instantiations, by reordered opcodes up to hundreds of instructions
+// (DESIGN.md 4.11 has the table).  Compare with tools/isa_compare.py before believing otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -126,8 +126,6 @@ int fp_dev_done(fp_ctx *c, int rc) {
 }
 
 // ---- arenas ----------------------------------------------------------------
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // c->last_rng points into the arena: whoever recycles or frees it forgets the pointer
 void fp_ws_reset(fp_ctx *c) {
     c->ws_top = 0;
@@ -140,16 +138,16 @@ int fp_ws_reserve(fp_ctx *c, size_t bytes) {
     if (c->ws) (void)hipFree(c->ws);
     c->ws = nullptr;
     c->ws_cap = 0;
-    size_t cap = align256(bytes + bytes / 4 + 4096);
+    size_t cap = fp_align256(bytes + bytes / 4 + 4096);
     FP_HIP(hipMalloc(&c->ws, cap));
     c->ws_cap = cap;
     return FP_OK;
 }
 void *fp_ws_take(fp_ctx *c, size_t bytes) {
-    size_t top = align256(c->ws_top);
-    if (top + bytes > c->ws_cap) return nullptr;
-    c->ws_top = top + bytes;
-    return c->ws + top;
+    const size_t end = fp_take_end(c->ws_top, bytes);
+    if (end > c->ws_cap) return nullptr;
+    c->ws_top = end;
+    return c->ws + (end - bytes);
 }
 void fp_stage_reset(fp_ctx *c) { c->stage_top = 0; }
 int fp_stage_reserve(fp_ctx *c, size_t bytes) {
@@ -158,16 +156,16 @@ int fp_stage_reserve(fp_ctx *c, size_t bytes) {
     if (c->stage) (void)hipFree(c->stage);
     c->stage = nullptr;
     c->stage_cap = 0;
-    size_t cap = align256(bytes + bytes / 4 + 4096);
+    size_t cap = fp_align256(bytes + bytes / 4 + 4096);
     FP_HIP(hipMalloc(&c->stage, cap));
     c->stage_cap = cap;
     return FP_OK;
 }
 void *fp_stage_take(fp_ctx *c, size_t bytes) {
-    size_t top = align256(c->stage_top);
-    if (top + bytes > c->stage_cap) return nullptr;
-    c->stage_top = top + bytes;
-    return c->stage + top;
+    const size_t end = fp_take_end(c->stage_top, bytes);
+    if (end > c->stage_cap) return nullptr;
+    c->stage_top = end;
+    return c->stage + (end - bytes);
 }
 
 int fp_take_err(fp_ctx *c) {
@@ -269,113 +267,96 @@ extern "C" int fp_dev_feasibility(fp_ctx *c, const fp_containers *cs, const fp_n
 }
 
 // ---- host-pointer entry points -------------------------------------------------
-template <class T>
-static T *stage_in(fp_ctx *c, const T *h, size_t n, int *rc) {
-    if (*rc) return nullptr;
-    if (!h) return nullptr;
-    T *d = (T *)fp_stage_take(c, n * sizeof(T) + 4);
-    if (!d) { *rc = FP_ENOMEM; return nullptr; }
-    if (n && hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        *rc = FP_EDEVICE;
-    return d;
-}
-template <class T>
-static T *stage_out(fp_ctx *c, size_t n, int *rc) {
-    if (*rc) return nullptr;
-    T *d = (T *)fp_stage_take(c, n * sizeof(T) + 4);
-    if (!d) *rc = FP_ENOMEM;
-    return d;
-}
-// Results of a host-pointer call: every device buffer goes to pinned staging first; the
-// caller's buffers are written only after the kernels' error word and every copy came
-// back clean ("on error nothing is written", fleetplace.h).
-struct OutCopy {
-    void *h;
-    const void *d;
-    size_t bytes;
-};
+// Every device buffer of a host-pointer call is one fp_row (fp_layout.h; the lists are in fp_rows.h): its host
+// source, its host destination, its size and where the device pointer goes.  The rows of a call, in the order of
+// its takes, are all that describes its staging: stage_rows sizes the arena from them, takes and copies in;
+// copy_back_all and copy_back_span copy out.
+
 // a pinned host buffer of at least `need` bytes: grown with headroom, the old content dropped
 static int grow_pinned(char **buf, size_t *cap, size_t need) {
     if (need <= *cap) return FP_OK;
     if (*buf) (void)hipHostFree(*buf);
     *buf = nullptr;
     *cap = 0;
-    const size_t grown = align256(need + need / 4 + 4096);
+    const size_t grown = fp_align256(need + need / 4 + 4096);
     FP_HIP(hipHostMalloc(buf, grown, hipHostMallocDefault));
     *cap = grown;
     return FP_OK;
 }
-static int copy_back_all(fp_ctx *c, const OutCopy *o, int n) {
+
+// Reserves exactly what the rows take, takes it, hands out the device pointers and issues the copies in: one
+// per input that has bytes.
+// packed: small host-pointer calls (a fleet.kdl stage: config 1) pay per HIP call, not per byte.  Their inputs,
+// which are the leading rows, go through one pinned buffer and ONE host-to-device copy, and copy_back_span
+// brings the results and the call's error word back in ONE device-to-host copy (6 HIP calls per fp_levelize
+// instead of 10), so the word's slot behind the rows is reserved here too.
+static int stage_rows(fp_ctx *c, const fp_row *r, int n, bool packed) {
+    size_t off[FP_MAX_ROWS];
+    if (n > FP_MAX_ROWS) return FP_EINVAL;
+    const size_t end = fp_rows_layout(r, n, 0, off);
+    if (int rc = fp_stage_reserve(c, packed ? fp_take_end(end, 4) : end)) return rc;
+    fp_stage_reset(c);
+    char *base = (char *)fp_stage_take(c, end);
+    if (!base) return FP_ENOMEM;
+    fp_rows_point(r, n, base, off);
+    size_t in_end = 0;  // where the last input that is there ends
+    for (int i = 0; i < n; ++i)
+        if (r[i].in) in_end = off[i] + r[i].bytes + FP_STAGE_PAD;
+    if (!packed) {
+        for (int i = 0; i < n; ++i)
+            if (r[i].in && r[i].bytes)
+                FP_HIP(hipMemcpyAsync(*r[i].dev, r[i].in, r[i].bytes, hipMemcpyHostToDevice, c->stream));
+        return FP_OK;
+    }
+    if (!in_end) return FP_OK;
+    if (c->h_in_ev) FP_HIP(hipEventSynchronize(c->h_in_ev));  // the previous copy out of h_in is done
+    if (int rc = grow_pinned(&c->h_in, &c->h_in_cap, in_end)) return rc;
+    if (!c->h_in_ev) FP_HIP(hipEventCreateWithFlags(&c->h_in_ev, hipEventDisableTiming));
+    for (int i = 0; i < n; ++i)
+        if (r[i].in) memcpy(c->h_in + off[i], r[i].in, r[i].bytes);
+    FP_HIP(hipMemcpyAsync(base, c->h_in, in_end, hipMemcpyHostToDevice, c->stream));
+    FP_HIP(hipEventRecord(c->h_in_ev, c->stream));
+    return FP_OK;
+}
+template <int N>
+static int stage_rows(fp_ctx *c, const fp_row (&r)[N], bool packed = false) {
+    return stage_rows(c, r, N, packed);
+}
+
+// Results of a host-pointer call: every device buffer goes to pinned staging first; the caller's buffers are
+// written only after the kernels' error word and every copy came back clean ("on error nothing is written",
+// fleetplace.h).
+static int copy_back_all(fp_ctx *c, const fp_row *r, int n) {
     size_t total = 0;
     for (int i = 0; i < n; ++i)
-        if (o[i].h && o[i].bytes) total += align256(o[i].bytes);
+        if (r[i].out && r[i].bytes) total += fp_align256(r[i].bytes);
     if (int rc = grow_pinned(&c->h_stage, &c->h_stage_cap, total)) return rc;
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
-        if (!o[i].h || !o[i].bytes) continue;
-        FP_HIP(hipMemcpyAsync(c->h_stage + off, o[i].d, o[i].bytes, hipMemcpyDeviceToHost, c->stream));
-        off += align256(o[i].bytes);
+        if (!r[i].out || !r[i].bytes) continue;
+        FP_HIP(hipMemcpyAsync(c->h_stage + off, *r[i].dev, r[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        off += fp_align256(r[i].bytes);
     }
     const int rc = fp_take_err(c);  // synchronises the copies too
     if (rc) return rc;
     off = 0;
     for (int i = 0; i < n; ++i) {
-        if (!o[i].h || !o[i].bytes) continue;
-        memcpy(o[i].h, c->h_stage + off, o[i].bytes);
-        off += align256(o[i].bytes);
+        if (!r[i].out || !r[i].bytes) continue;
+        memcpy(r[i].out, c->h_stage + off, r[i].bytes);
+        off += fp_align256(r[i].bytes);
     }
     return FP_OK;
 }
-
-// Small host-pointer calls (a fleet.kdl stage: config 1) pay per HIP call, not per byte: the
-// inputs go through one pinned buffer and ONE host-to-device copy, and the results plus the
-// call's error word come back in ONE device-to-host copy of the contiguous staging span
-// (6 HIP calls per fp_levelize instead of 10; the results are still written only when the error
-// word is clean).
-struct InCopy {
-    const void *h;
-    size_t bytes;
-    const void **d;  // receives the device copy (nullptr when h is null)
-};
-static int stage_in_packed(fp_ctx *c, const InCopy *in, int n) {
-    size_t total = 0;
-    for (int i = 0; i < n; ++i)
-        if (in[i].h) total += align256(in[i].bytes + 4);
-    if (!total) {
-        for (int i = 0; i < n; ++i) *in[i].d = nullptr;
-        return FP_OK;
-    }
-    if (c->h_in_ev) FP_HIP(hipEventSynchronize(c->h_in_ev));  // the previous copy out of h_in is done
-    if (int rc = grow_pinned(&c->h_in, &c->h_in_cap, total)) return rc;
-    if (!c->h_in_ev) FP_HIP(hipEventCreateWithFlags(&c->h_in_ev, hipEventDisableTiming));
-    char *d = (char *)fp_stage_take(c, total);
-    if (!d) return FP_ENOMEM;
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!in[i].h) { *in[i].d = nullptr; continue; }
-        memcpy(c->h_in + off, in[i].h, in[i].bytes);
-        *in[i].d = d + off;
-        off += align256(in[i].bytes + 4);
-    }
-    FP_HIP(hipMemcpyAsync(d, c->h_in, total, hipMemcpyHostToDevice, c->stream));
-    FP_HIP(hipEventRecord(c->h_in_ev, c->stream));
-    return FP_OK;
-}
-// Results from stage_out buffers taken one after another (a contiguous span of the staging
-// arena): the call's error word is copied behind them on the device, the span comes back in one
-// copy, and the caller's buffers are written only when that word is clean.
-static int copy_back_span(fp_ctx *c, const OutCopy *o, int n) {
-    const char *lo = nullptr, *hi = nullptr;
-    for (int i = 0; i < n; ++i) {
-        if (!o[i].d) continue;
-        const char *a = (const char *)o[i].d, *b = a + o[i].bytes;
-        if (!lo || a < lo) lo = a;
-        if (!hi || b > hi) hi = b;
-    }
+// The results of a packed call (stage_rows): the rows from the first result on are a contiguous span of the
+// staging arena.  The call's error word is copied behind them on the device, the span comes back in one copy,
+// and the caller's buffers are written only when that word is clean.
+static int copy_back_span(fp_ctx *c, const fp_row *r, int n) {
+    const char *lo = nullptr;
+    for (int i = 0; i < n && !lo; ++i)
+        if (r[i].out || r[i].take) lo = (const char *)*r[i].dev;
     uint32_t *slot = (uint32_t *)fp_stage_take(c, 4);
     if (!slot) return FP_ENOMEM;
     if (!lo) lo = (const char *)slot;
-    if ((const char *)slot < hi) return FP_EINVAL;  // not the layout this helper assumes
     const size_t span = (size_t)((const char *)slot + 4 - lo);
     if (int rc = grow_pinned(&c->h_stage, &c->h_stage_cap, span)) return rc;
     FP_HIP(hipMemcpyAsync(slot, c->d_err, 4, hipMemcpyDeviceToDevice, c->stream));
@@ -388,9 +369,13 @@ static int copy_back_span(fp_ctx *c, const OutCopy *o, int n) {
         return -(int)e;
     }
     for (int i = 0; i < n; ++i)
-        if (o[i].h && o[i].bytes) memcpy(o[i].h, c->h_stage + ((const char *)o[i].d - lo), o[i].bytes);
+        if (r[i].out && r[i].bytes) memcpy(r[i].out, c->h_stage + ((const char *)*r[i].dev - lo), r[i].bytes);
     return FP_OK;
 }
+template <int N>
+static int copy_back_all(fp_ctx *c, const fp_row (&r)[N]) { return copy_back_all(c, r, N); }
+template <int N>
+static int copy_back_span(fp_ctx *c, const fp_row (&r)[N]) { return copy_back_span(c, r, N); }
 
 extern "C" int fp_legacy_order(fp_ctx *c, const fp_graph *g, uint32_t *perm_out) {
     if (!c || !g || (g->n_vertices && (!g->has_deps || !perm_out))) return FP_EINVAL;
@@ -398,22 +383,14 @@ extern "C" int fp_legacy_order(fp_ctx *c, const fp_graph *g, uint32_t *perm_out)
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
     const size_t V = g->n_vertices;
-    int rc = fp_stage_reserve(c, 2 * V * 4 + 8192);
-    if (rc) return rc;
-    fp_stage_reset(c);
     fp_graph dg = *g;
-    const void *dhd = nullptr;
-    const InCopy in[] = {{g->has_deps, V, &dhd}};
-    if ((rc = stage_in_packed(c, in, 1))) return rc;
-    dg.has_deps = (const uint8_t *)dhd;
     dg.row_ptr = nullptr;
     dg.col = nullptr;
-    uint32_t *dperm = stage_out<uint32_t>(c, V, &rc);
-    if (rc) return rc;
-    rc = fp_dev_legacy_order_impl(c, &dg, dperm);
-    if (rc) return rc;
-    const OutCopy o[] = {{perm_out, dperm, V * 4}};
-    return copy_back_span(c, o, 1);
+    uint32_t *dperm = nullptr;
+    const fp_row rows[] = {fp_row_in(g->has_deps, V, &dg.has_deps), fp_row_out(perm_out, V, &dperm)};
+    if (int rc = stage_rows(c, rows, true)) return rc;
+    if (int rc = fp_dev_legacy_order_impl(c, &dg, dperm)) return rc;
+    return copy_back_span(c, rows);
 }
 
 extern "C" int fp_levelize(fp_ctx *c, const fp_graph *g, uint32_t *level_out, uint32_t *order_out,
@@ -431,25 +408,14 @@ extern "C" int fp_levelize(fp_ctx *c, const fp_graph *g, uint32_t *level_out, ui
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, (V + 1) * 4 + E * 4 + V + 2 * V * 4 + 16 * 256);
-    if (rc) return rc;
-    fp_stage_reset(c);
     fp_graph dg = *g;
-    const void *drp = nullptr, *dcol = nullptr, *dhd = nullptr;
-    const InCopy in[] = {{g->row_ptr, (V + 1) * 4, &drp}, {E ? g->col : nullptr, E * 4, &dcol},
-                         {g->has_deps, V, &dhd}};
-    if ((rc = stage_in_packed(c, in, 3))) return rc;
-    dg.row_ptr = (const uint32_t *)drp;
-    dg.col = (const uint32_t *)dcol;
-    dg.has_deps = (const uint8_t *)dhd;
-    uint32_t *dlev = stage_out<uint32_t>(c, V, &rc);
-    uint32_t *dord = stage_out<uint32_t>(c, V, &rc);
-    uint32_t *dcyc = stage_out<uint32_t>(c, 1, &rc);
-    if (rc) return rc;
-    rc = fp_dev_levelize_impl(c, &dg, dlev, dord, dcyc);
-    if (rc) return rc;
-    const OutCopy o[] = {{level_out, dlev, V * 4}, {order_out, dord, V * 4}, {n_cycle_out, dcyc, 4}};
-    return copy_back_span(c, o, 3);
+    uint32_t *dlev = nullptr, *dord = nullptr, *dcyc = nullptr;
+    const fp_row rows[] = {fp_row_in(g->row_ptr, V + 1, &dg.row_ptr), fp_row_in(E ? g->col : nullptr, E, &dg.col),
+                           fp_row_in(g->has_deps, V, &dg.has_deps), fp_row_out(level_out, V, &dlev),
+                           fp_row_out(order_out, V, &dord), fp_row_out(n_cycle_out, 1, &dcyc)};
+    if (int rc = stage_rows(c, rows, true)) return rc;
+    if (int rc = fp_dev_levelize_impl(c, &dg, dlev, dord, dcyc)) return rc;
+    return copy_back_span(c, rows);
 }
 
 // ---- placement: fp_place*, fp_place*_policy* --------------------------------------
@@ -485,84 +451,31 @@ static fp_batch single_batch(const fp_containers *cs, const fp_nodes *ns, const 
     return b;
 }
 
-// The device copy of a host batch: its ten input arrays, then (scored placement: `o` and `dopt` non-null)
-// the policy inputs, then assign / reason / cost and the policy outputs the caller asked for.  The order
-// of the takes is the layout of the staging arena and the order of the copies.
-static fp_batch stage_batch(fp_ctx *c, const fp_batch *b, const fp_policy_opts *o, fp_policy_opts *dopt, int *rc) {
-    const size_t S = b->n_scen, SC = S * b->n_containers, SN = S * b->n_nodes;
-    fp_batch d = *b;
-    d.cpu_m = stage_in(c, b->cpu_m, SC, rc);
-    d.mem_mib = stage_in(c, b->mem_mib, SC, rc);
-    d.req_labels = stage_in(c, b->req_labels, SC, rc);
-    d.conflict = stage_in(c, b->conflict, SC, rc);
-    d.level = b->level ? stage_in(c, b->level, SC, rc) : nullptr;
-    d.cpu_free = stage_in(c, b->cpu_free, SN, rc);
-    d.mem_free = stage_in(c, b->mem_free, SN, rc);
-    d.labels = stage_in(c, b->labels, SN, rc);
-    d.conflict_used = stage_in(c, b->conflict_used, SN, rc);
-    d.schedulable = stage_in(c, b->schedulable, SN, rc);
-    if (o) {
-        dopt->strategy = stage_in(c, o->strategy, S, rc);
-        dopt->preferred = stage_in(c, o->preferred, S, rc);
-        dopt->node_count = stage_in(c, o->node_count, SN, rc);
-        dopt->domain = stage_in(c, o->domain, SN, rc);
-        dopt->max_skew = stage_in(c, o->max_skew, S, rc);
-        dopt->relax_mask = stage_in(c, o->relax_mask, S * FP_FALLBACK_MAX_HOPS, rc);
-        dopt->n_hops = stage_in(c, o->n_hops, S, rc);
-        dopt->quota = stage_in(c, o->quota, S * FP_QUOTA_DIMS, rc);
-        dopt->quota_used = stage_in(c, o->quota_used, S * FP_QUOTA_DIMS, rc);
-    }
-    d.assign = stage_out<uint32_t>(c, SC, rc);
-    d.reason = stage_out<uint8_t>(c, SC, rc);
-    d.cost = stage_out<uint64_t>(c, S, rc);
-    if (o) {
-        dopt->hops = o->hops ? stage_out<uint8_t>(c, SC, rc) : nullptr;
-        dopt->quota_why = o->quota_why ? stage_out<uint8_t>(c, SC, rc) : nullptr;
-    }
-    return d;
-}
-
-// the plan and the updated node state of staged batch `d` into the caller's `b`, with the policy outputs
-static int batch_copy_back(fp_ctx *c, const fp_batch *b, const fp_batch &d, const fp_policy_opts *o,
-                           const fp_policy_opts *dopt) {
-    const size_t S = b->n_scen, SC = S * b->n_containers, SN = S * b->n_nodes;
-    OutCopy out[10] = {{b->assign, d.assign, SC * 4},    {b->reason, d.reason, SC},
-                       {b->cost, d.cost, S * 8},         {b->cpu_free, d.cpu_free, SN * 4},
-                       {b->mem_free, d.mem_free, SN * 4}, {b->conflict_used, d.conflict_used, SN * 4}};
-    if (!o) return copy_back_all(c, out, 6);
-    out[6] = {o->node_count, dopt->node_count, SN * 4};
-    out[7] = {o->hops, dopt->hops, SC};
-    out[8] = {o->quota_used, dopt->quota_used, S * FP_QUOTA_DIMS * 4};
-    out[9] = {o->quota_why, dopt->quota_why, SC};
-    return copy_back_all(c, out, 10);
-}
-
-static int batch_host(fp_ctx *c, const fp_batch *b) {
-    const size_t S = b->n_scen, SC = S * b->n_containers, SN = S * b->n_nodes;
+// A host batch through the staging arena (fp_batch_rows, fp_rows.h): first fit when `o` is null, else scored
+static int batch_run(fp_ctx *c, const fp_batch *b, const fp_policy_opts *o) {
     if (!batch_has_tables(b)) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1) + SN * (4 * 4 + 1) + S * 8 + 16 * 256);
-    if (rc) return rc;
-    fp_stage_reset(c);
-    const fp_batch d = stage_batch(c, b, nullptr, nullptr, &rc);
-    if (rc) return rc;
-    rc = fp_dev_place_batch_impl(c, &d);
-    if (rc) return rc;
-    return batch_copy_back(c, b, d, nullptr, nullptr);
+    fp_row rows[FP_MAX_ROWS];
+    fp_batch d;
+    fp_policy_opts dopt;
+    const int n = fp_batch_rows(b, o, &d, &dopt, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = o ? fp_dev_place_batch_policy_impl(c, &d, dopt) : fp_dev_place_batch_impl(c, &d)) return rc;
+    return copy_back_all(c, rows, n);
 }
 
 extern "C" int fp_place_batch(fp_ctx *c, const fp_batch *b) {
     if (!c || !b) return FP_EINVAL;
-    return batch_host(c, b);
+    return batch_run(c, b, nullptr);
 }
 
 extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
                         uint32_t *assign_out, uint8_t *reason_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
     const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
-    return batch_host(c, &b);
+    return batch_run(c, &b, nullptr);
 }
 
 // Scored placement (SPEC.md 2.6): fp_place_batch's staging with the per-scenario strategy and
@@ -575,8 +488,7 @@ extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const 
 // quota (SPEC.md 2.10; null = no quota, and then quota_used and quota_why are not touched) has no
 // illegal value.  quota_used (nullable) goes in and comes back; quota_why (nullable) comes back.
 static int batch_policy_host(fp_ctx *c, const fp_batch *b, fp_policy_opts o) {
-    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes;
-    const size_t SC = S * C, SN = S * N;
+    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes, SC = S * C;
     if (S && !o.strategy) return FP_EINVAL;
     for (size_t s = 0; s < S; ++s)
         if (o.strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
@@ -591,20 +503,7 @@ static int batch_policy_host(fp_ctx *c, const fp_batch *b, fp_policy_opts o) {
         if (o.n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
     if (!o.quota) o.quota_used = nullptr, o.quota_why = nullptr;
     if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
-    if (!batch_has_tables(b)) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    fp_host_err_scope es(c);
-    if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, SC * (4 * 6 + 1 + 1 + 1) + SN * (4 * 6 + 1) +
-                                     S * (8 + 4 + 4 + 4 + 4 * FP_FALLBACK_MAX_HOPS + 4 + 2 * 4 * FP_QUOTA_DIMS) + 28 * 256);
-    if (rc) return rc;
-    fp_stage_reset(c);
-    fp_policy_opts dopt;
-    const fp_batch d = stage_batch(c, b, &o, &dopt, &rc);
-    if (rc) return rc;
-    rc = fp_dev_place_batch_policy_impl(c, &d, dopt);
-    if (rc) return rc;
-    return batch_copy_back(c, b, d, &o, &dopt);
+    return batch_run(c, b, &o);
 }
 
 // The twelve exports set the fields their signature has.  A single-scenario export points the per-scenario
@@ -743,23 +642,6 @@ extern "C" int fp_dev_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, con
 }
 
 // ---- feasibility and rejection diagnosis -----------------------------------------
-// the device copies of one scenario's container and node tables (nine arrays, in this order)
-static void stage_tables(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, fp_containers *dc, fp_nodes *dn,
-                         int *rc) {
-    const size_t C = cs->n, N = ns->n;
-    *dc = *cs;
-    *dn = *ns;
-    dc->cpu_m = stage_in(c, cs->cpu_m, C, rc);
-    dc->mem_mib = stage_in(c, cs->mem_mib, C, rc);
-    dc->req_labels = stage_in(c, cs->req_labels, C, rc);
-    dc->conflict = stage_in(c, cs->conflict, C, rc);
-    dn->cpu_free = stage_in(c, ns->cpu_free, N, rc);
-    dn->mem_free = stage_in(c, ns->mem_free, N, rc);
-    dn->labels = stage_in(c, ns->labels, N, rc);
-    dn->conflict_used = stage_in(c, ns->conflict_used, N, rc);
-    dn->schedulable = stage_in(c, ns->schedulable, N, rc);
-}
-
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,
                               uint32_t *first_out, uint32_t *count_out, uint64_t *bitmap_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
@@ -773,20 +655,18 @@ extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, C * 24 + N * 17 + (bitmap_out ? WC * N * 8 : 0) + 16 * 256);
-    if (rc) return rc;
-    fp_stage_reset(c);
+    fp_row rows[FP_MAX_ROWS];
     fp_containers dc;
     fp_nodes dn;
-    stage_tables(c, cs, ns, &dc, &dn, &rc);
-    uint32_t *dfirst = stage_out<uint32_t>(c, C, &rc);
-    uint32_t *dcount = stage_out<uint32_t>(c, C, &rc);
-    uint64_t *dbits = bitmap_out ? stage_out<uint64_t>(c, WC * N, &rc) : nullptr;
-    if (rc) return rc;
-    rc = fp_dev_feasibility_impl(c, &dc, &dn, dfirst, dcount, dbits);
-    if (rc) return rc;
-    const OutCopy o[] = {{first_out, dfirst, C * 4}, {count_out, dcount, C * 4}, {bitmap_out, dbits, WC * N * 8}};
-    return copy_back_all(c, o, 3);
+    uint32_t *dfirst = nullptr, *dcount = nullptr;
+    uint64_t *dbits = nullptr;
+    int n = fp_tables_rows(cs, ns, &dc, &dn, rows);
+    rows[n++] = fp_row_out(first_out, C, &dfirst);
+    rows[n++] = fp_row_out(count_out, C, &dcount);
+    rows[n++] = fp_row_opt(bitmap_out, WC * N, &dbits);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = fp_dev_feasibility_impl(c, &dc, &dn, dfirst, dcount, dbits)) return rc;
+    return copy_back_all(c, rows, n);
 }
 
 // rejection diagnosis (SPEC.md 2.9, fp_explain.hip)
@@ -819,19 +699,17 @@ extern "C" int fp_explain(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, C * 16 + N * 17 + M * (4 + FP_EXPLAIN_WORDS * 4) + 16 * 256);
-    if (rc) return rc;
-    fp_stage_reset(c);
+    fp_row rows[FP_MAX_ROWS];
     fp_containers dc;
     fp_nodes dn;
-    stage_tables(c, cs, ns, &dc, &dn, &rc);
-    const uint32_t *dsel = stage_in(c, sel, M, &rc);
-    uint32_t *drows = stage_out<uint32_t>(c, M * FP_EXPLAIN_WORDS, &rc);  // 256-byte aligned
-    if (rc) return rc;
-    rc = fp_dev_explain_impl(c, &dc, &dn, dsel, n_sel, ignore_labels, drows);
-    if (rc) return rc;
-    const OutCopy o[] = {{rows_out, drows, M * FP_EXPLAIN_WORDS * 4}};
-    return copy_back_all(c, o, 1);
+    const uint32_t *dsel = nullptr;
+    uint32_t *drows = nullptr;  // 256-byte aligned
+    int n = fp_tables_rows(cs, ns, &dc, &dn, rows);
+    rows[n++] = fp_row_in(sel, M, &dsel);
+    rows[n++] = fp_row_out(rows_out, M * FP_EXPLAIN_WORDS, &drows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = fp_dev_explain_impl(c, &dc, &dn, dsel, n_sel, ignore_labels, drows)) return rc;
+    return copy_back_all(c, rows, n);
 }
 
 extern "C" int fp_explain_batch(fp_ctx *c, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
@@ -849,28 +727,22 @@ extern "C" int fp_explain_batch(fp_ctx *c, const fp_batch *b, uint32_t reason_ma
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, SC * 17 + SN * 17 + S * (4 + FP_EXPLAIN_HIST_WORDS * 4) + 16 * 256);
-    if (rc) return rc;
-    fp_stage_reset(c);
     fp_batch d = *b;
     d.level = nullptr; d.assign = nullptr; d.cost = nullptr;
-    d.cpu_m = stage_in(c, b->cpu_m, SC, &rc);
-    d.mem_mib = stage_in(c, b->mem_mib, SC, &rc);
-    d.req_labels = stage_in(c, b->req_labels, SC, &rc);
-    d.conflict = stage_in(c, b->conflict, SC, &rc);
-    d.cpu_free = stage_in(c, b->cpu_free, C ? SN : 0, &rc);
-    d.mem_free = stage_in(c, b->mem_free, C ? SN : 0, &rc);
-    d.labels = stage_in(c, b->labels, C ? SN : 0, &rc);
-    d.conflict_used = stage_in(c, b->conflict_used, C ? SN : 0, &rc);
-    d.schedulable = stage_in(c, b->schedulable, C ? SN : 0, &rc);
-    d.reason = reason_mask ? stage_in(c, b->reason, SC, &rc) : nullptr;
-    const uint32_t *dign = stage_in(c, ignore_labels, S, &rc);
-    uint32_t *dhist = stage_out<uint32_t>(c, S * FP_EXPLAIN_HIST_WORDS, &rc);
-    if (rc) return rc;
-    rc = fp_dev_explain_batch_impl(c, &d, reason_mask, dign, dhist);
-    if (rc) return rc;
-    const OutCopy o[] = {{hist_out, dhist, S * FP_EXPLAIN_HIST_WORDS * 4}};
-    return copy_back_all(c, o, 1);
+    const uint32_t *dign = nullptr;
+    uint32_t *dhist = nullptr;
+    const size_t SNc = C ? SN : 0;  // without containers the node tables are not read
+    const fp_row rows[] = {fp_row_in(b->cpu_m, SC, &d.cpu_m), fp_row_in(b->mem_mib, SC, &d.mem_mib),
+                           fp_row_in(b->req_labels, SC, &d.req_labels), fp_row_in(b->conflict, SC, &d.conflict),
+                           fp_row_in(b->cpu_free, SNc, &d.cpu_free), fp_row_in(b->mem_free, SNc, &d.mem_free),
+                           fp_row_in(b->labels, SNc, &d.labels), fp_row_in(b->conflict_used, SNc, &d.conflict_used),
+                           fp_row_in(b->schedulable, SNc, &d.schedulable),
+                           fp_row_in(reason_mask ? b->reason : nullptr, SC, &d.reason),
+                           fp_row_in(ignore_labels, S, &dign),
+                           fp_row_out(hist_out, S * FP_EXPLAIN_HIST_WORDS, &dhist)};
+    if (int rc = stage_rows(c, rows)) return rc;
+    if (int rc = fp_dev_explain_batch_impl(c, &d, reason_mask, dign, dhist)) return rc;
+    return copy_back_all(c, rows);
 }
 
 // drain what-if sweep (SPEC.md 2.11, fp_drain.hip)
@@ -889,7 +761,7 @@ extern "C" int fp_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes
                               const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
                               uint32_t *summary_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
-    const size_t C = cs->n, N = ns->n, R = (size_t)n_cand * FP_DRAIN_WORDS;
+    const size_t C = cs->n, N = ns->n;
     if (N > FP_POLICY_MAX_NODES || n_cand > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
     if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
     if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out || !reason_out))
@@ -906,22 +778,12 @@ extern "C" int fp_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
-    int rc = fp_stage_reserve(c, C * 25 + N * 25 + R * 4 + 20 * 256);
-    if (rc) return rc;
-    fp_stage_reset(c);
-    fp_containers dc;
-    fp_nodes dn;
-    stage_tables(c, cs, ns, &dc, &dn, &rc);
-    const uint32_t *dassign = stage_in(c, assign, C, &rc);
-    const uint32_t *dgroup = stage_in(c, group, N, &rc);
-    const uint32_t *dcount = stage_in(c, node_count, N, &rc);
-    uint32_t *dout = stage_out<uint32_t>(c, C, &rc);
-    uint8_t *dreason = stage_out<uint8_t>(c, C, &rc);
-    uint32_t *drows = stage_out<uint32_t>(c, R, &rc);
-    if (rc) return rc;
-    rc = fp_dev_drain_sweep_impl(c, &dc, &dn, dassign, dgroup, n_cand, strategy, preferred_labels, dcount, dout, dreason,
-                                 drows);
-    if (rc) return rc;
-    const OutCopy o[] = {{assign_out, dout, C * 4}, {reason_out, dreason, C}, {summary_out, drows, R * 4}};
-    return copy_back_all(c, o, 3);
+    fp_row rows[FP_MAX_ROWS];
+    fp_drain_dev d;
+    const int n = fp_drain_rows(cs, ns, assign, group, n_cand, node_count, assign_out, reason_out, summary_out, &d, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = fp_dev_drain_sweep_impl(c, &d.cs, &d.ns, d.assign, d.group, n_cand, strategy, preferred_labels,
+                                         d.node_count, d.assign_out, d.reason_out, d.summary))
+        return rc;
+    return copy_back_all(c, rows, n);
 }

@@ -6,7 +6,7 @@
 //   1. k_drain_check  : sets the call's "bad" word for a group[n] that is neither < n_cand nor FP_NONE and for
 //                       an assign[c] that is neither < N nor FP_NONE, and FP_EINVAL in the context's error
 //                       word; every later kernel that writes an output returns on the word first
-//   2. bucketing      : k_drain_keys + a stable 64-bit radix sort give the 2.3 order of all containers
+//   2. bucketing      : the radix FFD order (fp_ffd_order.hip) is the 2.3 order of all containers
 //                       (cpu desc, mem desc, index asc), k_drain_cand keys that order by the candidate of each
 //                       container's node (n_cand = no candidate) and a second stable sort over those few bits
 //                       leaves each candidate's evictees contiguous and still in the 2.3 order;
@@ -38,12 +38,6 @@ using fpd::min64;
 using fpd::row_min64;
 using fpd::wave_min64;
 
-static inline unsigned grid_for(size_t n, unsigned block) {
-    size_t g = (n + block - 1) / block;
-    if (g > 65535u * 4) g = 65535u * 4;
-    return (unsigned)(g ? g : 1);
-}
-
 // behind a memset of *bad on the stream; only ever sets it
 __global__ __launch_bounds__(256) void k_drain_check(const uint32_t *__restrict__ assign, uint32_t C,
                                                      const uint32_t *__restrict__ group, uint32_t N, uint32_t n_cand,
@@ -58,14 +52,6 @@ __global__ __launch_bounds__(256) void k_drain_check(const uint32_t *__restrict_
     if (threadIdx.x == 0 && any) {
         atomicOr(bad, 1u);
         atomicMax(err, (uint32_t)(-FP_EINVAL));
-    }
-}
-
-__global__ __launch_bounds__(256) void k_drain_keys(const uint32_t *__restrict__ cpu, const uint32_t *__restrict__ mem,
-                                                    uint32_t C, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < C; i += (size_t)gridDim.x * blockDim.x) {
-        keys[i] = ((uint64_t)~cpu[i] << 32) | (uint32_t)~mem[i];
-        vals[i] = (uint32_t)i;
     }
 }
 
@@ -321,17 +307,16 @@ int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
     hipStream_t st = c->stream;
 
     const uint32_t cand_bits = fp_bitwidth(n_cand);  // the keys are 0..n_cand
-    size_t tmp1 = 0, tmp2 = 0;
+    size_t tmp2 = 0;
+    fp_ffd_order fo = {};
     if (C) {
-        FP_HIP(rocprim::radix_sort_pairs(nullptr, tmp1, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                         (uint32_t *)nullptr, C, 0, 64, st));
         if (cand_bits)
             FP_HIP(rocprim::radix_sort_pairs(nullptr, tmp2, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                              (uint32_t *)nullptr, C, 0, cand_bits, st));
+        if (int rc = fp_ffd_order_size(c, 1, C, tmp2, &fo)) return rc;
     }
-    const size_t sort_tmp = tmp1 > tmp2 ? tmp1 : tmp2;
-    const size_t need = (size_t)C * (8 * 2 + 4 * 2) + ((size_t)n_cand + 1) * 4 + sort_tmp + 16 + 8 * 256;
-    if (int rc = fp_ws_reserve(c, need)) return rc;
+    // the bad word, the FFD order (whose buffers the candidate sort reuses), off
+    if (int rc = fp_ws_reserve(c, 256 + fo.bytes + fp_align256(((size_t)n_cand + 1) * 4))) return rc;
     fp_ws_reset(c);
     uint32_t *bad = (uint32_t *)fp_ws_take(c, 4);
     if (!bad) return FP_ENOMEM;
@@ -346,36 +331,28 @@ int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
         FP_HIP(hipGetLastError());
         return FP_OK;
     }
-    uint64_t *keys_a = (uint64_t *)fp_ws_take(c, (size_t)C * 8);
-    uint64_t *keys_b = (uint64_t *)fp_ws_take(c, (size_t)C * 8);
-    uint32_t *vals_a = (uint32_t *)fp_ws_take(c, (size_t)C * 4);
-    uint32_t *vals_b = (uint32_t *)fp_ws_take(c, (size_t)C * 4);
-    uint32_t *off = (uint32_t *)fp_ws_take(c, ((size_t)n_cand + 1) * 4);
-    void *tmp = fp_ws_take(c, sort_tmp + 16);
-    if (!keys_a || !keys_b || !vals_a || !vals_b || !off || !tmp) return FP_ENOMEM;
-
     k_drain_init<<<grid_for(C, 256), 256, 0, st>>>(assign, C, assign_out, reason_out, bad);
     FP_HIP(hipGetLastError());
     if (n_cand == 0) return FP_OK;
 
     // ---- the evictee lists: 2.3 order, then stable by candidate.  The 64-bit key buffers are free after the
     // first sort and hold the candidate keys of the second ----
+    uint32_t *off = (uint32_t *)fp_ws_take(c, ((size_t)n_cand + 1) * 4);
+    if (!off) return FP_ENOMEM;
     hipEvent_t ev;
     fp_prof_begin(c, FP_K_SORT, &ev);
-    k_drain_keys<<<grid_for(C, 256), 256, 0, st>>>(cs->cpu_m, cs->mem_mib, C, keys_a, vals_a);
+    if (int rc = fp_ffd_order_run(c, 1, C, cs->cpu_m, cs->mem_mib, nullptr, &fo)) return rc;
+    uint32_t *cand_a = (uint32_t *)fo.keys_in, *cand_b = (uint32_t *)fo.keys_out;
+    k_drain_cand<<<grid_for(C, 256), 256, 0, st>>>(fo.order, C, assign, group, N, n_cand, cand_a);
     FP_HIP(hipGetLastError());
-    FP_HIP(rocprim::radix_sort_pairs(tmp, tmp1, keys_a, keys_b, vals_a, vals_b, C, 0, 64, st));
-    uint32_t *cand_a = (uint32_t *)keys_a, *cand_b = (uint32_t *)keys_b;
-    k_drain_cand<<<grid_for(C, 256), 256, 0, st>>>(vals_b, C, assign, group, N, n_cand, cand_a);
-    FP_HIP(hipGetLastError());
-    FP_HIP(rocprim::radix_sort_pairs(tmp, tmp2, cand_a, cand_b, vals_b, vals_a, C, 0, cand_bits, st));
+    FP_HIP(rocprim::radix_sort_pairs(fo.tmp, tmp2, cand_a, cand_b, fo.order, fo.vals_in, C, 0, cand_bits, st));
     k_drain_offsets<<<(n_cand + 1 + 255) / 256, 256, 0, st>>>(cand_b, C, n_cand, off);
     FP_HIP(hipGetLastError());
     fp_prof_end(c, FP_K_SORT, ev);
 
     DrainArgs a;
     a.C = C; a.N = N; a.strategy = strategy; a.preferred = preferred;
-    a.order = vals_a; a.off = off;
+    a.order = fo.vals_in; a.off = off;
     a.cpu = cs->cpu_m; a.mem = cs->mem_mib; a.req = cs->req_labels; a.conf = cs->conflict;
     a.cpu_free = ns->cpu_free; a.mem_free = ns->mem_free; a.conflict_used = ns->conflict_used;
     a.labels = ns->labels; a.schedulable = ns->schedulable;

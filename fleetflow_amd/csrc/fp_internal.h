@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <vector>
 #include "../../include/fleetplace.h"
+#include "fp_rows.h"
 
 #define FP_HIP(call)                                   \
     do {                                               \
@@ -129,6 +130,32 @@ static inline uint32_t fp_bitwidth(uint64_t v) {
     return b;
 }
 
+// blocks of `block` threads for a grid-stride loop over n items
+static inline unsigned grid_for(size_t n, unsigned block) {
+    size_t g = (n + block - 1) / block;
+    if (g > 65535u * 4) g = 65535u * 4;
+    return (unsigned)(g ? g : 1);
+}
+
+// The radix FFD order (fp_ffd_order.hip): key (~cpu << 32 | ~mem), value = the index in the scenario, and a
+// stable rocprim radix sort over all 64 bits -- device-wide for one scenario, segmented for several -- give
+// (cpu desc, mem desc, index asc) per scenario.  S * C < 2^32, C > 0.
+struct fp_ffd_order {
+    size_t bytes;      // workspace fp_ffd_order_run takes: 24 bytes per container, the offsets, the scratch
+    size_t tmp_bytes;  // the sort's scratch, at least what the caller asked for
+    // filled by fp_ffd_order_run: the sorted keys are in keys_out and the order in `order`; keys_in and vals_in
+    // are the sort's inputs, free for the caller afterwards, and so is tmp
+    uint64_t *keys_in, *keys_out;
+    uint32_t *vals_in, *order;
+    void *tmp;
+};
+// min_tmp: scratch bytes the caller wants for a sort of its own through the same buffers (0: none)
+int fp_ffd_order_size(fp_ctx *c, uint32_t S, uint32_t C, size_t min_tmp, fp_ffd_order *fo);
+// takes fo->bytes from the workspace and launches the key kernel, the offsets kernel (S > 1) and the sort.
+// rng: null, or [2] words that receive the OR of every cpu / mem value (one atomic per block and word)
+int fp_ffd_order_run(fp_ctx *c, uint32_t S, uint32_t C, const uint32_t *cpu, const uint32_t *mem, uint32_t *rng,
+                     fp_ffd_order *fo);
+
 // ---- entry points shared between translation units ----
 int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b);
 int fp_dev_levelize_impl(fp_ctx *c, const fp_graph *g, uint32_t *level, uint32_t *order,
@@ -142,23 +169,7 @@ int fp_dev_explain_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, 
                         uint32_t ignore_labels, uint32_t *rows);
 int fp_dev_explain_batch_impl(fp_ctx *c, const fp_batch *b, uint32_t reason_mask, const uint32_t *ignore_labels,
                               uint32_t *hist);
-// scored placement (fp_policy.hip, SPEC.md 2.6 to 2.10): what a call has besides its batch.  Not ABI: the
-// exports of fp_ctx.hip fill in the fields their signature has.  Only strategy [S] is required.
-struct fp_policy_opts {
-    const uint32_t *strategy = nullptr, *preferred = nullptr;  // [S] each
-    uint32_t *node_count = nullptr;                            // [S][N], in/out
-    // topology spread (2.7): domain [S][N], max_skew [S]; either one null = no constraint
-    const uint32_t *domain = nullptr, *max_skew = nullptr;
-    // fallback chain (2.8): relax_mask [S][4], n_hops [S]; either one null = no fallback.  hops [S][C]
-    // receives the winner's hop: all zero when the call has no chain
-    const uint32_t *relax_mask = nullptr, *n_hops = nullptr;
-    uint8_t *hops = nullptr;
-    // resource quota (2.10): quota [S][3], null = no quota; quota_used [S][3] (in/out) and quota_why
-    // [S][C] are untouched without quota
-    const uint32_t *quota = nullptr;
-    uint32_t *quota_used = nullptr;
-    uint8_t *quota_why = nullptr;
-};
+// scored placement (fp_policy.hip, SPEC.md 2.6 to 2.10; fp_policy_opts: fp_rows.h)
 // every pointer is device memory
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy_opts &o);
 

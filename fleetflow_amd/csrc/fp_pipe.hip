@@ -131,7 +131,7 @@ struct PipeArgs {
     const uint32_t *thr;    // [2K] device: ascending thresholds, cpu then mem, thr[0] = thr[K] = 0
     uint32_t prio;          // wave priority mode (FP_PRIO_LEVEL comment)
     // packed-capacity pair (fp_pipe_pk.h): the batch's OR of every cpu value [0] and mem value [1]
-    // (containers and schedulable nodes; k_scen_sort / k_make_keys / k_node_summary), and the mode:
+    // (containers and schedulable nodes; k_scen_sort / k_ffd_keys / k_node_summary), and the mode:
     // 0 = the u32 kernel alone; 1 / 2 = the u32 / packed kernel of a pair launched back to back,
     // each running the batch only when the values do not / do pack (the other one returns)
     uint32_t *rng;  // [3]: [2] = the kernel that ran (1 u32, 2 packed; fp_ctx_place_path)

@@ -14,15 +14,13 @@
 //      sample's value set, or in the scenario's own when it holds a value the sample lacks), which
 //      falls back, in the same workgroup, to a generic stable LSD sort of the raw values when the
 //      scenario has more than 256 distinct values or values >= 2^18
-//   3b. larger scenarios: k_make_keys (full-width key (~cpu << 32 | ~mem), value = index) and a
-//      stable rocprim radix sort over 64 bits, segmented per scenario when there are several
+//   3b. larger scenarios: the radix FFD order (fp_ffd_order.hip: full-width key (~cpu << 32 | ~mem), value =
+//      index, and a stable rocprim radix sort over 64 bits, segmented per scenario when there are several)
 //   4. k_ffd_pipe   : (fp_pipe.hip) per scenario, containers in key order stream
 //                     through a pipeline of node-group stages (LDS-resident node
 //                     tiles); lowest feasible node wins, capacity updated in place.
 //   5. k_cost_reduce: packed cost per scenario from the per-segment counters.
 #include "fp_internal.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace {
 
@@ -161,45 +159,6 @@ __global__ __launch_bounds__(1024) void k_rank_tables(const uint32_t *__restrict
         cnt[2 + blockIdx.x] = d ? val[d - 1] : 0u;                 // max value
         cnt[4 + blockIdx.x] = d == 0 ? 0xFFFFFFFFu : val[0] ? val[0] : d > 1 ? val[1] : 0xFFFFFFFFu;  // min positive
     }
-}
-
-// Radix-path keys: (~cpu << 32) | ~mem (descending demands sort ascending), value = the index in
-// the scenario.
-// Also ORs every value into rng[0] (cpu) / rng[1] (mem): one atomic per block and word.
-__global__ __launch_bounds__(256) void k_make_keys(const uint32_t *__restrict__ cpu, const uint32_t *__restrict__ mem,
-                                                   size_t n, uint32_t C, uint64_t *__restrict__ keys,
-                                                   uint32_t *__restrict__ vals, uint32_t *__restrict__ rng) {
-    uint32_t oc = 0, om = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t s = (uint32_t)i / C, j = (uint32_t)i - s * C;  // n = S * C < 2^32
-        const uint32_t c = cpu[i], m = mem[i];
-        keys[i] = ((uint64_t)~c << 32) | (uint32_t)~m;
-        vals[i] = j;
-        oc |= c;
-        om |= m;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        oc |= (uint32_t)__shfl_xor((int)oc, o);
-        om |= (uint32_t)__shfl_xor((int)om, o);
-    }
-    __shared__ uint32_t red[2];
-    if (threadIdx.x < 2) red[threadIdx.x] = 0u;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        atomicOr(&red[0], oc);
-        atomicOr(&red[1], om);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        fp_or_new_bits(&rng[0], red[0]);
-        fp_or_new_bits(&rng[1], red[1]);
-    }
-}
-
-__global__ void k_seg_offsets(uint32_t S, uint32_t C, uint32_t *__restrict__ off) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= S) off[i] = i * C;
 }
 
 __global__ void k_fill_cost(uint32_t S, uint32_t scen_base, uint64_t *__restrict__ cost) {
@@ -892,44 +851,27 @@ extern "C" int fp_debug_sort_stats(unsigned long long *out, int reset) {
 }
 #endif
 
-static inline unsigned grid_for(size_t n, unsigned block) {
-    size_t g = (n + block - 1) / block;
-    if (g > 65535u * 4) g = 65535u * 4;
-    return (unsigned)(g ? g : 1);
-}
-
-// Workspace bytes fp_dev_place_batch takes for S scenarios of C containers x N nodes
-// (sort_tmp: the sorts' scratch share of it).
 // scenarios whose values set the bucket thresholds (k_value_bitmap's sample)
 constexpr uint32_t THR_SAMPLE = 8;
 
-static int place_ws_need(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, size_t *need, size_t *sort_tmp_out) {
-    hipStream_t st = c->stream;
-    const size_t SC = (size_t)S * C;
-    // the radix path sorts full-width u64 keys: device-wide for one scenario, segmented for several
-    size_t sort_tmp = 0, t = 0;
-    FP_HIP(rocprim::radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                     (uint32_t *)nullptr, SC, 0, 64, st));
-    sort_tmp = t;
-    FP_HIP(rocprim::segmented_radix_sort_pairs(nullptr, t, (uint64_t *)nullptr,
-                                               (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                               (uint32_t *)nullptr, (unsigned)SC, S,
-                                               (uint32_t *)nullptr, (uint32_t *)nullptr, 0, 64, st));
-    sort_tmp = t > sort_tmp ? t : sort_tmp;
+// Workspace bytes fp_dev_place_batch takes for S scenarios of C containers x N nodes: the rank tables, the
+// radix FFD order (`fo`; the LDS sort's path takes only an order row, which is less) and the pipeline's share.
+static int place_ws_need(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, size_t *need, fp_ffd_order *fo) {
+    if (int rc = fp_ffd_order_size(c, S, C, 0, fo)) return rc;
     const size_t pipe_ws = fp_pipe_ws_bytes(c, S, C, N);
     if (pipe_ws == 0) return FP_EOVERFLOW;
     const size_t rank_ws = 2 * (2 * RANK_WORDS * 4 + RANK_MAX_VALUE * 4) + CN_WORDS * 4 + 2 * FP_BUCKETS * 4 + 3 * 256
                            + SS_IMG_BYTES + 256;
-    *need = SC * (8 * 2 + 4 * 2) + (S + 1) * 4 + sort_tmp + pipe_ws + rank_ws + 16 * 256;
-    *sort_tmp_out = sort_tmp;
+    *need = rank_ws + fo->bytes + pipe_ws + 2 * 256;
     return FP_OK;
 }
 
 int fp_place_ws_bytes_impl(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint64_t *bytes) {
     if (S == 0 || C == 0) { *bytes = 0; return FP_OK; }
     if ((size_t)S * C > 0xFFFFFFFFull) return FP_EOVERFLOW;
-    size_t need = 0, sort_tmp = 0;
-    if (int rc = place_ws_need(c, S, C, N, &need, &sort_tmp)) return rc;
+    size_t need = 0;
+    fp_ffd_order fo;
+    if (int rc = place_ws_need(c, S, C, N, &need, &fo)) return rc;
     *bytes = need;
     return FP_OK;
 }
@@ -957,17 +899,12 @@ int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b) {
         return FP_EINVAL;
 
     // ---- workspace ----
-    size_t need = 0, sort_tmp = 0;
-    if (int rc0 = place_ws_need(c, S, C, N, &need, &sort_tmp)) return rc0;
+    size_t need = 0;
+    fp_ffd_order fo;
+    if (int rc0 = place_ws_need(c, S, C, N, &need, &fo)) return rc0;
     int rc = fp_ws_reserve(c, need);
     if (rc) return rc;
     fp_ws_reset(c);
-    uint64_t *keys_in = (uint64_t *)fp_ws_take(c, SC * 8);
-    uint64_t *keys_out = (uint64_t *)fp_ws_take(c, SC * 8);
-    uint32_t *vals_in = (uint32_t *)fp_ws_take(c, SC * 4);
-    uint32_t *vals_out = (uint32_t *)fp_ws_take(c, SC * 4);
-    uint32_t *offs = (uint32_t *)fp_ws_take(c, (S + 1) * 4);
-    void *tmp = fp_ws_take(c, sort_tmp + 16);
     // rank tables: bitmaps + prefix counts [2][RANK_WORDS] each, value tables, counts / bounds /
     // eligibility (CN_*), thresholds [2][FP_BUCKETS] -- all device-resident, nothing is read back
     uint32_t *rbm = (uint32_t *)fp_ws_take(c, 2 * RANK_WORDS * 4);
@@ -976,9 +913,7 @@ int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b) {
     uint32_t *rcnt = (uint32_t *)fp_ws_take(c, CN_WORDS * 4);
     uint32_t *thr = (uint32_t *)fp_ws_take(c, 2 * FP_BUCKETS * 4);
     unsigned char *simg = (unsigned char *)fp_ws_take(c, SS_IMG_BYTES);
-    if (!keys_in || !keys_out || !vals_in || !vals_out || !offs || !tmp || !rbm || !rpre || !rval || !rcnt || !thr ||
-        !simg)
-        return FP_ENOMEM;
+    if (!rbm || !rpre || !rval || !rcnt || !thr || !simg) return FP_ENOMEM;
     c->last_rng = rcnt + CN_ORC;
 
     // ---- 1-2: the bucket thresholds (device), from the distinct values and bounds of a sample:
@@ -1012,7 +947,9 @@ int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b) {
         sa.cpu = b->cpu_m; sa.mem = b->mem_mib;
         fp_pipe_soa soa;
         if (int rs = fp_pipe_soa_take(c, SC, &soa)) return rs;
-        sa.order = vals_out; sa.s_cpu = soa.s_cpu; sa.s_mem = soa.s_mem; sa.s_idx = soa.s_idx;
+        uint32_t *order = (uint32_t *)fp_ws_take(c, SC * 4);
+        if (!order) return FP_ENOMEM;
+        sa.order = order; sa.s_cpu = soa.s_cpu; sa.s_mem = soa.s_mem; sa.s_idx = soa.s_idx;
         sa.T = thr;
         sa.scnt = rcnt;
         sa.rng = rcnt + CN_ORC;
@@ -1024,27 +961,16 @@ int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b) {
         k_scen_sort<<<S, 1024, lds, st>>>(sa);
         FP_HIP(hipGetLastError());
         fp_prof_end(c, FP_K_SORT, ev);
-        return fp_pipe_launch(c, S, C, N, b->scen_base, vals_out, nullptr, 4, 0, 0, 0, rval, rval + RANK_MAX_VALUE, b,
+        return fp_pipe_launch(c, S, C, N, b->scen_base, order, nullptr, 4, 0, 0, 0, rval, rval + RANK_MAX_VALUE, b,
                               thr, &soa, rcnt + CN_ORC);
     }
-    // ---- 3b: radix path: key = (~cpu << 32 | ~mem), value = the container's index; a stable
-    // radix sort over all 64 bits gives (cpu desc, mem desc, index asc) without knowing the key
-    // range on the host (FP_OPT_SEGSORT no longer changes anything: several scenarios are always
-    // sorted as segments, one scenario device-wide) ----
+    // ---- 3b: the radix FFD order, which needs no key range on the host (FP_OPT_SEGSORT no longer changes
+    // anything: several scenarios are always sorted as segments, one scenario device-wide) ----
     const uint64_t full = 0xFFFFFFFFull;
-    k_make_keys<<<grid_for(SC, 256), 256, 0, st>>>(b->cpu_m, b->mem_mib, SC, C, keys_in, vals_in, rcnt + CN_ORC);
-    FP_HIP(hipGetLastError());
-    if (S == 1) {
-        FP_HIP(rocprim::radix_sort_pairs(tmp, sort_tmp, keys_in, keys_out, vals_in, vals_out, SC, 0, 64, st));
-    } else {
-        k_seg_offsets<<<(S + 1 + 255) / 256, 256, 0, st>>>(S, C, offs);
-        FP_HIP(hipGetLastError());
-        FP_HIP(rocprim::segmented_radix_sort_pairs(tmp, sort_tmp, keys_in, keys_out, vals_in, vals_out, (unsigned)SC,
-                                                   S, offs, offs + 1, 0, 64, st));
-    }
+    if (int rs = fp_ffd_order_run(c, S, C, b->cpu_m, b->mem_mib, rcnt + CN_ORC, &fo)) return rs;
     fp_prof_end(c, FP_K_SORT, ev);
     // ---- 4-5: placement + cost ----
-    return fp_pipe_launch(c, S, C, N, b->scen_base, vals_out, keys_out, 8, 32, full, full, nullptr, nullptr, b, thr,
+    return fp_pipe_launch(c, S, C, N, b->scen_base, fo.order, fo.keys_out, 8, 32, full, full, nullptr, nullptr, b, thr,
                           nullptr, rcnt + CN_ORC);
 }
 

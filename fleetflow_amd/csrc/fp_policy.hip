@@ -14,9 +14,7 @@
 //                       k_policy_check_domain sets the same word for a domain id of 64 or more in a
 //                       scenario whose max_skew is not 0, and with a fallback chain k_policy_check_hops
 //                       sets it for an n_hops above FP_FALLBACK_MAX_HOPS
-//   2. k_policy_keys  : key (~cpu << 32 | ~mem), value = the index in the scenario; a stable rocprim
-//                       radix sort over 64 bits (segmented per scenario for S > 1) gives the FFD order
-//                       (cpu desc, mem desc, index asc) -- the recipe of fp_place.hip step 3b
+//   2. the radix FFD order (fp_ffd_order.hip): cpu desc, mem desc, index asc per scenario
 //   3. k_policy<BLK,K,SP,FB,QT>: the placer (SP: with the spread constraint; launched when the call gives
 //                       domain and max_skew.  FB: with the fallback chain; launched when the call gives
 //                       relax_mask and n_hops).  The scenario's node state lives in registers for the whole
@@ -78,8 +76,6 @@
 #include "fp_internal.h"
 #include "fp_argmin.h"
 #include <type_traits>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace {
 
@@ -152,20 +148,6 @@ __global__ void k_policy_fill_cost(uint32_t S, uint32_t scen_base, const uint32_
     if (*bad) return;
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < S) cost[s] = fpd::pack_cost(0, 0, scen_base + s);
-}
-
-__global__ __launch_bounds__(256) void k_policy_keys(const uint32_t *__restrict__ cpu, const uint32_t *__restrict__ mem,
-                                                     size_t n, uint32_t C, uint64_t *__restrict__ keys,
-                                                     uint32_t *__restrict__ vals) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        keys[i] = ((uint64_t)~cpu[i] << 32) | (uint32_t)~mem[i];
-        vals[i] = (uint32_t)i % C;  // n = S * C < 2^32
-    }
-}
-
-__global__ void k_policy_offsets(uint32_t S, uint32_t C, uint32_t *__restrict__ off) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= S) off[i] = i * C;
 }
 
 struct PolicyArgs {
@@ -585,27 +567,6 @@ void launch_policy_by(bool sp, bool fb, const PolicyArgs &a, uint32_t S, uint32_
     else launch_policy<false, false, QT>(a, S, N, st);
 }
 
-static inline unsigned grid_for(size_t n, unsigned block) {
-    size_t g = (n + block - 1) / block;
-    if (g > 65535u * 4) g = 65535u * 4;
-    return (unsigned)(g ? g : 1);
-}
-
-// the sorts' scratch bytes for S scenarios of C containers
-int policy_sort_tmp(hipStream_t st, uint32_t S, size_t SC, size_t *bytes) {
-    size_t t = 0;
-    if (S == 1) {
-        FP_HIP(rocprim::radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                         (uint32_t *)nullptr, SC, 0, 64, st));
-    } else {
-        FP_HIP(rocprim::segmented_radix_sort_pairs(nullptr, t, (uint64_t *)nullptr, (uint64_t *)nullptr,
-                                                   (uint32_t *)nullptr, (uint32_t *)nullptr, (unsigned)SC, S,
-                                                   (uint32_t *)nullptr, (uint32_t *)nullptr, 0, 64, st));
-    }
-    *bytes = t;
-    return FP_OK;
-}
-
 }  // namespace
 
 int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy_opts &o) {
@@ -624,11 +585,10 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy
     const bool fb = o.relax_mask && o.n_hops;  // SPEC.md 2.8: either pointer null = no fallback anywhere
     const bool qt = o.quota != nullptr;    // SPEC.md 2.10: null = no quota anywhere; any u32 is a legal cap
 
-    size_t sort_tmp = 0;
+    fp_ffd_order fo = {};
     if (C)
-        if (int rc = policy_sort_tmp(st, S, SC, &sort_tmp)) return rc;
-    const size_t need = SC * (8 * 2 + 4 * 2) + ((size_t)S + 1) * 4 + sort_tmp + 16 + 8 * 256;
-    if (int rc = fp_ws_reserve(c, need)) return rc;
+        if (int rc = fp_ffd_order_size(c, S, C, 0, &fo)) return rc;
+    if (int rc = fp_ws_reserve(c, 256 + fo.bytes)) return rc;  // the bad word, the FFD order
     fp_ws_reset(c);
     uint32_t *bad = (uint32_t *)fp_ws_take(c, 4);
     if (!bad) return FP_ENOMEM;
@@ -650,33 +610,16 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy
         }
         return FP_OK;
     }
-    uint64_t *keys_in = (uint64_t *)fp_ws_take(c, SC * 8);
-    uint64_t *keys_out = (uint64_t *)fp_ws_take(c, SC * 8);
-    uint32_t *vals_in = (uint32_t *)fp_ws_take(c, SC * 4);
-    uint32_t *vals_out = (uint32_t *)fp_ws_take(c, SC * 4);
-    uint32_t *offs = (uint32_t *)fp_ws_take(c, ((size_t)S + 1) * 4);
-    void *tmp = fp_ws_take(c, sort_tmp + 16);
-    if (!keys_in || !keys_out || !vals_in || !vals_out || !offs || !tmp) return FP_ENOMEM;
-
     // ---- FFD order ----
     hipEvent_t ev;
     fp_prof_begin(c, FP_K_SORT, &ev);
-    k_policy_keys<<<grid_for(SC, 256), 256, 0, st>>>(b->cpu_m, b->mem_mib, SC, C, keys_in, vals_in);
-    FP_HIP(hipGetLastError());
-    if (S == 1) {
-        FP_HIP(rocprim::radix_sort_pairs(tmp, sort_tmp, keys_in, keys_out, vals_in, vals_out, SC, 0, 64, st));
-    } else {
-        k_policy_offsets<<<(S + 1 + 255) / 256, 256, 0, st>>>(S, C, offs);
-        FP_HIP(hipGetLastError());
-        FP_HIP(rocprim::segmented_radix_sort_pairs(tmp, sort_tmp, keys_in, keys_out, vals_in, vals_out, (unsigned)SC, S,
-                                                   offs, offs + 1, 0, 64, st));
-    }
+    if (int rc = fp_ffd_order_run(c, S, C, b->cpu_m, b->mem_mib, nullptr, &fo)) return rc;
     fp_prof_end(c, FP_K_SORT, ev);
 
     // ---- placement ----
     PolicyArgs a;
     a.C = C; a.N = N; a.scen_base = b->scen_base;
-    a.order = vals_out;
+    a.order = fo.order;
     a.cpu = b->cpu_m; a.mem = b->mem_mib; a.req = b->req_labels; a.conf = b->conflict;
     a.level = b->level;
     a.cpu_free = b->cpu_free; a.mem_free = b->mem_free; a.conflict_used = b->conflict_used;

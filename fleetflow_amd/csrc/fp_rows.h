@@ -1,0 +1,125 @@
+// fp_rows.h -- the staged buffers of the host-pointer entry points as fp_row lists (fp_layout.h): one row per
+// device buffer, in the order of the takes.  fp_ctx.hip sizes the staging arena from these lists, copies in and
+// copies back by them; nothing else says how many bytes a call stages.  Free of HIP like fp_layout.h, so that
+// the CPU test walks the same lists the library does.
+#pragma once
+#include <stdint.h>
+#include "../../include/fleetplace.h"
+#include "fp_layout.h"
+
+// scored placement (fp_policy.hip, SPEC.md 2.6 to 2.10): what a call has besides its batch.  Not ABI: the
+// exports of fp_ctx.hip fill in the fields their signature has.  Only strategy [S] is required.
+struct fp_policy_opts {
+    const uint32_t *strategy = nullptr, *preferred = nullptr;  // [S] each
+    uint32_t *node_count = nullptr;                            // [S][N], in/out
+    // topology spread (2.7): domain [S][N], max_skew [S]; either one null = no constraint
+    const uint32_t *domain = nullptr, *max_skew = nullptr;
+    // fallback chain (2.8): relax_mask [S][4], n_hops [S]; either one null = no fallback.  hops [S][C]
+    // receives the winner's hop: all zero when the call has no chain
+    const uint32_t *relax_mask = nullptr, *n_hops = nullptr;
+    uint8_t *hops = nullptr;
+    // resource quota (2.10): quota [S][3], null = no quota; quota_used [S][3] (in/out) and quota_why
+    // [S][C] are untouched without quota
+    const uint32_t *quota = nullptr;
+    uint32_t *quota_used = nullptr;
+    uint8_t *quota_why = nullptr;
+};
+
+template <class H, class D>
+static inline fp_row fp_row_in(const H *h, size_t n, D **d) {  // an input; null = absent
+    return {h, nullptr, n * sizeof(H), (void **)d, false};
+}
+template <class H, class D>
+static inline fp_row fp_row_io(H *h, size_t n, D **d) {  // an input that comes back; null = absent
+    return {h, h, n * sizeof(H), (void **)d, false};
+}
+template <class H>
+static inline fp_row fp_row_out(H *h, size_t n, H **d) {  // a result the kernels always write; null = not copied back
+    return {nullptr, h, n * sizeof(H), (void **)d, true};
+}
+template <class H>
+static inline fp_row fp_row_opt(H *h, size_t n, H **d) {  // a result written only when the caller asks for it
+    return {nullptr, h, n * sizeof(H), (void **)d, h != nullptr};
+}
+constexpr int FP_MAX_ROWS = 32;
+
+// A host batch `b` as device batch `d`: its ten input arrays, then (scored placement: `o` and `dopt` non-null)
+// the policy inputs, then assign / reason / cost and the policy outputs the caller asked for.  The node state,
+// node_count and quota_used come back.  Returns the number of rows.
+static inline int fp_batch_rows(const fp_batch *b, const fp_policy_opts *o, fp_batch *d, fp_policy_opts *dopt,
+                                fp_row *r) {
+    const size_t S = b->n_scen, SC = S * b->n_containers, SN = S * b->n_nodes;
+    *d = *b;
+    int n = 0;
+    r[n++] = fp_row_in(b->cpu_m, SC, &d->cpu_m);
+    r[n++] = fp_row_in(b->mem_mib, SC, &d->mem_mib);
+    r[n++] = fp_row_in(b->req_labels, SC, &d->req_labels);
+    r[n++] = fp_row_in(b->conflict, SC, &d->conflict);
+    r[n++] = fp_row_in(b->level, SC, &d->level);
+    r[n++] = fp_row_io(b->cpu_free, SN, &d->cpu_free);
+    r[n++] = fp_row_io(b->mem_free, SN, &d->mem_free);
+    r[n++] = fp_row_in(b->labels, SN, &d->labels);
+    r[n++] = fp_row_io(b->conflict_used, SN, &d->conflict_used);
+    r[n++] = fp_row_in(b->schedulable, SN, &d->schedulable);
+    if (o) {
+        r[n++] = fp_row_in(o->strategy, S, &dopt->strategy);
+        r[n++] = fp_row_in(o->preferred, S, &dopt->preferred);
+        r[n++] = fp_row_io(o->node_count, SN, &dopt->node_count);
+        r[n++] = fp_row_in(o->domain, SN, &dopt->domain);
+        r[n++] = fp_row_in(o->max_skew, S, &dopt->max_skew);
+        r[n++] = fp_row_in(o->relax_mask, S * FP_FALLBACK_MAX_HOPS, &dopt->relax_mask);
+        r[n++] = fp_row_in(o->n_hops, S, &dopt->n_hops);
+        r[n++] = fp_row_in(o->quota, S * FP_QUOTA_DIMS, &dopt->quota);
+        r[n++] = fp_row_io(o->quota_used, S * FP_QUOTA_DIMS, &dopt->quota_used);
+    }
+    r[n++] = fp_row_out(b->assign, SC, &d->assign);
+    r[n++] = fp_row_out(b->reason, SC, &d->reason);
+    r[n++] = fp_row_out(b->cost, S, &d->cost);
+    if (o) {
+        r[n++] = fp_row_opt(o->hops, SC, &dopt->hops);
+        r[n++] = fp_row_opt(o->quota_why, SC, &dopt->quota_why);
+    }
+    return n;
+}
+
+// one scenario's container and node tables as inputs (nine rows, in this order)
+static inline int fp_tables_rows(const fp_containers *cs, const fp_nodes *ns, fp_containers *dc, fp_nodes *dn,
+                                 fp_row *r) {
+    const size_t C = cs->n, N = ns->n;
+    *dc = *cs;
+    *dn = *ns;
+    int n = 0;
+    r[n++] = fp_row_in(cs->cpu_m, C, &dc->cpu_m);
+    r[n++] = fp_row_in(cs->mem_mib, C, &dc->mem_mib);
+    r[n++] = fp_row_in(cs->req_labels, C, &dc->req_labels);
+    r[n++] = fp_row_in(cs->conflict, C, &dc->conflict);
+    r[n++] = fp_row_in(ns->cpu_free, N, &dn->cpu_free);
+    r[n++] = fp_row_in(ns->mem_free, N, &dn->mem_free);
+    r[n++] = fp_row_in(ns->labels, N, &dn->labels);
+    r[n++] = fp_row_in(ns->conflict_used, N, &dn->conflict_used);
+    r[n++] = fp_row_in(ns->schedulable, N, &dn->schedulable);
+    return n;
+}
+
+// fp_drain_sweep: the tables, the live plan, the candidate groups, the counts; then the three results
+struct fp_drain_dev {
+    fp_containers cs;
+    fp_nodes ns;
+    const uint32_t *assign, *group, *node_count;
+    uint32_t *assign_out, *summary;
+    uint8_t *reason_out;
+};
+static inline int fp_drain_rows(const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                const uint32_t *group, uint32_t n_cand, const uint32_t *node_count,
+                                uint32_t *assign_out, uint8_t *reason_out, uint32_t *summary_out, fp_drain_dev *d,
+                                fp_row *r) {
+    const size_t C = cs->n, N = ns->n;
+    int n = fp_tables_rows(cs, ns, &d->cs, &d->ns, r);
+    r[n++] = fp_row_in(assign, C, &d->assign);
+    r[n++] = fp_row_in(group, N, &d->group);
+    r[n++] = fp_row_in(node_count, N, &d->node_count);
+    r[n++] = fp_row_out(assign_out, C, &d->assign_out);
+    r[n++] = fp_row_out(reason_out, C, &d->reason_out);
+    r[n++] = fp_row_out(summary_out, (size_t)n_cand * FP_DRAIN_WORDS, &d->summary);
+    return n;
+}
