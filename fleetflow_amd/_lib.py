@@ -42,6 +42,12 @@ EXPLAIN_HIST_MIXED, EXPLAIN_HIST_FITS, EXPLAIN_HIST_SELECTED, EXPLAIN_HIST_WORDS
 DRAIN_EVICTED, DRAIN_STRANDED, DRAIN_STRANDED_CPU, DRAIN_STRANDED_MEM = 0, 1, 2, 3
 DRAIN_TARGETS, DRAIN_FIRST_STRANDED, DRAIN_NODES, DRAIN_WORDS = 4, 5, 6, 8
 DRAIN_FIELDS = ("evicted", "stranded", "stranded_cpu", "stranded_mem", "targets", "first_stranded", "nodes")
+# scale-out sweep (SPEC.md 2.12): the word indices of a candidate's summary row, their names in order, and the
+# most new servers a candidate may open
+GROW_PENDING, GROW_PLACED, GROW_OPENED, GROW_UNPLACEABLE, GROW_CAPPED = 0, 1, 2, 3, 4
+GROW_LEFT_CPU, GROW_LEFT_MEM, GROW_FIRST_UNPLACED, GROW_WORDS = 5, 6, 7, 8
+GROW_FIELDS = ("pending", "placed", "opened", "unplaceable", "capped", "left_cpu", "left_mem", "first_unplaced")
+GROW_MAX_NEW = 8192
 # context options (fleetplace.h enum fp_option); FP_OPT_AUTO = the production default
 # ("segsort" is ignored by the library and kept for ABI stability)
 FP_OPT_AUTO = -1
@@ -147,6 +153,10 @@ SIGNATURES = {
                                   ct.c_uint32, ct.c_uint32, u32p, u32p, u8p, u32p]),
     "fp_dev_drain_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, vp, ct.c_uint32,
                                       ct.c_uint32, ct.c_uint32, vp, vp, vp, vp]),
+    "fp_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), u8p, ct.c_uint32, ct.c_uint32, u32p, u32p, u32p, u32p,
+                                 ct.c_uint32, u32p, u32p]),
+    "fp_dev_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), vp, ct.c_uint32, ct.c_uint32, vp, vp, vp, vp,
+                                     ct.c_uint32, vp, vp]),
     "fp_dev_argmin_cost": (ct.c_int, [vp, vp, ct.c_uint32, vp]),
     "fp_dev_gen_batch": (ct.c_int, [vp, ct.c_uint64, ct.POINTER(FpBatch), ct.c_uint32]),
 }

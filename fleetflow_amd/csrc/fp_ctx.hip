@@ -787,3 +787,39 @@ extern "C" int fp_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes
         return rc;
     return copy_back_all(c, rows, n);
 }
+
+// scale-out sweep (SPEC.md 2.12, fp_grow.hip)
+extern "C" int fp_dev_grow_sweep(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
+                                 uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                                 const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out) {
+    if (!c || !cs) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_grow_sweep_impl(c, cs, reason, reason_mask, n_cand, t_cpu, t_mem, t_labels, t_max,
+                                                 max_new, summary_out, assign_out));
+}
+
+extern "C" int fp_grow_sweep(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
+                             uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                             const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out) {
+    if (!c || !cs) return FP_EINVAL;
+    const size_t C = cs->n;
+    if (n_cand > 65535u || max_new > FP_GROW_MAX_NEW) return FP_EOVERFLOW;
+    if (reason_mask && !reason) return FP_EINVAL;
+    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict)) return FP_EINVAL;
+    if (n_cand && (!t_cpu || !t_mem || !t_labels || !summary_out)) return FP_EINVAL;
+    for (size_t k = 0; t_max && k < n_cand; ++k)
+        if (t_max[k] > max_new) return FP_EINVAL;
+    if (n_cand == 0) return FP_OK;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_grow_dev d;
+    const int n = fp_grow_rows(cs, reason, reason_mask, n_cand, t_cpu, t_mem, t_labels, t_max, summary_out, assign_out,
+                               &d, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = fp_dev_grow_sweep_impl(c, &d.cs, d.reason, reason_mask, n_cand, d.t_cpu, d.t_mem, d.t_labels, d.t_max,
+                                        max_new, d.summary, d.assign_out))
+        return rc;
+    return copy_back_all(c, rows, n);
+}

@@ -180,6 +180,12 @@ int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
                             const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
                             uint32_t *summary_out);
 
+// scale-out sweep (fp_grow.hip, SPEC.md 2.12); every pointer is device memory, max_new a host value.  A t_max
+// value above max_new is found on the device (FP_EINVAL in the context's error word, nothing written)
+int fp_dev_grow_sweep_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
+                           uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                           const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
+
 // tile-pipeline FFD (fp_pipe.hip)
 bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint32_t *W_out, uint32_t *B_out,
                   size_t *lds_out);

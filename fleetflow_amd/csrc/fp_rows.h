@@ -123,3 +123,31 @@ static inline int fp_drain_rows(const fp_containers *cs, const fp_nodes *ns, con
     r[n++] = fp_row_out(summary_out, (size_t)n_cand * FP_DRAIN_WORDS, &d->summary);
     return n;
 }
+
+// fp_grow_sweep: the requests, the reasons (absent without a mask), the templates; then the two results
+struct fp_grow_dev {
+    fp_containers cs;
+    const uint8_t *reason;
+    const uint32_t *t_cpu, *t_mem, *t_labels, *t_max;
+    uint32_t *summary, *assign_out;
+};
+static inline int fp_grow_rows(const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask, uint32_t n_cand,
+                               const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                               const uint32_t *t_max, uint32_t *summary_out, uint32_t *assign_out, fp_grow_dev *d,
+                               fp_row *r) {
+    const size_t C = cs->n, K = n_cand;
+    d->cs = *cs;
+    int n = 0;
+    r[n++] = fp_row_in(cs->cpu_m, C, &d->cs.cpu_m);
+    r[n++] = fp_row_in(cs->mem_mib, C, &d->cs.mem_mib);
+    r[n++] = fp_row_in(cs->req_labels, C, &d->cs.req_labels);
+    r[n++] = fp_row_in(cs->conflict, C, &d->cs.conflict);
+    r[n++] = fp_row_in(reason_mask ? reason : nullptr, C, &d->reason);
+    r[n++] = fp_row_in(t_cpu, K, &d->t_cpu);
+    r[n++] = fp_row_in(t_mem, K, &d->t_mem);
+    r[n++] = fp_row_in(t_labels, K, &d->t_labels);
+    r[n++] = fp_row_in(t_max, K, &d->t_max);
+    r[n++] = fp_row_out(summary_out, K * FP_GROW_WORDS, &d->summary);
+    r[n++] = fp_row_opt(assign_out, K * C, &d->assign_out);
+    return n;
+}

@@ -15,6 +15,8 @@ the same:
 * ``levelize_stage`` / ``plan_stage``: the new planner outputs (SPEC.md 2).
 * ``drain_stage``: which servers, or zones, of a stage that runs as a plan says can be taken out
   (SPEC.md 2.11; the `drain` scheduling state of controlplane model.rs:435-442).
+* ``grow_stage``: the new servers of each template of a catalogue that a plan's NOFIT services need
+  (SPEC.md 2.12).
 
 Strings never cross the C ABI: names are mapped to u32 ids in stage order here.
 """
@@ -696,6 +698,85 @@ def drain_stage(flow: Flow, stage_name: str, plan: Plan, by: str | None = None, 
         report.candidates.append(DrainCandidate(name, [s for s, g in zip(slugs, group) if g == k], moves, stranded,
                                                 row[DRAIN_EVICTED], row[DRAIN_STRANDED_CPU], row[DRAIN_STRANDED_MEM],
                                                 row[DRAIN_TARGETS]))
+    return report
+
+
+@dataclass
+class GrowCandidate:
+    """One candidate of a scale-out sweep (SPEC.md 2.12): a server template and what adding servers of it does
+    for the plan's unplaced services."""
+    name: str
+    cpu_m: int
+    mem_mib: int
+    labels: list[str]                      # the template's labels the stage knows; others are dropped
+    max_new: int = 0                       # the most new servers the candidate could open
+    pending: int = 0                       # the eight words of the summary row
+    placed: int = 0
+    opened: int = 0
+    unplaceable: int = 0
+    capped: int = 0
+    left_cpu_m: int = 0
+    left_mem_mib: int = 0
+    first_unplaced: str | None = None      # the first service in visiting order that gets no server
+    # the services of each new server in visiting order (cpu desc, mem desc, stage order); None where the
+    # candidate was not detailed
+    servers: list[list[str]] | None = None
+
+
+@dataclass
+class GrowReport:
+    """``grow_stage``'s answer: one GrowCandidate per template of the catalogue, every one computed
+    independently for the same pending services."""
+    stage: str
+    max_new: int = 0
+    pending: list[str] = field(default_factory=list)  # the plan's NOFIT services, stage order
+    candidates: list[GrowCandidate] = field(default_factory=list)
+
+
+def grow_stage(flow: Flow, stage_name: str, plan: Plan, catalogue: list[Server], max_new: int = 64,
+               planner: Planner | None = None) -> GrowReport:
+    """"What do I have to add?" for a stage planned as ``plan`` says (SPEC.md 2.12): the pending services are
+    the plan's NOFIT rejections, with their full required labels, and every ``Server`` of ``catalogue``
+    (``registry.plan_template``) is a template of which up to ``max_new`` new servers may be opened, first
+    fit.  Template labels go through the stage's label dictionary; a label nothing in the stage uses is
+    dropped.  One ``Planner.grow_sweep`` covers the catalogue; a second one, with the per-server lists,
+    covers the templates that place every pending service or, when none does, the one that places the most
+    (the first of them in catalogue order)."""
+    from ._lib import (GROW_CAPPED, GROW_FIRST_UNPLACED, GROW_LEFT_CPU, GROW_LEFT_MEM, GROW_OPENED, GROW_PENDING,
+                       GROW_PLACED, GROW_UNPLACEABLE, REASON_NOFIT, REASON_OK)
+    p = planner or default_planner()
+    stage = flow.stages[stage_name]
+    names = list(dict.fromkeys(stage.services))
+    nodes = _server_nodes(flow, stage.servers)
+    cont, _ = _stage_tables(names, flow, nodes, plan.preferred)
+    ld = _stage_labels(names, flow, nodes, plan.preferred)
+    reason = [REASON_NOFIT if plan.rejected.get(n) == "NOFIT" else REASON_OK for n in names]
+    report = GrowReport(stage_name, int(max_new), [n for n, r in zip(names, reason) if r == REASON_NOFIT])
+    if not catalogue:
+        return report
+    known = [[lab for lab in t.labels if lab in ld.bits] for t in catalogue]
+    tpl = ([t.cpu_m for t in catalogue], [t.mem_mib for t in catalogue], [ld.mask(k) for k in known])
+    summary, _ = p.grow_sweep(cont, reason, tpl, max_new)
+    for t, labs, row in zip(catalogue, known, summary):
+        row = [int(x) for x in row]
+        first = row[GROW_FIRST_UNPLACED]
+        report.candidates.append(GrowCandidate(
+            t.slug, t.cpu_m, t.mem_mib, labs, int(max_new), row[GROW_PENDING], row[GROW_PLACED], row[GROW_OPENED],
+            row[GROW_UNPLACEABLE], row[GROW_CAPPED], row[GROW_LEFT_CPU], row[GROW_LEFT_MEM],
+            names[first] if first != NONE else None))
+    if not report.pending:
+        return report
+    detail = [k for k, c in enumerate(report.candidates) if c.placed == c.pending]
+    if not detail:
+        detail = [max(range(len(catalogue)), key=lambda k: (report.candidates[k].placed, -k))]
+    _, assign = p.grow_sweep(cont, reason, tuple([x[k] for k in detail] for x in tpl), max_new, want_assign=True)
+    visit = sorted((v for v, r in enumerate(reason) if r == REASON_NOFIT), key=lambda v: (-cont[0][v], -cont[1][v], v))
+    for k, row in zip(detail, assign):
+        c = report.candidates[k]
+        c.servers = [[] for _ in range(c.opened)]
+        for v in visit:
+            if int(row[v]) != NONE:
+                c.servers[int(row[v])].append(names[v])
     return report
 
 

@@ -15,6 +15,10 @@ absent without a quota.
 and ``drain_report_to_json`` / ``drain_report_from_json`` carry it as
 ``{stage, by, placement: {strategy, preferred}, candidates: [{name, servers, moves, stranded, ...}]}``.
 
+``format_grow_report`` prints a scale-out sweep (SPEC.md 2.12, ``flow.grow_stage``), one line per template with
+the services of each new server indented under it where the candidate was detailed, and ``grow_report_to_json``
+/ ``grow_report_from_json`` carry it as ``{stage, max_new, pending, candidates: [{name, cpu_m, ...}]}``.
+
 ``format_up_dry_run`` / ``format_deploy_dry_run`` reproduce the reference's
 ``fleet up --dry-run`` (crates/fleetflow/src/commands/up.rs:57-136) and
 ``fleet deploy --dry-run`` (crates/fleetflow/src/commands/deploy.rs:14-100)
@@ -32,7 +36,7 @@ import json
 from dataclasses import asdict
 
 from ._lib import QUOTA_NAMES
-from .flow import U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, Plan, Why
+from .flow import U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, GrowCandidate, GrowReport, Plan, Why
 from .parser import FlowError
 
 
@@ -110,6 +114,32 @@ def drain_report_from_json(text: str) -> DrainReport:
                             c.get("evicted", 0), c.get("stranded_cpu_m", 0), c.get("stranded_mem_mib", 0),
                             c.get("targets", 0)) for c in d.get("candidates") or []]
     return DrainReport(d["stage"], d.get("by"), pol.get("strategy"), list(pol.get("preferred") or []), cands)
+
+
+def format_grow_report(report: GrowReport) -> str:
+    """One line per template, ``grow <name>: <opened> new servers take <placed> of <pending> services, <u> fit
+    no such server, <c> over the cap of <max>``, with the services of each new server (``+<ordinal>: a, b``)
+    indented under it where the candidate was detailed."""
+    lines = []
+    for c in report.candidates:
+        lines.append(f"grow {c.name}: {c.opened} new servers take {c.placed} of {c.pending} services, "
+                     f"{c.unplaceable} fit no such server, {c.capped} over the cap of {c.max_new}")
+        lines += [f"  +{j}: {', '.join(svcs)}" for j, svcs in enumerate(c.servers or [])]
+    return "\n".join(lines)
+
+
+def grow_report_to_json(report: GrowReport, indent: int | None = None) -> str:
+    d = {"stage": report.stage, "max_new": report.max_new, "pending": report.pending,
+         "candidates": [asdict(c) for c in report.candidates]}
+    return json.dumps(d, ensure_ascii=False, indent=indent)
+
+
+def grow_report_from_json(text: str) -> GrowReport:
+    d = json.loads(text)
+    cands = [GrowCandidate(**{**c, "labels": list(c["labels"]),
+                              "servers": None if c.get("servers") is None else [list(s) for s in c["servers"]]})
+             for c in d.get("candidates") or []]
+    return GrowReport(d["stage"], d.get("max_new", 0), list(d.get("pending") or []), cands)
 
 
 def get_network_name(project: str, stage: str) -> str:

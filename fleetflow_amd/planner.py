@@ -590,7 +590,70 @@ class Planner:
             nc[n:n + 1] += np.uint32(1)
         return out, reason, nodes, nc, summary[0]
 
+    def grow_sweep(self, cont, reason, templates, max_new, reason_mask=1 << _lib.REASON_NOFIT, t_max=None,
+                   want_assign=False):
+        """Scale-out sweep (SPEC.md 2.12, fp_grow_sweep): the pending containers are those of ``cont`` whose
+        ``reason`` [C] has its bit set in ``reason_mask`` (0 = every container, ``reason`` may be None);
+        ``templates`` = (t_cpu, t_mem, t_labels), one entry per candidate server template.  Every candidate
+        is computed independently: first fit of the pending containers on ``t_max[k]`` (None = ``max_new``
+        everywhere; ``max_new`` <= GROW_MAX_NEW) empty servers of the template.  Inputs are not mutated.
+        Returns (summary [n_cand, 8], assign): summary's word indices are _lib.GROW_*, and assign is
+        [n_cand, C] with ``want_assign`` (the ordinal of the new server of a placed pending container, NONE
+        for every other one), else None."""
+        cont = tuple(_u32(x) for x in cont)
+        C = cont[0].size
+        self._need(len(cont) == 4 and all(x.size == C for x in cont), "every container array must hold C entries")
+        tpl = tuple(_u32(x).reshape(-1) for x in templates)
+        self._need(len(tpl) == 3, "templates must be (t_cpu, t_mem, t_labels)")
+        n_cand = tpl[0].size
+        self._need(all(x.size == n_cand for x in tpl), "every template array must hold n_cand entries")
+        rs = _u8(reason) if reason is not None else None
+        reason_mask, max_new = int(reason_mask), int(max_new)
+        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
+        self._need(reason_mask == 0 or rs is None or rs.size == C, "reason must hold C entries")
+        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
+        tm = _u32(t_max).reshape(-1) if t_max is not None else None
+        self._need(tm is None or tm.size == n_cand, "t_max must hold n_cand entries")
+        summary = np.empty((n_cand, _lib.GROW_WORDS), np.uint32)
+        assign = np.empty((n_cand, C), np.uint32) if want_assign else None
+        cs = FpContainers(C, *(_ptr(x) for x in cont))
+        check(self._L.fp_grow_sweep(self._ctx, ct.byref(cs), _arg(rs if reason_mask else None), reason_mask, n_cand,
+                                    _arg(tpl[0]), _arg(tpl[1]), _arg(tpl[2]), _arg(tm), max_new, _arg(summary),
+                                    _arg(assign)), "fp_grow_sweep")
+        return summary, assign
+
     # -- device-pointer API -------------------------------------------------------------
+    def dev_grow_sweep(self, cont_t, reason_t, templates_t, max_new, summary_t, reason_mask=1 << _lib.REASON_NOFIT,
+                       t_max_t=None, assign_out_t=None):
+        """fp_dev_grow_sweep on device tensors: ``cont_t`` = (cpu, mem, req, conf) [C] each (int32 storage of
+        u32 values), ``reason_t`` [C] uint8 or None (``reason_mask`` 0), ``templates_t`` = (t_cpu, t_mem,
+        t_labels) [n_cand] each, ``t_max_t`` [n_cand] or None; out: ``summary_t`` [n_cand * 8] and
+        ``assign_out_t`` [n_cand * C] or None.  ``max_new`` is a host value.  A t_max above max_new is found
+        on the device: nothing is written and sync() raises FP_EINVAL."""
+        C = cont_t[0].numel()
+        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
+                   "every container tensor must hold C 32-bit entries")
+        self._need(len(templates_t) == 3, "templates_t must be (t_cpu, t_mem, t_labels)")
+        n_cand = templates_t[0].numel()
+        self._need(all(t.numel() == n_cand and t.element_size() == 4 for t in templates_t),
+                   "every template tensor must hold n_cand 32-bit entries")
+        reason_mask, max_new = int(reason_mask), int(max_new)
+        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
+        self._need(reason_mask == 0 or reason_t is None or (reason_t.numel() == C and reason_t.element_size() == 1),
+                   "reason_t must hold C bytes")
+        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
+        self._need(t_max_t is None or (t_max_t.numel() == n_cand and t_max_t.element_size() == 4),
+                   "t_max_t must hold n_cand 32-bit entries")
+        self._need(summary_t.numel() == n_cand * _lib.GROW_WORDS and summary_t.element_size() == 4,
+                   "summary_t must hold n_cand * 8 32-bit entries")
+        self._need(assign_out_t is None or (assign_out_t.numel() == n_cand * C and assign_out_t.element_size() == 4),
+                   "assign_out_t must hold n_cand * C 32-bit entries")
+        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
+        self._dev(lambda: check(self._L.fp_dev_grow_sweep(
+            self._ctx, ct.byref(cs), _arg(reason_t if reason_mask else None), reason_mask, n_cand,
+            *(_arg(t) for t in templates_t), _arg(t_max_t), max_new, _arg(summary_t), _arg(assign_out_t)),
+            "fp_dev_grow_sweep"))
+
     def dev_drain_sweep(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t, strategy=0,
                         preferred=0, count_t=None):
         """fp_dev_drain_sweep on device tensors: ``cont_t`` = (cpu, mem, req, conf) [C] each and ``nodes_t`` =

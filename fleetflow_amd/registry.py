@@ -86,6 +86,16 @@ def server_from_row(row: dict) -> Server:
                   plan=row.get("plan"), draining=sched == DRAIN)
 
 
+def plan_template(plan: str | None, labels: dict | None = None, name: str | None = None) -> Server:
+    """A server template for ``flow.grow_stage`` (SPEC.md 2.12) from a provider plan string: ``parse_plan``'s
+    cores * 1000 millicores and GB * 1024 MiB (provider.rs:15-30), and the ServerLabels a new server of the
+    plan would carry (model.rs:399-411) as ``server_labels`` renders them.  ``name`` defaults to the plan
+    string."""
+    cores, gb = parse_plan(plan)
+    return Server(slug=name if name is not None else str(plan), cpu_m=_clamp_u32(cores * 1000),
+                  mem_mib=_clamp_u32(gb * 1024), labels=server_labels(labels), plan=plan)
+
+
 def node_table(rows: list[dict]) -> list[Server]:
     """db.rs:741-750: live rows (``deleted_at`` None) in slug order."""
     live = [r for r in rows if r.get("deleted_at") is None]

@@ -29,6 +29,10 @@
  *   fp_drain_sweep    <- new: evacuate each server, or each topology domain, from a live plan: the `drain`
  *                        scheduling state, under which existing placements leave as well (`cordon` only
  *                        stops new ones)  crates/fleetflow-controlplane/src/model.rs:435-442
+ *   fp_grow_sweep     <- new: the new servers of each template (a plan string's size,
+ *                        crates/fleetflow-cloud-sakura/src/provider.rs:15-30, with the ServerLabels /
+ *                        ServerCapacity a new server would carry, crates/fleetflow-controlplane/src/model.rs:399-419)
+ *                        that a plan's unplaced containers need
  *
  * Conventions
  *   - All buffers are caller-owned; no allocation crosses the ABI.
@@ -367,6 +371,30 @@ enum { FP_DRAIN_EVICTED = 0, FP_DRAIN_STRANDED = 1, FP_DRAIN_STRANDED_CPU = 2, F
 int fp_drain_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
                    const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
                    const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out, uint32_t *summary_out);
+/* Scale-out sweep (SPEC.md 2.12): "what do I have to add?", asked of every server template at once.  The pending
+ * containers are those whose reason's bit is set in reason_mask (fp_explain_batch's convention; reason_mask == 0
+ * selects every container and reason is not read and may be NULL).  Candidate k is a template: a new server has
+ * cpu_free = t_cpu[k], mem_free = t_mem[k], labels = t_labels[k] (a plan string's size, provider.rs:15-30; the
+ * labels and capacity a new server carries, model.rs:399-419), conflict_used = 0 and is schedulable.  Every
+ * candidate is computed independently: fp_place of the pending containers on t_max[k] such servers (t_max NULL =
+ * max_new for every candidate; max_new <= FP_GROW_MAX_NEW is the most any candidate may open).  The servers are
+ * identical, so the used ones are [0, OPENED).  summary_out holds one row of FP_GROW_WORDS u32 per candidate:
+ *   PENDING  the number pending (the same in every row)     PLACED  those that got a new server
+ *   OPENED   new servers used                                UNPLACEABLE  pending that no such server can take
+ *   CAPPED   the rest: room ran out within t_max[k]          (cpu_m > t_cpu || mem_mib > t_mem || labels missing)
+ *   LEFT_CPU, LEFT_MEM  what is free on the OPENED servers at the end (u32, wrap)
+ *   FIRST_UNPLACED  the first container in visiting order that is UNPLACEABLE or CAPPED, else FP_NONE
+ * PENDING == PLACED + UNPLACEABLE + CAPPED.  assign_out (nullable) is [n_cand][c->n]: the ordinal in [0, OPENED)
+ * of the new server a placed pending container got, FP_NONE for every other container.  No input is written.
+ * n_cand > 65535 or max_new > FP_GROW_MAX_NEW is FP_EOVERFLOW; reason == NULL with reason_mask != 0 and a
+ * t_max[k] > max_new are FP_EINVAL; on any error nothing is written.  Only first fit; preferred labels, the
+ * spread constraint, the fallback chain and the quota are not applied. */
+enum { FP_GROW_PENDING = 0, FP_GROW_PLACED = 1, FP_GROW_OPENED = 2, FP_GROW_UNPLACEABLE = 3, FP_GROW_CAPPED = 4,
+       FP_GROW_LEFT_CPU = 5, FP_GROW_LEFT_MEM = 6, FP_GROW_FIRST_UNPLACED = 7, FP_GROW_WORDS = 8 };
+#define FP_GROW_MAX_NEW 8192u
+int fp_grow_sweep(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
+                  uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                  const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
 /* One stage's whole plan, the `fleet up --dry-run` path (crates/fleetflow/src/commands/up.rs:57-136):
  *   perm_out                 A1 legacy start order (engine.rs:64-85, as fp_legacy_order)
  *   level_out, order_out, n_cycle_out   A2 levels and start order (as fp_levelize)
@@ -444,6 +472,12 @@ int fp_dev_drain_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *node
                        const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
                        const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
                        uint32_t *summary_out);
+/* As fp_grow_sweep on device pointers (max_new stays a host value: the kernel's geometry follows it, nothing is
+ * read back).  A t_max[k] > max_new is found on the device before any store: nothing is written and fp_ctx_sync()
+ * reports FP_EINVAL.  The call takes 28 bytes per container plus the sort's scratch from the context's workspace. */
+int fp_dev_grow_sweep(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
+                      uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                      const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

@@ -56,6 +56,17 @@ pub const FP_DRAIN_TARGETS: usize = 4;
 pub const FP_DRAIN_FIRST_STRANDED: usize = 5;
 pub const FP_DRAIN_NODES: usize = 6;
 pub const FP_DRAIN_WORDS: usize = 8;
+// scale-out sweep (SPEC.md 2.12): the word indices of a candidate's summary row, and the most new servers
+pub const FP_GROW_PENDING: usize = 0;
+pub const FP_GROW_PLACED: usize = 1;
+pub const FP_GROW_OPENED: usize = 2;
+pub const FP_GROW_UNPLACEABLE: usize = 3;
+pub const FP_GROW_CAPPED: usize = 4;
+pub const FP_GROW_LEFT_CPU: usize = 5;
+pub const FP_GROW_LEFT_MEM: usize = 6;
+pub const FP_GROW_FIRST_UNPLACED: usize = 7;
+pub const FP_GROW_WORDS: usize = 8;
+pub const FP_GROW_MAX_NEW: u32 = 8192;
 pub const FP_K_PLACE: c_int = 0;
 pub const FP_K_SORT: c_int = 1;
 pub const FP_K_FEAS: c_int = 2;
@@ -218,6 +229,9 @@ unsafe extern "C" {
                           group: *const u32, n_cand: u32, strategy: u32, preferred_labels: u32,
                           node_count: *const u32, assign_out: *mut u32, reason_out: *mut u8,
                           summary_out: *mut u32) -> c_int;
+    pub fn fp_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32, n_cand: u32,
+                         t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32, t_max: *const u32,
+                         max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,
                          perm_out: *mut u32, level_out: *mut u32, order_out: *mut u32, n_cycle_out: *mut u32,
                          first_out: *mut u32, count_out: *mut u32, assign_out: *mut u32, reason_out: *mut u8)
@@ -255,6 +269,9 @@ unsafe extern "C" {
                               group: *const u32, n_cand: u32, strategy: u32, preferred_labels: u32,
                               node_count: *const u32, assign_out: *mut u32, reason_out: *mut u8,
                               summary_out: *mut u32) -> c_int;
+    pub fn fp_dev_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
+                             n_cand: u32, t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32,
+                             t_max: *const u32, max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
     pub fn fp_dev_argmin_cost(ctx: *mut fp_ctx, cost: *const u64, n: u32, best_dev: *mut u32) -> c_int;
     pub fn fp_dev_gen_batch(ctx: *mut fp_ctx, seed: u64, b: *const fp_batch, flags: u32) -> c_int;
 }

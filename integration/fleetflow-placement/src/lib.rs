@@ -162,6 +162,35 @@ impl Planner {
         Ok((out, reason, rows))
     }
 
+    /// Scale-out sweep (SPEC.md 2.12, fleetplace.h `fp_grow_sweep`): the pending containers are those whose
+    /// `reason` has its bit set in `reason_mask` (0 = every container, `reason` may be None); candidate k is a
+    /// server template (`t_cpu[k]`, `t_mem[k]`, `t_labels[k]`) of which at most `t_max[k]` (None = `max_new`
+    /// <= `ffi::FP_GROW_MAX_NEW`) are opened, first fit.  No input is changed.  Returns one row of
+    /// `ffi::FP_GROW_WORDS` words per candidate and, with `want_assign`, the ordinal of the new server per
+    /// candidate and container (`ffi::FP_NONE` = none), candidate-major.
+    #[allow(clippy::too_many_arguments)]
+    pub fn grow_sweep(&mut self, c: &Containers, reason: Option<&[u8]>, reason_mask: u32, t_cpu: &[u32], t_mem: &[u32],
+                      t_labels: &[u32], t_max: Option<&[u32]>, max_new: u32, want_assign: bool)
+                      -> Result<(Vec<[u32; ffi::FP_GROW_WORDS]>, Option<Vec<u32>>), PlanError> {
+        let (n, k) = (c.cpu_m.len(), t_cpu.len());
+        if !c.all_len(n) || t_mem.len() != k || t_labels.len() != k || t_max.map_or(false, |m| m.len() != k)
+            || (reason_mask != 0 && reason.map_or(true, |r| r.len() != n)) {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        let mut rows = vec![[0u32; ffi::FP_GROW_WORDS]; k];
+        let mut assign = if want_assign { Some(vec![ffi::FP_NONE; k * n]) } else { None };
+        let reason_ptr = if reason_mask != 0 { reason.map_or(std::ptr::null(), |r| r.as_ptr()) } else { std::ptr::null() };
+        check(unsafe {
+            ffi::fp_grow_sweep(self.ctx, &cs, reason_ptr, reason_mask, k as u32, t_cpu.as_ptr(), t_mem.as_ptr(),
+                               t_labels.as_ptr(), t_max.map_or(std::ptr::null(), |m| m.as_ptr()), max_new,
+                               rows.as_mut_ptr() as *mut u32,
+                               assign.as_mut().map_or(std::ptr::null_mut(), |a| a.as_mut_ptr()))
+        })?;
+        Ok((rows, assign))
+    }
+
     /// Scored placement (SPEC.md 2.6, fleetplace.h `fp_place_policy`): `strategy` is one of
     /// `ffi::FP_STRATEGY_*`, `preferred_labels` the soft preferred-label mask, `node_count` the
     /// containers already on each node (updated in place; None starts at zero).  `nodes` is
