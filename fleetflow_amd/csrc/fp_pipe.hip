@@ -350,6 +350,25 @@ constexpr uint32_t SYS_MAX_G = 4;
 #ifndef FPP_MASK_UPKEEP
 #define FPP_MASK_UPKEEP 0
 #endif
+// The packed 4096-scenario kernel (bigp: one wave, 12 groups, PK; fp_pipe_tus.h names it by WV = 7):
+// FPP_BIGP_NOMASK 1: no bucket masks.  A group is a candidate when the batch corner holds a node
+//   (e != 0).  With the upkeep off the masks stay at the tile's start state, and a batch of 64
+//   consecutive containers in FFD order has one or two cpu values and a narrow mem range, so the exact
+//   corner says nearly all they said; it is still a superset of the feasible groups (same plans).  The
+//   mask build at the tile's start, the two mask loads per group and prescan and 6144 B of LDS per
+//   workgroup go: LDS no longer caps the residency at 26 workgroups per CU.  0: masks as in the u32 twin.
+// FPP_BIGP_WAVES: the waves per SIMD it is compiled for (7: 7168 resident segments, so config 4's
+//   4096 x 7 segments are exactly four rounds; 6 with the masks gone: profiles/r12a_bigp_steps_ab.jsonl).
+#ifndef FPP_BIGP_NOMASK
+#define FPP_BIGP_NOMASK 1
+#endif
+#ifndef FPP_BIGP_WAVES
+#define FPP_BIGP_WAVES 7
+#endif
+constexpr uint32_t BIGP_WV = 7;  // the WV that names bigp in fp_pipe_tus.h
+constexpr bool is_bigp(uint32_t G, uint32_t BLK, uint32_t WV, bool PK) {
+    return G == 12 && BLK == 64 && WV == BIGP_WV && PK;
+}
 #ifndef FPP_PK_SYS_MAX_G
 #define FPP_PK_SYS_MAX_G 4
 #endif
@@ -502,7 +521,11 @@ constexpr uint32_t WIDE_WAVES = 3, WIDE12_WAVES = 5;
 // FFD 14.93-14.95 vs 15.20-15.23 ms; at 2048 it loses (10.21-10.35 vs 9.87-9.90), the spills costing
 // more than the extra slots buy (profiles/r04x_waves_ab.jsonl).  The 8-group segments of batches of up to
 // 1024 scenarios stay at five waves (k_ffd_pipe<8, 1024>, 82 VGPRs): six or seven waves ran 1024
-// scenarios 8.69 / 9.18 vs 8.46-8.54 ms (profiles/r04ab_small8_waves_ab.jsonl)
+// scenarios 8.69 / 9.18 vs 8.46-8.54 ms (profiles/r04ab_small8_waves_ab.jsonl).
+// The packed twin of that instantiation (bigp) runs without bucket masks at seven waves per SIMD
+// (FPP_BIGP_NOMASK / FPP_BIGP_WAVES above: 72 VGPRs, 60 B of scratch outside the batch loop, 7168
+// resident segments): config-4 FFD 10.30-10.32 -> 9.83-9.85 (no masks, six waves) -> 9.64-9.66 ms
+// (profiles/r12_bigp_nomask_waves_ab.jsonl); WIDE12_BIG_WAVES is the u32 kernel's
 #ifndef FPP_BIG_WAVES
 #define FPP_BIG_WAVES 6
 #endif
@@ -518,7 +541,11 @@ constexpr uint32_t WIDE_WAVES = 3, WIDE12_WAVES = 5;
 // round 4: per-group capacity bounds in place of the corner ballots (15.73 vs 15.08
 // ms, r03af), req / conf of link input loaded after the prescan (15.45 vs 15.08 ms, r03ac).
 template <uint32_t G, uint32_t BLK, uint32_t WV = 0, bool PK = false>
-__global__ __launch_bounds__(BLK, BLK == 64 ? (WV ? WV : G == 12 ? WIDE12_WAVES : WIDE_WAVES) : 1) void
+__global__ __launch_bounds__(BLK, BLK == 64 ? (is_bigp(G, BLK, WV, PK) ? FPP_BIGP_WAVES
+                                                : WV   ? WV
+                                                : G == 12 ? WIDE12_WAVES
+                                                          : WIDE_WAVES)
+                                               : 1) void
 k_ffd_pipe(const PipeArgs a_arg) {
     // the arguments are read through the kernarg segment (memory), not promoted to SGPRs for the
     // whole kernel: held in SGPRs they spilled into VGPR lanes (wide kernel: 781 v_readlane vs 296,
@@ -544,8 +571,10 @@ k_ffd_pipe(const PipeArgs a_arg) {
     // per-lane group bit sets (schedulable / candidate groups): 64-bit above 32 groups
     using GM = typename std::conditional<(G > 32), uint64_t, uint32_t>::type;
 
+    // NM: bigp without bucket masks (FPP_BIGP_NOMASK): the M region is empty
+    constexpr bool NM = is_bigp(G, BLK, WV, PK) && FPP_BIGP_NOMASK;
     uint64_t *M = reinterpret_cast<uint64_t *>(smem);
-    uint32_t *CTL = reinterpret_cast<uint32_t *>(M + (size_t)W * G * K * 2);
+    uint32_t *CTL = reinterpret_cast<uint32_t *>(M + (NM ? 0 : (size_t)W * G * K * 2));
     uint32_t *CNT = CTL + (W - 1) * 8;
     uint32_t *D = CNT + 8;
 
@@ -600,7 +629,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
     // ---- stage the tile into LDS and build the bucket masks ----
     // lane k < 32 holds Tc[k], lane 32 + k holds Tm[k] (K == 32: one wave covers both)
     static_assert(K == 32, "mask/threshold lane layout assumes K == 32");
-    const uint32_t my_t = a.thr[lane];
+    const uint32_t my_t = NM ? 0u : a.thr[lane];  // (no masks: no thresholds)
     const uint32_t gbase = (b * W + w) * G;             // first (global) group of this tile
     uint64_t *Mw = M + (size_t)w * G * K * 2;           // the tile's masks
     // LDS byte address of this bucket lane's mask word of group 0 (one-wave kernels' mask upkeep)
@@ -611,7 +640,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
     // would pass, never reaches the check (placed on the tile's first schedulable node).
     // rlab holds ~labels: label and conflict tests become one ((~lab & req) | (cu & conf)) == 0.
     RecT<G> rcf, rmf, rcu, rlab;
-    GM schedbits = 0;                                   // bit g: node (g, lane) schedulable
+    GM schedbits = 0;                                  // bit g: node (g, lane) schedulable
     uint32_t usedbits = 0, used_hi = 0;                 // bit g (g - 32 in used_hi): node (g, lane) used
     {
         // branch-free loads from one base address per array (group g at an immediate
@@ -649,7 +678,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
     // bucket-major (a rolled loop): two thresholds live in scalars at a time -- hoisting all
     // 64 of them out of an unrolled loop spilled scalars into VGPR lanes
 #pragma unroll 1
-    for (uint32_t k = 0; k < (uint32_t)K; ++k) {
+    for (uint32_t k = 0; k < (NM ? 0u : (uint32_t)K); ++k) {  // (NM: no masks to build)
         const uint32_t tc = __builtin_amdgcn_readlane(my_t, k), tm = __builtin_amdgcn_readlane(my_t, K + k);
 #pragma unroll
         for (uint32_t g = 0; g < G; ++g) {  // every lane takes part in each ballot
@@ -819,6 +848,10 @@ k_ffd_pipe(const PipeArgs a_arg) {
             } else {
                 n = g_ld_u(sd);
                 pos = g_ld(sd + 64 + lane);  // with the count: one round trip
+                // NM: drained at once (the rare path).  Left pending into the blocks below, the position
+                // word's register made every group's serial loop wait for the carried gathers (s_waitcnt
+                // vmcnt(4)) in a build whose allocator reused it there (profiles/r12_bigp_regs.txt)
+                if constexpr (NM) __builtin_amdgcn_s_waitcnt(VMCNT0);
             }
             if (n & END) break;
             valid = lane < n;
@@ -929,7 +962,9 @@ k_ffd_pipe(const PipeArgs a_arg) {
         // bucket indices: packed into s_idx by k_gather_sorted (one binary search per container
         // instead of one per container and stage), else searched here
         uint32_t kc, km;
-        if (a.kpack) {
+        if constexpr (NM) {
+            kc = km = 0;  // no bucket masks: no bucket indices
+        } else if (a.kpack) {
             kc = (idx >> 21) & (uint32_t)(K - 1);
             km = (idx >> 26) & (uint32_t)(K - 1);
         } else {
@@ -979,7 +1014,10 @@ k_ffd_pipe(const PipeArgs a_arg) {
             const uint64_t e = PK ? __builtin_amdgcn_ballot_w64(pk_fits(rcf[g], qw))
                                   : (__builtin_amdgcn_ballot_w64(rcf[g] >= qc) & __builtin_amdgcn_ballot_w64(rmf[g] >= qm));
             const uint64_t *mg = Mw + (size_t)g * K * 2;
-            if (prescan_skip) {
+            if constexpr (NM) {
+                // the corner alone: every valid lane gets the same candidate groups
+                cand |= e ? GM(1) << g : GM(0);
+            } else if (prescan_skip) {
                 // a group whose corner is empty fits no container of the batch: no mask loads
                 // (most wide-stage batches pass through with every corner empty)
                 if (e) cand |= (mg[oc] & mg[om] & e) ? GM(1) << g : GM(0);
@@ -1638,6 +1676,9 @@ __global__ __launch_bounds__(1024) void k_unsort(uint32_t C, uint32_t H, uint32_
 size_t lds_bytes(uint32_t W, uint32_t G, uint32_t R) {
     return (size_t)W * G * K * 16 + ((size_t)(W - 1) * 8 + 8) * 4 + (size_t)(W - 1) * R * NF * 64 * 4;
 }
+// bigp's own dynamic LDS: without the masks (FPP_BIGP_NOMASK) only the control words are left, so the
+// 28 workgroups per CU of seven waves per SIMD fit; with the masks (6176 B) 26 do.
+size_t lds_bytes_bigp(uint32_t R) { return FPP_BIGP_NOMASK ? 8 * 4 : lds_bytes(1, 12, R); }
 
 // G is a template parameter (records are register arrays); one instantiation per G
 template <uint32_t G, uint32_t BLK = 1024, uint32_t WV = 0, bool PK = false>
@@ -1659,7 +1700,8 @@ struct TuKernel {
     launch_fn launch;
     const void *(*kernel)();
 };
-static_assert(WIDE12_BIG_WAVES == 6, "fp_pipe_tus.h names the six-wave 4096-scenario kernel");
+static_assert(WIDE12_BIG_WAVES == 6 && BIGP_WV == 7,
+              "fp_pipe_tus.h names the 4096-scenario kernels: big by six waves per SIMD, bigp by seven");
 #ifdef FPP_SPLIT
 }  // namespace fpp
 #define FPP_TU_DECL(name, G, BLK, WV, PK)                                                    \
@@ -1724,11 +1766,12 @@ static const void *const kKernelWide[MAX_G_WIDE / 4 + 1] = {
 static inline bool wide_g(uint32_t W, uint32_t G) { return W == 1 && G >= 12; }
 // the six-wave 12-group instantiation (WIDE12_BIG_S)
 static inline bool wide12_big(uint32_t S, uint32_t W, uint32_t G) { return W == 1 && G == 12 && S >= WIDE12_BIG_S; }
-// The kernel of a geometry (PK: the packed one, if compiled; else null).  big: the six-wave
-// 12-group kernel (fp_pipe_launch takes it only with unbounded links).
+// The kernel of a geometry (PK: the packed one, if compiled; else null).  big: the 4096-scenario
+// 12-group kernels (fp_pipe_launch takes them only with unbounded links): six waves per SIMD for the u32
+// one, seven for its packed twin, which runs on an LDS size of its own (lds_bytes_bigp).
 static void pipe_kernel(uint32_t G, uint32_t W, bool big, bool PK, launch_fn *l, const void **k) {
     const bool wide = wide_g(W, G);
-    const uint32_t BLK = wide ? 64u : 1024u, WV = big ? WIDE12_BIG_WAVES : 0u;
+    const uint32_t BLK = wide ? 64u : 1024u, WV = big ? (PK ? BIGP_WV : WIDE12_BIG_WAVES) : 0u;
     *l = nullptr;
     *k = nullptr;
     if (const TuKernel *t = tu_find(G, BLK, WV, PK)) {
@@ -1841,6 +1884,7 @@ bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint
 struct PipeGeom {
     uint32_t G, W, B, R;
     size_t lds;
+    size_t lds_big_pk;  // the packed twin's when the 4096-scenario pair runs (bigp: lds_bytes_bigp)
     uint32_t lag;       // segment ticket lag (kernel comment)
     uint32_t slots;     // slots per global link
     uint32_t bounded;   // links are rings with back-pressure
@@ -1878,6 +1922,7 @@ static bool pipe_geom(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, PipeGeom *g
     }
     g->R = R;
     g->lds = lds_bytes(W, G, R);
+    g->lds_big_pk = wide12_big(S, W, G) ? lds_bytes_bigp(R) : g->lds;
     // resident segments on this device (0 if unknown)
     // (the kernel fp_pipe_launch will run: the six-wave one only with unbounded links)
     // (and of its packed twin when there is one: the smaller of the two, either may run the batch)
@@ -1891,7 +1936,8 @@ static bool pipe_geom(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, PipeGeom *g
             pipe_kernel(G, W, big, pk, &l, &fn);
             int occ = 0;
             if (!fn) continue;
-            if (dev_cu <= 0 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)(W * 64), g->lds) != hipSuccess ||
+            if (dev_cu <= 0 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)(W * 64), big && pk ? g->lds_big_pk : g->lds) !=
+                                   hipSuccess ||
                 occ <= 0)
                 return 0;
             const uint64_t r = (uint64_t)occ * (uint64_t)dev_cu;
@@ -2128,7 +2174,7 @@ int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_
         if (!rc) {
             FP_HIP(hipGetLastError());
             a.pk_mode = 2;
-            rc = pkfn(st, (unsigned)(S * B), W * 64, lds, a);
+            rc = pkfn(st, (unsigned)(S * B), W * 64, big ? geo.lds_big_pk : lds, a);
         }
     } else {
         a.pk_mode = 0;
@@ -2171,6 +2217,28 @@ int fp_place_geometry_impl(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32
 }
 
 #ifdef FP_PIPE_STATS
+// What hipOccupancyMaxActiveBlocksPerMultiprocessor reports for the kernels fp_pipe_launch runs for
+// S x C x N (tools/pipe_occupancy.py): out = {u32 kernel: workgroups per CU, dynamic LDS bytes; packed
+// twin: the same (0, 0 without one); compute units}
+extern "C" int fp_debug_pipe_occupancy(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, int *out) {
+    PipeGeom g;
+    if (!pipe_geom(c, S, C, N, &g)) return FP_EOVERFLOW;
+    const bool big = wide12_big(S, g.W, g.G) && !g.bounded;
+    for (int pk = 0; pk < 2; ++pk) {
+        launch_fn l;
+        const void *fn;
+        pipe_kernel(g.G, g.W, big, pk != 0, &l, &fn);
+        const size_t lds = big && pk ? g.lds_big_pk : g.lds;
+        int occ = 0;
+        if (fn && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, (int)(g.W * 64), lds) != hipSuccess)
+            return FP_EDEVICE;
+        out[2 * pk] = occ;
+        out[2 * pk + 1] = fn ? (int)lds : 0;
+    }
+    out[4] = 0;
+    (void)hipDeviceGetAttribute(&out[4], hipDeviceAttributeMultiprocessorCount, c->device);
+    return FP_OK;
+}
 extern "C" int fp_debug_pipe_timeline(unsigned long long *out) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pipe_tl), sizeof(unsigned long long) * 16 * TL_B * 8) != hipSuccess)
         return FP_EDEVICE;

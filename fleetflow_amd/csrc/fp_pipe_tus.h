@@ -1,7 +1,9 @@
 // The k_ffd_pipe instantiations compiled in translation units of their own (fp_pipe_tu.hip, one
 // object per entry, each under the LLVM machine scheduler the Makefile's FFD_TUS gives it).
 // X(name, G, BLK, WV, PK):
-//   big / bigp  the 4096-scenario kernel (one-wave 12-group segments, six waves per SIMD), u32 / packed
+//   big / bigp  the 4096-scenario kernels (one-wave 12-group segments): u32 at six waves per SIMD; packed
+//               at seven and without bucket masks (fp_pipe.hip FPP_BIGP_NOMASK; WV = 7 names it,
+//               FPP_BIGP_WAVES sets the waves it is compiled for)
 //   w12 / w12p  one-wave 12-group segments at five waves per SIMD (2048-scenario loads, bounded rings)
 //   m8  / m8p   2-stage segments of 8 groups (1024-scenario loads)
 //   m10 / m10p  4-stage segments of 10 groups (512-scenario loads)
@@ -13,7 +15,7 @@
 
 #define FPP_TUS(X)            \
     X(big, 12, 64, 6, 0)      \
-    X(bigp, 12, 64, 6, 1)     \
+    X(bigp, 12, 64, 7, 1)     \
     X(w12, 12, 64, 0, 0)      \
     X(w12p, 12, 64, 0, 1)     \
     X(m8, 8, 1024, 0, 0)      \

@@ -1,7 +1,8 @@
 //! Builds libfleetplace.so for gfx950 by running fleetflow_amd/csrc/Makefile itself -- objects and
 //! library under OUT_DIR -- so the crate links the library the bench measures: the same sources,
-//! translation units (fp_pipe.hip with -DFPP_SPLIT_BIG, fp_pipe_big.hip under its own LLVM machine
-//! scheduler) and flags, with no second copy of the recipe to drift.  Or links a prebuilt one.
+//! translation units (fp_pipe.hip with -DFPP_SPLIT, and fp_pipe_tu.hip once per FFD kernel of the
+//! Makefile's FFD_TUS, each under its own LLVM machine scheduler) and flags, with no second copy of
+//! the recipe to drift.  Or links a prebuilt one.
 //!
 //!   FLEETPLACE_LIB_DIR=/path/with/libfleetplace.so   use a prebuilt library
 //!   FLEETPLACE_SRC=/path/to/fleetflow_amd/csrc       HIP sources + Makefile (default: ../../fleetflow_amd/csrc)
