@@ -48,6 +48,12 @@ GROW_PENDING, GROW_PLACED, GROW_OPENED, GROW_UNPLACEABLE, GROW_CAPPED = 0, 1, 2,
 GROW_LEFT_CPU, GROW_LEFT_MEM, GROW_FIRST_UNPLACED, GROW_WORDS = 5, 6, 7, 8
 GROW_FIELDS = ("pending", "placed", "opened", "unplaceable", "capped", "left_cpu", "left_mem", "first_unplaced")
 GROW_MAX_NEW = 8192
+# re-planning a running stage (SPEC.md 2.13): enum fp_change with its names in value order, and the word indices
+# of a scenario's summary row (words 0..4 count the change values)
+CHANGE_KEPT, CHANGE_NEW, CHANGE_MOVED, CHANGE_LOST, CHANGE_ABSENT = 0, 1, 2, 3, 4
+CHANGE_NAMES = ("kept", "new", "moved", "lost", "absent")
+REPLAN_KEPT, REPLAN_NEW, REPLAN_MOVED, REPLAN_LOST, REPLAN_ABSENT = 0, 1, 2, 3, 4
+REPLAN_MOVED_CPU, REPLAN_MOVED_MEM, REPLAN_WORDS = 5, 6, 8
 # context options (fleetplace.h enum fp_option); FP_OPT_AUTO = the production default
 # ("segsort" is ignored by the library and kept for ABI stability)
 FP_OPT_AUTO = -1
@@ -157,6 +163,10 @@ SIGNATURES = {
                                  ct.c_uint32, u32p, u32p]),
     "fp_dev_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), vp, ct.c_uint32, ct.c_uint32, vp, vp, vp, vp,
                                      ct.c_uint32, vp, vp]),
+    "fp_replan": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, u32p, ct.c_uint32, ct.c_uint32,
+                             u32p, u32p, u8p, u8p, u32p]),
+    "fp_replan_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u8p, u32p]),
+    "fp_dev_replan_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp, vp]),
     "fp_dev_argmin_cost": (ct.c_int, [vp, vp, ct.c_uint32, vp]),
     "fp_dev_gen_batch": (ct.c_int, [vp, ct.c_uint64, ct.POINTER(FpBatch), ct.c_uint32]),
 }

@@ -641,6 +641,58 @@ extern "C" int fp_dev_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, con
     return dev_policy(c, b, o);
 }
 
+// ---- re-planning a running stage (SPEC.md 2.13, fp_replan.hip) --------------------
+// A scored batch's staging (batch_run's row list) with prev and the two optional results behind it.  Everything
+// the device entry finds on the device is host memory here and refused before anything is staged.
+static int replan_host(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o, uint8_t *change_out,
+                       uint32_t *summary_out) {
+    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes, SC = S * C;
+    if (S && !o.strategy) return FP_EINVAL;
+    if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
+    for (size_t s = 0; s < S; ++s)
+        if (o.strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (!batch_has_tables(b) || (SC && !prev)) return FP_EINVAL;
+    if (SC && prev == b->assign) return FP_EINVAL;
+    for (size_t i = 0; i < SC; ++i)
+        if (prev[i] >= N && prev[i] != FP_NONE) return FP_EINVAL;
+    if (S == 0) return FP_OK;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_batch d;
+    fp_policy_opts dopt;
+    fp_replan_dev dr;
+    const int n = fp_replan_rows(b, &o, prev, change_out, summary_out, &d, &dopt, &dr, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = fp_dev_replan_batch_impl(c, &d, dr.prev, dopt, dr.change, dr.summary)) return rc;
+    return copy_back_all(c, rows, n);
+}
+
+extern "C" int fp_replan_batch(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                               const uint32_t *preferred_labels, uint32_t *node_count, uint8_t *change_out,
+                               uint32_t *summary_out) {
+    if (!c || !b) return FP_EINVAL;
+    return replan_host(c, b, prev, policy_opts(strategy, preferred_labels, node_count), change_out, summary_out);
+}
+
+extern "C" int fp_replan(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level, const uint32_t *prev,
+                         uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count, uint32_t *assign_out,
+                         uint8_t *reason_out, uint8_t *change_out, uint32_t *summary_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
+    return replan_host(c, &b, prev, policy_opts(&strategy, &preferred_labels, node_count), change_out, summary_out);
+}
+
+extern "C" int fp_dev_replan_batch(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                                   const uint32_t *preferred_labels, uint32_t *node_count, uint8_t *change_out,
+                                   uint32_t *summary_out) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_replan_batch_impl(c, b, prev, policy_opts(strategy, preferred_labels, node_count),
+                                                   change_out, summary_out));
+}
+
 // ---- feasibility and rejection diagnosis -----------------------------------------
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,
                               uint32_t *first_out, uint32_t *count_out, uint64_t *bitmap_out) {

@@ -186,6 +186,12 @@ int fp_dev_grow_sweep_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *re
                            uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                            const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
 
+// re-planning a running stage (fp_replan.hip, SPEC.md 2.13); every pointer is device memory.  Of `o` the call
+// reads strategy, preferred and node_count.  A strategy that is no fp_strategy value and a prev value out of
+// range are found on the device (FP_EINVAL in the context's error word, nothing written)
+int fp_dev_replan_batch_impl(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o,
+                             uint8_t *change_out, uint32_t *summary_out);
+
 // tile-pipeline FFD (fp_pipe.hip)
 bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint32_t *W_out, uint32_t *B_out,
                   size_t *lds_out);

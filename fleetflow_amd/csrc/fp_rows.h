@@ -82,6 +82,24 @@ static inline int fp_batch_rows(const fp_batch *b, const fp_policy_opts *o, fp_b
     return n;
 }
 
+// fp_replan / fp_replan_batch (SPEC.md 2.13): the rows of a scored batch (`o` holds strategy, preferred and
+// node_count), then prev, then the two results the caller may ask for
+struct fp_replan_dev {
+    const uint32_t *prev;
+    uint8_t *change;
+    uint32_t *summary;
+};
+static inline int fp_replan_rows(const fp_batch *b, const fp_policy_opts *o, const uint32_t *prev, uint8_t *change_out,
+                                 uint32_t *summary_out, fp_batch *d, fp_policy_opts *dopt, fp_replan_dev *dr,
+                                 fp_row *r) {
+    const size_t S = b->n_scen, SC = S * b->n_containers;
+    int n = fp_batch_rows(b, o, d, dopt, r);
+    r[n++] = fp_row_in(prev, SC, &dr->prev);
+    r[n++] = fp_row_opt(change_out, SC, &dr->change);
+    r[n++] = fp_row_opt(summary_out, S * FP_REPLAN_WORDS, &dr->summary);
+    return n;
+}
+
 // one scenario's container and node tables as inputs (nine rows, in this order)
 static inline int fp_tables_rows(const fp_containers *cs, const fp_nodes *ns, fp_containers *dc, fp_nodes *dn,
                                  fp_row *r) {

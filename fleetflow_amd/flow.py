@@ -17,6 +17,9 @@ the same:
   (SPEC.md 2.11; the `drain` scheduling state of controlplane model.rs:435-442).
 * ``grow_stage``: the new servers of each template of a catalogue that a plan's NOFIT services need
   (SPEC.md 2.12).
+* ``replan_stage``: the next plan of a stage that runs as a plan says, every service staying on its server
+  while it still fits there (SPEC.md 2.13; `cordon` of model.rs:435-442 "stops new placements, existing
+  placements continue").
 
 Strings never cross the C ABI: names are mapped to u32 ids in stage order here.
 """
@@ -778,6 +781,115 @@ def grow_stage(flow: Flow, stage_name: str, plan: Plan, catalogue: list[Server],
             if int(row[v]) != NONE:
                 c.servers[int(row[v])].append(names[v])
     return report
+
+
+@dataclass
+class Replan:
+    """``replan_stage``'s answer (SPEC.md 2.13): the stage's next plan and what it changes for the services that
+    ran under the previous one.  Services are listed in stage order."""
+    plan: Plan                                  # goes straight into drain_stage, grow_stage or the next replan_stage
+    kept: list[str] = field(default_factory=list)                    # stayed on their server
+    new: list[str] = field(default_factory=list)                     # did not run before, placed now
+    moved: list[tuple[str, str, str]] = field(default_factory=list)  # (service, from, to)
+    lost: list[tuple[str, str, str]] = field(default_factory=list)   # (service, from, "NOFIT" | "CYCLE")
+    moved_cpu_m: int = 0                        # what the moved services ask for in sum: the migration volume
+    moved_mem_mib: int = 0
+
+
+def _hard_guarantees(policy: PlacementPolicy | None, plan: Plan) -> list[str]:
+    """The hard guarantees of ``policy`` -- or, without one, of the policy ``plan`` was made under -- that a
+    re-plan would not apply (SPEC.md 2.13)."""
+    if policy is not None:
+        found = (policy.spread is not None, bool(policy.fallback), policy.quota is not None)
+    else:
+        found = (plan.spread_topology_key is not None and bool(plan.spread_max_skew), bool(plan.fallback_relax_order)
+                 and plan.fallback_max_hops != 0, plan.quota is not None)
+    return [name for name, there in zip(("spread constraint", "fallback chain", "resource quota"), found) if there]
+
+
+def replan_stage(flow: Flow, stage_name: str, plan: Plan, planner: Planner | None = None,
+                 policy: PlacementPolicy | None = None) -> Replan:
+    """The next plan of a stage that runs as ``plan`` says (SPEC.md 2.13): `fleet up` on a running stage.  The
+    tables are built as ``plan_stage`` builds them, from the flow as it is now (new requests, new servers); a
+    service keeps the server ``plan.assignment`` names while it still fits there -- on a cordoned server too --
+    and one ``Planner.replan`` call places the others under the strategy and preferred labels of ``policy`` or,
+    without one, of the policy the plan was made under.  Levels and orders are computed as in ``plan_stage``.
+
+    A service whose old server is no longer in the stage, or is flagged ``draining``, has no seat to keep: it
+    goes to the planner as one that does not run, and is reported here as moved (from its old slug) or lost.
+
+    The spread constraint, the fallback chain and the quota are not applied by a re-plan, and a new plan must not
+    silently drop a hard guarantee: a ``policy`` that carries one, or without a policy a ``plan`` made under
+    one, is a ValueError that names it."""
+    from ._lib import CHANGE_KEPT, CHANGE_LOST, CHANGE_MOVED, CHANGE_NEW, REPLAN_MOVED_CPU, REPLAN_MOVED_MEM
+    hard = _hard_guarantees(policy, plan)
+    if hard:
+        raise ValueError(f"replan of stage '{stage_name}': the {' and the '.join(hard)} of the "
+                         f"{'policy' if policy is not None else 'plan'} would not be applied (SPEC.md 2.13); "
+                         "plan the stage afresh with plan_stage, or pass a policy without it")
+    p = planner or default_planner()
+    stage = flow.stages[stage_name]
+    services = list(stage.services)
+    nodes = _server_nodes(flow, stage.servers)
+    strategy = policy.strategy if policy is not None else plan.strategy
+    preferred = policy.preferred if policy is not None else list(plan.preferred)
+    if not services:
+        return Replan(Plan(stage_name, [], {}, [], {}, {}, strategy=strategy, preferred=preferred))
+    names, pos2v, row_ptr, col, has_deps = stage_graph(services, flow)
+    if len(names) == len(services):
+        perm, level_v, order_v, _, _ = p.plan_stage(row_ptr, col, has_deps)
+        order = [services[i] for i in perm.tolist()]
+        levels = level_v.tolist()
+        level_order = [services[i] for i in order_v.tolist()]
+    else:
+        order = order_by_dependencies(services, flow, p)
+        levels, level_order = levelize_stage(services, flow, p)
+    lvl_v = {names[v]: levels[i] for i, v in enumerate(pos2v)}
+    new_plan = Plan(stage_name, order, dict(zip(services, levels)), level_order, {}, {}, strategy=strategy,
+                    preferred=preferred)
+    out = Replan(new_plan)
+    slugs = [nd.slug for nd in nodes]
+    index = {s: n for n, s in enumerate(slugs)}
+    prev, gone = [NONE] * len(names), {}
+    for v, name in enumerate(names):
+        slug = plan.assignment.get(name)
+        if slug is None:
+            continue
+        if slug not in index or nodes[index[slug]].draining:
+            gone[name] = slug
+        else:
+            prev[v] = index[slug]
+    if not nodes:  # nothing to place on, as in plan_stage: whatever ran is lost
+        out.lost = [(n, gone[n], "CYCLE" if lvl_v[n] == NONE else "NOFIT") for n in names if n in gone]
+        return out
+    cont, ntab = _stage_tables(names, flow, nodes, preferred)
+    pmask = _stage_labels(names, flow, nodes, preferred).mask(preferred)
+    assign, reason, change, summary, _, _ = p.replan(cont, ntab, prev, strategy if strategy is not None else 0, pmask,
+                                                     level=[lvl_v[n] for n in names])
+    out.moved_cpu_m, out.moved_mem_mib = int(summary[REPLAN_MOVED_CPU]), int(summary[REPLAN_MOVED_MEM])
+    for v, name in enumerate(names):
+        why = "CYCLE" if int(reason[v]) == 2 else "NOFIT"
+        if int(assign[v]) != NONE:
+            new_plan.assignment[name] = slugs[int(assign[v])]
+        else:
+            new_plan.rejected[name] = why
+        chg = int(change[v])
+        if chg == CHANGE_KEPT:
+            out.kept.append(name)
+        elif chg == CHANGE_MOVED:
+            out.moved.append((name, slugs[prev[v]], slugs[int(assign[v])]))
+        elif chg == CHANGE_LOST:
+            out.lost.append((name, slugs[prev[v]], why))
+        elif name in gone:  # NEW or ABSENT at the ABI: it ran, on a server it cannot stay on
+            if chg == CHANGE_NEW:
+                out.moved.append((name, gone[name], slugs[int(assign[v])]))
+                out.moved_cpu_m = (out.moved_cpu_m + cont[0][v]) & U32_MAX
+                out.moved_mem_mib = (out.moved_mem_mib + cont[1][v]) & U32_MAX
+            else:
+                out.lost.append((name, gone[name], why))
+        elif chg == CHANGE_NEW:
+            out.new.append(name)
+    return out
 
 
 def resolve_target_server(flow: Flow, stage_name: str, planner: Planner | None = None) -> str | None:

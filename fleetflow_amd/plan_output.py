@@ -19,6 +19,10 @@ and ``drain_report_to_json`` / ``drain_report_from_json`` carry it as
 the services of each new server indented under it where the candidate was detailed, and ``grow_report_to_json``
 / ``grow_report_from_json`` carry it as ``{stage, max_new, pending, candidates: [{name, cpu_m, ...}]}``.
 
+``format_replan_report`` prints a re-plan (SPEC.md 2.13, ``flow.replan_stage``): one line of counts, then the
+moves, the new and the lost services, and ``replan_report_to_json`` / ``replan_report_from_json`` carry it as
+``{plan, kept, new, moved, lost, moved_cpu_m, moved_mem_mib}`` with ``plan`` in ``plan_to_json``'s form.
+
 ``format_up_dry_run`` / ``format_deploy_dry_run`` reproduce the reference's
 ``fleet up --dry-run`` (crates/fleetflow/src/commands/up.rs:57-136) and
 ``fleet deploy --dry-run`` (crates/fleetflow/src/commands/deploy.rs:14-100)
@@ -36,7 +40,7 @@ import json
 from dataclasses import asdict
 
 from ._lib import QUOTA_NAMES
-from .flow import U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, GrowCandidate, GrowReport, Plan, Why
+from .flow import U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, GrowCandidate, GrowReport, Plan, Replan, Why
 from .parser import FlowError
 
 
@@ -114,6 +118,34 @@ def drain_report_from_json(text: str) -> DrainReport:
                             c.get("evicted", 0), c.get("stranded_cpu_m", 0), c.get("stranded_mem_mib", 0),
                             c.get("targets", 0)) for c in d.get("candidates") or []]
     return DrainReport(d["stage"], d.get("by"), pol.get("strategy"), list(pol.get("preferred") or []), cands)
+
+
+def format_replan_report(report: Replan) -> str:
+    """``replan <stage>: <k> kept, <n> new, <m> moved (<cpu>m cpu, <mem> MiB), <l> lost``, then the moves
+    (``service: from -> to``), the new services (``service: -> to``) and the lost ones
+    (``service: from -> lost (REASON)``) indented under it."""
+    plan = report.plan
+    lines = [f"replan {plan.stage}: {len(report.kept)} kept, {len(report.new)} new, {len(report.moved)} moved "
+             f"({report.moved_cpu_m}m cpu, {report.moved_mem_mib} MiB), {len(report.lost)} lost"]
+    lines += [f"  {svc}: {src} -> {dst}" for svc, src, dst in report.moved]
+    lines += [f"  {svc}: -> {plan.assignment[svc]}" for svc in report.new]
+    lines += [f"  {svc}: {src} -> lost ({why})" for svc, src, why in report.lost]
+    return "\n".join(lines)
+
+
+def replan_report_to_json(report: Replan, indent: int | None = None) -> str:
+    """``{plan: <plan_to_json's object>, kept, new, moved, lost, moved_cpu_m, moved_mem_mib}``."""
+    d = {"plan": json.loads(plan_to_json(report.plan)), "kept": report.kept, "new": report.new,
+         "moved": [list(m) for m in report.moved], "lost": [list(x) for x in report.lost],
+         "moved_cpu_m": report.moved_cpu_m, "moved_mem_mib": report.moved_mem_mib}
+    return json.dumps(d, ensure_ascii=False, indent=indent)
+
+
+def replan_report_from_json(text: str) -> Replan:
+    d = json.loads(text)
+    return Replan(plan_from_json(json.dumps(d["plan"], ensure_ascii=False)), list(d.get("kept") or []),
+                  list(d.get("new") or []), [tuple(m) for m in d.get("moved") or []],
+                  [tuple(x) for x in d.get("lost") or []], d.get("moved_cpu_m", 0), d.get("moved_mem_mib", 0))
 
 
 def format_grow_report(report: GrowReport) -> str:

@@ -495,6 +495,39 @@ class Planner:
                                                   _arg(o.qu), _arg(o.why)), "fp_place_batch_policy_quota")
         return o.assign, o.reason, o.hops, o.cost, o.nodes, o.nc, o.why, o.qu
 
+    def replan(self, cont, nodes, prev, strategy=0, preferred=0, level=None, node_count=None, *, want_change=True,
+               want_summary=True):
+        """Re-plan a running stage (SPEC.md 2.13, fp_replan): ``nodes`` is the base table (everything deducted
+        except these containers' own requests), ``prev`` [C] the node each container runs on now (NONE = none).
+        A container keeps its node while it still fits there (a cordoned node keeps what runs on it); the
+        others are placed as place_policy places them, on the state the seats left.  ``prev`` all NONE is
+        place_policy.  Inputs are not mutated.  Returns (assign, reason, change, summary, nodes_after,
+        node_count_after): change [C] u8 holds _lib.CHANGE_* values and summary [8] the _lib.REPLAN_* words
+        (None with ``want_change`` / ``want_summary`` False); node_count_after is None without node_count."""
+        o = _policy_call(None, cont, nodes, strategy, preferred, level, node_count, max_skew=0)
+        C = o.cont[0].size
+        pv = _u32(prev).reshape(-1)
+        self._need(pv.size == C, "prev must hold C entries")
+        change = np.empty(C, np.uint8) if want_change else None
+        summary = np.empty(_lib.REPLAN_WORDS, np.uint32) if want_summary else None
+        check(self._L.fp_replan(self._ctx, *o.head[:3], _arg(pv), *o.head[3:], _arg(o.assign), _arg(o.reason),
+                                _arg(change), _arg(summary)), "fp_replan")
+        return o.assign, o.reason, change, summary, o.nodes, o.nc
+
+    def replan_batch(self, S, C, N, cont, nodes, prev, strategy, preferred=None, level=None, node_count=None,
+                     scen_base=0, *, want_change=True, want_summary=True):
+        """replan over scenario-major arrays (fp_replan_batch): ``prev`` [S*C], ``strategy`` [S] ints or policy
+        strings, ``preferred`` [S] or None, ``node_count`` [S*N] or None.  Returns (assign, reason, cost, change
+        [S*C], summary [S, 8], nodes_after, node_count_after); change and summary are None when not wanted."""
+        o = _policy_call((S, C, N, scen_base), cont, nodes, strategy, preferred, level, node_count)
+        pv = _u32(prev).reshape(-1)
+        self._need(pv.size == S * C, "prev must hold S * C entries")
+        change = np.empty(S * C, np.uint8) if want_change else None
+        summary = np.empty((S, _lib.REPLAN_WORDS), np.uint32) if want_summary else None
+        check(self._L.fp_replan_batch(self._ctx, o.head[0], _arg(pv), *o.head[1:], _arg(change), _arg(summary)),
+              "fp_replan_batch")
+        return o.assign, o.reason, o.cost, change, summary, o.nodes, o.nc
+
     def feasibility(self, cont, nodes, bitmap=True):
         cont, nodes = _tables(cont, nodes, None, None, False)
         C, N = cont[0].size, nodes[0].size
@@ -762,6 +795,23 @@ class Planner:
         self._dev(lambda: check(self._L.fp_dev_place_batch_policy_quota(self._ctx, ct.byref(db.struct()), *args),
                                 "fp_dev_place_batch_policy_quota"))
         return hops_t, quota_why_t, quota_used_t
+
+    def dev_replan_batch(self, db: "DevBatch", prev_t, strategy_t, preferred_t=None, count_t=None, change_t=None,
+                         summary_t=None):
+        """fp_dev_replan_batch (SPEC.md 2.13) on device tensors: ``prev_t`` [S*C] (int32 storage of u32 values,
+        -1 = NONE), ``strategy_t`` [S], ``preferred_t`` [S] or None, ``count_t`` [S*N] in/out or None; out:
+        ``change_t`` [S*C] uint8 or None and ``summary_t`` [S * 8] or None.  ``db``'s node tables are the base
+        tables and are updated in place.  A strategy that is no fp_strategy value and a prev value out of range
+        are found on the device: nothing is written and sync() raises FP_EINVAL."""
+        _dev_policy_checks(db, strategy_t, preferred_t, count_t, None, None)
+        self._need(prev_t.numel() == db.S * db.C and prev_t.element_size() == 4, "prev_t must hold S * C 32-bit entries")
+        self._need(change_t is None or (change_t.numel() == db.S * db.C and change_t.element_size() == 1),
+                   "change_t must hold S * C bytes")
+        self._need(summary_t is None or (summary_t.numel() == db.S * _lib.REPLAN_WORDS and summary_t.element_size() == 4),
+                   "summary_t must hold S * 8 32-bit entries")
+        args = [_arg(t) for t in (prev_t, strategy_t, preferred_t, count_t, change_t, summary_t)]
+        self._dev(lambda: check(self._L.fp_dev_replan_batch(self._ctx, ct.byref(db.struct()), *args),
+                                "fp_dev_replan_batch"))
 
     def dev_argmin_cost(self, cost_t, out_t):
         self._dev(lambda: check(self._L.fp_dev_argmin_cost(self._ctx, cost_t.data_ptr(), cost_t.numel(),

@@ -33,6 +33,10 @@
  *                        crates/fleetflow-cloud-sakura/src/provider.rs:15-30, with the ServerLabels /
  *                        ServerCapacity a new server would carry, crates/fleetflow-controlplane/src/model.rs:399-419)
  *                        that a plan's unplaced containers need
+ *   fp_replan         <- new: the next plan of a stage that already runs: a container stays on its server while
+ *                        it still fits there and only the others are placed.  `cordon` "stops new placements,
+ *                        existing placements continue" (crates/fleetflow-controlplane/src/model.rs:435-442);
+ *                        ServerAllocated is committed and released per placement (model.rs:421-427)
  *
  * Conventions
  *   - All buffers are caller-owned; no allocation crosses the ABI.
@@ -395,6 +399,37 @@ enum { FP_GROW_PENDING = 0, FP_GROW_PLACED = 1, FP_GROW_OPENED = 2, FP_GROW_UNPL
 int fp_grow_sweep(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
                   uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                   const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
+/* Re-planning a running stage (SPEC.md 2.13): fp_place_policy that knows where each container runs now.  nodes is
+ * the BASE table (everything deducted except these containers' own requests) and is updated in place; prev[c] is
+ * the node container c runs on, < nodes->n, or FP_NONE.  Pass 1 (seats) visits the containers in fp_place's order
+ * (cpu desc, mem desc, index asc), skipping CYCLE containers and those with prev == FP_NONE: a container keeps
+ * n = prev[c] iff cpu_free[n] >= cpu_m, mem_free[n] >= mem_mib, (labels[n] & req) == req and
+ * (conflict_used[n] & conflict) == 0 on the state the earlier seats left -- fp_place's predicate without
+ * `schedulable`: a cordoned node keeps what runs on it.  A kept container updates its node as fp_place_policy does
+ * (node_count += 1 included); assign = prev, reason OK, change KEPT.  Pass 2 visits, in the same order, every
+ * container that is neither CYCLE nor kept and places it exactly as fp_place_policy does (schedulable included) on
+ * the state pass 1 left: reason OK or NOFIT.  A CYCLE container is assign FP_NONE, reason CYCLE, whatever its prev.
+ * The cost counts NOFIT + CYCLE as rejected and the nodes that received a container in either pass.
+ * change_out (nullable) holds one enum fp_change per container; summary_out (nullable) one row of FP_REPLAN_WORDS
+ * u32 per scenario: words 0..4 the number of containers with each change value, MOVED_CPU / MOVED_MEM the sums of
+ * the MOVED containers' requests (the migration volume; u32, wrap), word 7 written as 0.
+ * prev all FP_NONE is exactly fp_place_policy; prev = the assign of an fp_place_policy call on the same inputs
+ * returns that call's outputs with every placed container KEPT.  nodes->n above FP_POLICY_MAX_NODES is
+ * FP_EOVERFLOW; a strategy above FP_STRATEGY_FILL_LOWEST, prev == assign_out (the same buffer read and written) and
+ * a prev[c] that is neither < nodes->n nor FP_NONE are FP_EINVAL; on any error nothing is written.  The policy's
+ * spread constraint, fallback chain and quota are not applied, and no capacity is handed back from a live table:
+ * the caller passes the base table. */
+enum fp_change { FP_CHANGE_KEPT = 0, FP_CHANGE_NEW = 1, FP_CHANGE_MOVED = 2, FP_CHANGE_LOST = 3, FP_CHANGE_ABSENT = 4 };
+enum { FP_REPLAN_KEPT = 0, FP_REPLAN_NEW = 1, FP_REPLAN_MOVED = 2, FP_REPLAN_LOST = 3, FP_REPLAN_ABSENT = 4,
+       FP_REPLAN_MOVED_CPU = 5, FP_REPLAN_MOVED_MEM = 6, FP_REPLAN_WORDS = 8 };
+int fp_replan(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32_t *level, const uint32_t *prev,
+              uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count, uint32_t *assign_out,
+              uint8_t *reason_out, uint8_t *change_out, uint32_t *summary_out);
+/* prev: [S][C]; strategy, preferred_labels: [S] (preferred_labels nullable = 0); node_count: [S][N] or NULL;
+ * change_out: [S][C] or NULL; summary_out: [S][FP_REPLAN_WORDS] or NULL.  prev == b->assign is FP_EINVAL. */
+int fp_replan_batch(fp_ctx *ctx, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                    const uint32_t *preferred_labels, uint32_t *node_count, uint8_t *change_out,
+                    uint32_t *summary_out);
 /* One stage's whole plan, the `fleet up --dry-run` path (crates/fleetflow/src/commands/up.rs:57-136):
  *   perm_out                 A1 legacy start order (engine.rs:64-85, as fp_legacy_order)
  *   level_out, order_out, n_cycle_out   A2 levels and start order (as fp_levelize)
@@ -478,6 +513,13 @@ int fp_dev_drain_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *node
 int fp_dev_grow_sweep(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
                       uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                       const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
+/* As fp_replan_batch on device pointers (change_out and summary_out included).  A strategy that is no fp_strategy
+ * value and a prev value out of range are found on the device before any store: nothing is written and
+ * fp_ctx_sync() reports FP_EINVAL.  The call takes the FFD order's 24 bytes per container plus the sort's scratch
+ * and one byte per container from the context's workspace. */
+int fp_dev_replan_batch(fp_ctx *ctx, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                        const uint32_t *preferred_labels, uint32_t *node_count, uint8_t *change_out,
+                        uint32_t *summary_out);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

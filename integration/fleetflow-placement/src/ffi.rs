@@ -67,6 +67,20 @@ pub const FP_GROW_LEFT_MEM: usize = 6;
 pub const FP_GROW_FIRST_UNPLACED: usize = 7;
 pub const FP_GROW_WORDS: usize = 8;
 pub const FP_GROW_MAX_NEW: u32 = 8192;
+// re-planning a running stage (SPEC.md 2.13): enum fp_change, and the word indices of a scenario's summary row
+pub const FP_CHANGE_KEPT: u8 = 0;
+pub const FP_CHANGE_NEW: u8 = 1;
+pub const FP_CHANGE_MOVED: u8 = 2;
+pub const FP_CHANGE_LOST: u8 = 3;
+pub const FP_CHANGE_ABSENT: u8 = 4;
+pub const FP_REPLAN_KEPT: usize = 0;
+pub const FP_REPLAN_NEW: usize = 1;
+pub const FP_REPLAN_MOVED: usize = 2;
+pub const FP_REPLAN_LOST: usize = 3;
+pub const FP_REPLAN_ABSENT: usize = 4;
+pub const FP_REPLAN_MOVED_CPU: usize = 5;
+pub const FP_REPLAN_MOVED_MEM: usize = 6;
+pub const FP_REPLAN_WORDS: usize = 8;
 pub const FP_K_PLACE: c_int = 0;
 pub const FP_K_SORT: c_int = 1;
 pub const FP_K_FEAS: c_int = 2;
@@ -232,6 +246,12 @@ unsafe extern "C" {
     pub fn fp_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32, n_cand: u32,
                          t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32, t_max: *const u32,
                          max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
+    pub fn fp_replan(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
+                     prev: *const u32, strategy: u32, preferred_labels: u32, node_count: *mut u32,
+                     assign_out: *mut u32, reason_out: *mut u8, change_out: *mut u8, summary_out: *mut u32) -> c_int;
+    pub fn fp_replan_batch(ctx: *mut fp_ctx, b: *const fp_batch, prev: *const u32, strategy: *const u32,
+                           preferred_labels: *const u32, node_count: *mut u32, change_out: *mut u8,
+                           summary_out: *mut u32) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,
                          perm_out: *mut u32, level_out: *mut u32, order_out: *mut u32, n_cycle_out: *mut u32,
                          first_out: *mut u32, count_out: *mut u32, assign_out: *mut u32, reason_out: *mut u8)
@@ -272,6 +292,9 @@ unsafe extern "C" {
     pub fn fp_dev_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
                              n_cand: u32, t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32,
                              t_max: *const u32, max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
+    pub fn fp_dev_replan_batch(ctx: *mut fp_ctx, b: *const fp_batch, prev: *const u32, strategy: *const u32,
+                               preferred_labels: *const u32, node_count: *mut u32, change_out: *mut u8,
+                               summary_out: *mut u32) -> c_int;
     pub fn fp_dev_argmin_cost(ctx: *mut fp_ctx, cost: *const u64, n: u32, best_dev: *mut u32) -> c_int;
     pub fn fp_dev_gen_batch(ctx: *mut fp_ctx, seed: u64, b: *const fp_batch, flags: u32) -> c_int;
 }

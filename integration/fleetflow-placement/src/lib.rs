@@ -219,6 +219,38 @@ impl Planner {
         Ok((assign, reason))
     }
 
+    /// Re-planning a running stage (SPEC.md 2.13, fleetplace.h `fp_replan`): `nodes` is the base table (everything
+    /// deducted except these containers' own requests; updated in place) and `prev[c]` the node container c runs
+    /// on now (`ffi::FP_NONE` = none).  A container keeps its node while it still fits there -- a cordoned node
+    /// keeps what runs on it -- and the others are placed as `place_policy` places them, on the state the seats
+    /// left.  Returns (assign, reason, one `ffi::FP_CHANGE_*` value per container, the `ffi::FP_REPLAN_*` words).
+    #[allow(clippy::too_many_arguments)]
+    pub fn replan(&mut self, c: &Containers, nodes: &mut Nodes, level: Option<&[u32]>, prev: &[u32], strategy: u32,
+                  preferred_labels: u32, node_count: Option<&mut [u32]>)
+                  -> Result<(Vec<u32>, Vec<u8>, Vec<u8>, [u32; ffi::FP_REPLAN_WORDS]), PlanError> {
+        let n = c.cpu_m.len();
+        let nn = nodes.cpu_free.len();
+        if !c.all_len(n) || !nodes.all_len(nn) || level.map_or(false, |l| l.len() != n) || prev.len() != n
+            || node_count.as_ref().map_or(false, |k| k.len() != nn) {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        let mut ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_mut_ptr(),
+                                     mem_free: nodes.mem_free.as_mut_ptr(), labels: nodes.labels.as_ptr(),
+                                     conflict_used: nodes.conflict_used.as_mut_ptr(),
+                                     schedulable: nodes.schedulable.as_ptr() };
+        let (mut assign, mut reason, mut change) = (vec![0u32; n], vec![0u8; n], vec![0u8; n]);
+        let mut summary = [0u32; ffi::FP_REPLAN_WORDS];
+        let count_ptr = node_count.map_or(std::ptr::null_mut(), |k| k.as_mut_ptr());
+        check(unsafe {
+            ffi::fp_replan(self.ctx, &cs, &mut ns, level.map_or(std::ptr::null(), |l| l.as_ptr()), prev.as_ptr(),
+                           strategy, preferred_labels, count_ptr, assign.as_mut_ptr(), reason.as_mut_ptr(),
+                           change.as_mut_ptr(), summary.as_mut_ptr())
+        })?;
+        Ok((assign, reason, change, summary))
+    }
+
     /// Scored placement under a hard topology spread (SPEC.md 2.7, fleetplace.h `fp_place_policy_spread`),
     /// the PlacementPolicy's `SpreadConstraint { topology_key, max_skew }`: `domain[n]` is the topology
     /// domain of node n (below `ffi::FP_SPREAD_MAX_DOMAINS`, else FP_EINVAL) and a node is feasible only
