@@ -167,6 +167,13 @@ SIGNATURES = {
                              u32p, u32p, u8p, u8p, u32p]),
     "fp_replan_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u8p, u32p]),
     "fp_dev_replan_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp, vp]),
+    "fp_replan_policy": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, u32p, ct.c_uint32,
+                                    ct.c_uint32, u32p, u32p, ct.c_uint32, u32p, ct.c_uint32, u32p, u8p, u8p, u32p, u32p,
+                                    u8p, u8p, u32p]),
+    "fp_replan_batch_policy": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u8p,
+                                          u32p, u32p, u8p, u8p, u32p]),
+    "fp_dev_replan_batch_policy": (ct.c_int, [vp, ct.POINTER(FpBatch), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, vp]),
     "fp_dev_argmin_cost": (ct.c_int, [vp, vp, ct.c_uint32, vp]),
     "fp_dev_gen_batch": (ct.c_int, [vp, ct.c_uint64, ct.POINTER(FpBatch), ct.c_uint32]),
 }

@@ -693,6 +693,86 @@ extern "C" int fp_dev_replan_batch(fp_ctx *c, const fp_batch *b, const uint32_t 
                                                    change_out, summary_out));
 }
 
+// ---- re-planning under the policy (SPEC.md 2.14, fp_replan_policy.hip) -------------
+// replan_host's checks and batch_policy_host's, all before anything is staged; the rows are fp_replan_rows with
+// every policy option (27 rows).
+static int replan_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *prev, fp_policy_opts o, uint8_t *change_out,
+                              uint32_t *summary_out) {
+    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes, SC = S * C;
+    if (S && !o.strategy) return FP_EINVAL;
+    if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
+    for (size_t s = 0; s < S; ++s)
+        if (o.strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (!batch_has_tables(b) || (SC && !prev)) return FP_EINVAL;
+    if (SC && prev == b->assign) return FP_EINVAL;
+    for (size_t i = 0; i < SC; ++i)
+        if (prev[i] >= N && prev[i] != FP_NONE) return FP_EINVAL;
+    if (!o.domain || !o.max_skew) o.domain = o.max_skew = nullptr;
+    for (size_t s = 0; o.max_skew && s < S; ++s) {
+        if (o.max_skew[s] == 0u) continue;
+        for (size_t n = 0; n < N; ++n)
+            if (o.domain[s * N + n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
+    }
+    if (!o.relax_mask || !o.n_hops) o.relax_mask = o.n_hops = nullptr;
+    for (size_t s = 0; o.n_hops && s < S; ++s)
+        if (o.n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (!o.quota) o.quota_used = nullptr, o.quota_why = nullptr;
+    if (S == 0) return FP_OK;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_batch d;
+    fp_policy_opts dopt;
+    fp_replan_dev dr;
+    const int n = fp_replan_rows(b, &o, prev, change_out, summary_out, &d, &dopt, &dr, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = fp_dev_replan_batch_policy_impl(c, &d, dr.prev, dopt, dr.change, dr.summary)) return rc;
+    return copy_back_all(c, rows, n);
+}
+
+extern "C" int fp_replan_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                                      const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                                      const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
+                                      uint8_t *hops_out, const uint32_t *quota, uint32_t *quota_used,
+                                      uint8_t *quota_why_out, uint8_t *change_out, uint32_t *summary_out) {
+    if (!c || !b) return FP_EINVAL;
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    o.relax_mask = relax_mask; o.n_hops = n_hops; o.hops = hops_out;
+    o.quota = quota; o.quota_used = quota_used; o.quota_why = quota_why_out;
+    return replan_policy_host(c, b, prev, o, change_out, summary_out);
+}
+
+extern "C" int fp_replan_policy(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const uint32_t *level,
+                                const uint32_t *prev, uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count,
+                                const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out, const uint32_t *quota,
+                                uint32_t *quota_used, uint8_t *quota_why_out, uint8_t *change_out, uint32_t *summary_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const fp_batch b = single_batch(cs, ns, level, assign_out, reason_out);
+    fp_policy_opts o = policy_opts(&strategy, &preferred_labels, node_count);
+    o.domain = domain; o.max_skew = &max_skew;
+    o.relax_mask = relax_mask; o.n_hops = &n_hops; o.hops = hops_out;
+    o.quota = quota; o.quota_used = quota_used; o.quota_why = quota_why_out;
+    return replan_policy_host(c, &b, prev, o, change_out, summary_out);
+}
+
+extern "C" int fp_dev_replan_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                                          const uint32_t *preferred_labels, uint32_t *node_count,
+                                          const uint32_t *domain, const uint32_t *max_skew, const uint32_t *relax_mask,
+                                          const uint32_t *n_hops, uint8_t *hops_out, const uint32_t *quota,
+                                          uint32_t *quota_used, uint8_t *quota_why_out, uint8_t *change_out,
+                                          uint32_t *summary_out) {
+    if (!c || !b) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_policy_opts o = policy_opts(strategy, preferred_labels, node_count);
+    o.domain = domain; o.max_skew = max_skew;
+    o.relax_mask = relax_mask; o.n_hops = n_hops; o.hops = hops_out;
+    o.quota = quota; o.quota_used = quota_used; o.quota_why = quota_why_out;
+    return fp_dev_done(c, fp_dev_replan_batch_policy_impl(c, b, prev, o, change_out, summary_out));
+}
+
 // ---- feasibility and rejection diagnosis -----------------------------------------
 extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns,
                               uint32_t *first_out, uint32_t *count_out, uint64_t *bitmap_out) {

@@ -191,6 +191,11 @@ int fp_dev_grow_sweep_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *re
 // range are found on the device (FP_EINVAL in the context's error word, nothing written)
 int fp_dev_replan_batch_impl(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o,
                              uint8_t *change_out, uint32_t *summary_out);
+// the same under the policy's guarantees (fp_replan_policy.hip, SPEC.md 2.14): of `o` the call reads every field.
+// A domain id out of range in a constrained scenario and an n_hops above FP_FALLBACK_MAX_HOPS are found on the
+// device with the strategy and prev values.  Without a guarantee it is fp_dev_replan_batch_impl
+int fp_dev_replan_batch_policy_impl(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o,
+                                    uint8_t *change_out, uint32_t *summary_out);
 
 // tile-pipeline FFD (fp_pipe.hip)
 bool fp_pipe_plan(const fp_ctx *c, uint32_t S, uint32_t N, uint32_t *G_out, uint32_t *W_out, uint32_t *B_out,

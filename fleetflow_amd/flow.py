@@ -785,15 +785,21 @@ def grow_stage(flow: Flow, stage_name: str, plan: Plan, catalogue: list[Server],
 
 @dataclass
 class Replan:
-    """``replan_stage``'s answer (SPEC.md 2.13): the stage's next plan and what it changes for the services that
-    ran under the previous one.  Services are listed in stage order."""
+    """``replan_stage``'s answer (SPEC.md 2.13, 2.14): the stage's next plan and what it changes for the services
+    that ran under the previous one.  Services are listed in stage order."""
     plan: Plan                                  # goes straight into drain_stage, grow_stage or the next replan_stage
     kept: list[str] = field(default_factory=list)                    # stayed on their server
     new: list[str] = field(default_factory=list)                     # did not run before, placed now
     moved: list[tuple[str, str, str]] = field(default_factory=list)  # (service, from, to)
-    lost: list[tuple[str, str, str]] = field(default_factory=list)   # (service, from, "NOFIT" | "CYCLE")
+    # (service, from, "NOFIT" | "CYCLE"; under the policy, SPEC.md 2.14, "SKEW" | "QUOTA" as well)
+    lost: list[tuple[str, str, str]] = field(default_factory=list)
     moved_cpu_m: int = 0                        # what the moved services ask for in sum: the migration volume
     moved_mem_mib: int = 0
+    # SPEC.md 2.14: kept seats are never evicted, so they alone may leave the stage outside a guarantee.  The
+    # final max - min of the eligible domains' counts when it exceeds max_skew (else None), and the quota
+    # dimensions ("cpu", "memory", "services") whose usage ends above their cap
+    skew_excess: int | None = None
+    quota_over: list[str] = field(default_factory=list)
 
 
 def _hard_guarantees(policy: PlacementPolicy | None, plan: Plan) -> list[str]:
@@ -807,22 +813,62 @@ def _hard_guarantees(policy: PlacementPolicy | None, plan: Plan) -> list[str]:
     return [name for name, there in zip(("spread constraint", "fallback chain", "resource quota"), found) if there]
 
 
+def replan_domains(nodes: list[Server], topology_key: str) -> tuple[list[int], list[bool]]:
+    """``spread_domains`` for a re-plan (SPEC.md 2.14).  A server without the key is no candidate, but pass 1
+    ignores ``schedulable``: what runs on it stays and is counted in its domain, and ``spread_domains``' id 0
+    would count it into the first value's domain.  Keyless servers get one spare id, the next unused one: it has
+    no schedulable server, so it is never eligible and its count is never read.  64 values and a keyless server
+    leave no spare id: a ValueError."""
+    from ._lib import FP_SPREAD_MAX_DOMAINS
+    domain, has_key = spread_domains(nodes, topology_key)
+    if all(has_key):
+        return domain, has_key
+    spare = max((d for d, k in zip(domain, has_key) if k), default=-1) + 1
+    if spare >= FP_SPREAD_MAX_DOMAINS:
+        raise ValueError(f"spread constraint: topology key '{topology_key}' has {spare} distinct values in this stage "
+                         f"and a server without the key: a re-plan needs a spare domain id for it (at most "
+                         f"{FP_SPREAD_MAX_DOMAINS} in all)")
+    return [d if k else spare for d, k in zip(domain, has_key)], has_key
+
+
+def _plan_policy(plan: Plan) -> PlacementPolicy:
+    """The policy ``plan`` was made under, rebuilt from its fields."""
+    caps = plan.quota if plan.quota is not None else (None, None, None)
+    return PlacementPolicy(plan.strategy, dict(lab.split("=", 1) for lab in plan.preferred), plan.spread_topology_key,
+                           plan.spread_max_skew, tuple(plan.fallback_relax_order), plan.fallback_max_hops, *caps)
+
+
 def replan_stage(flow: Flow, stage_name: str, plan: Plan, planner: Planner | None = None,
-                 policy: PlacementPolicy | None = None) -> Replan:
-    """The next plan of a stage that runs as ``plan`` says (SPEC.md 2.13): `fleet up` on a running stage.  The
-    tables are built as ``plan_stage`` builds them, from the flow as it is now (new requests, new servers); a
-    service keeps the server ``plan.assignment`` names while it still fits there -- on a cordoned server too --
-    and one ``Planner.replan`` call places the others under the strategy and preferred labels of ``policy`` or,
-    without one, of the policy the plan was made under.  Levels and orders are computed as in ``plan_stage``.
+                 policy: PlacementPolicy | None = None, under_policy: bool = False, quota_used=None) -> Replan:
+    """The next plan of a stage that runs as ``plan`` says (SPEC.md 2.13; with ``under_policy``, 2.14): `fleet up`
+    on a running stage.  The tables are built as ``plan_stage`` builds them, from the flow as it is now (new
+    requests, new servers); a service keeps the server ``plan.assignment`` names while it still fits there -- on a
+    cordoned server too -- and one ``Planner.replan`` call (``Planner.replan_policy`` with ``under_policy``) places
+    the others under the strategy and preferred labels of ``policy`` or, without one, of the policy the plan was
+    made under.  Levels and orders are computed as in ``plan_stage``.
 
     A service whose old server is no longer in the stage, or is flagged ``draining``, has no seat to keep: it
     goes to the planner as one that does not run, and is reported here as moved (from its old slug) or lost.
 
-    The spread constraint, the fallback chain and the quota are not applied by a re-plan, and a new plan must not
-    silently drop a hard guarantee: a ``policy`` that carries one, or without a policy a ``plan`` made under
-    one, is a ValueError that names it."""
-    from ._lib import CHANGE_KEPT, CHANGE_LOST, CHANGE_MOVED, CHANGE_NEW, REPLAN_MOVED_CPU, REPLAN_MOVED_MEM
-    hard = _hard_guarantees(policy, plan)
+    By default the spread constraint, the fallback chain and the quota are not applied by a re-plan, and a new
+    plan must not silently drop a hard guarantee: a ``policy`` that carries one, or without a policy a ``plan``
+    made under one, is a ValueError that names it.
+
+    ``under_policy=True`` applies them (SPEC.md 2.14, one ``Planner.replan_policy`` call): the guarantees of
+    ``policy`` or, without one, those rebuilt from the plan's ``spread_*``, ``fallback_*`` and ``quota`` fields.
+    ``quota_used`` is what the tenant holds outside this stage, as in ``plan_stage`` (default zeros);
+    ``plan.quota_used`` is the usage after that plan and is not the base.  Seats are kept without a skew or
+    quota test and are counted and charged; only new and moved services are held to the guarantees, and may be
+    rejected "SKEW" or "QUOTA".  The returned plan carries ``relaxed``, ``quota``, ``quota_used`` and
+    ``quota_why`` as ``plan_stage`` fills them, and ``Replan.skew_excess`` / ``Replan.quota_over`` say where the
+    seats alone leave the stage outside a guarantee.  Servers without the topology key take no new service, but
+    keep what runs on them (``replan_domains``)."""
+    from ._lib import (CHANGE_KEPT, CHANGE_LOST, CHANGE_MOVED, CHANGE_NEW, QUOTA_NAMES, REPLAN_MOVED_CPU,
+                       REPLAN_MOVED_MEM)
+    pol = None
+    if under_policy:
+        pol = policy if policy is not None else _plan_policy(plan)
+    hard = [] if under_policy else _hard_guarantees(policy, plan)
     if hard:
         raise ValueError(f"replan of stage '{stage_name}': the {' and the '.join(hard)} of the "
                          f"{'policy' if policy is not None else 'plan'} would not be applied (SPEC.md 2.13); "
@@ -864,11 +910,46 @@ def replan_stage(flow: Flow, stage_name: str, plan: Plan, planner: Planner | Non
         return out
     cont, ntab = _stage_tables(names, flow, nodes, preferred)
     pmask = _stage_labels(names, flow, nodes, preferred).mask(preferred)
-    assign, reason, change, summary, _, _ = p.replan(cont, ntab, prev, strategy if strategy is not None else 0, pmask,
-                                                     level=[lvl_v[n] for n in names])
+    if pol is None:
+        assign, reason, change, summary, _, _ = p.replan(cont, ntab, prev, strategy if strategy is not None else 0, pmask,
+                                                         level=[lvl_v[n] for n in names])
+    else:
+        domain, max_skew = None, 0
+        if pol.spread is not None:
+            domain, has_key = replan_domains(nodes, pol.spread[0])
+            max_skew = pol.spread[1]
+            ntab = (*ntab[:4], [s if k else 0 for s, k in zip(ntab[4], has_key)])
+            new_plan.spread_topology_key, new_plan.spread_max_skew = pol.spread
+        ld = _stage_labels(names, flow, nodes, preferred)
+        relax = [ld.key_mask(k) for k in pol.fallback]
+        base = (0, 0, 0) if quota_used is None else tuple(int(x) for x in quota_used)
+        assign, reason, hops, change, summary, _, counts, qwhy, qused = p.replan_policy(
+            cont, ntab, prev, strategy if strategy is not None else 0, pol.quota, base, relax, preferred=pmask,
+            level=[lvl_v[n] for n in names], node_count=[0] * len(nodes), domain=domain, max_skew=max_skew)
+        if pol.fallback:
+            new_plan.fallback_relax_order, new_plan.fallback_max_hops = list(pol.fallback_relax_order), pol.fallback_max_hops
+            for v, n in enumerate(names):
+                if int(assign[v]) != NONE and int(hops[v]):
+                    required = {lab.split("=", 1)[0] for lab in flow.services.get(n, Service()).labels}
+                    new_plan.relaxed[n] = [k for k in pol.fallback[:int(hops[v])] if k in required]
+        if pol.quota is not None:
+            new_plan.quota, new_plan.quota_used = pol.quota, tuple(int(x) for x in qused)
+            new_plan.quota_why = {n: [d for k, d in enumerate(QUOTA_NAMES) if int(qwhy[v]) >> k & 1]
+                                  for v, n in enumerate(names) if int(reason[v]) == 4}
+            out.quota_over = [d for d, cap, u in zip(QUOTA_NAMES, pol.quota, new_plan.quota_used)
+                              if cap is not None and u > cap]
+        if pol.spread is not None:
+            per, eligible = {}, set()
+            for n, d in enumerate(domain):
+                per[d] = per.get(d, 0) + int(counts[n])
+                if ntab[4][n]:
+                    eligible.add(d)
+            if eligible:
+                skew = max(per[d] for d in eligible) - min(per[d] for d in eligible)
+                out.skew_excess = skew if skew > max_skew else None
     out.moved_cpu_m, out.moved_mem_mib = int(summary[REPLAN_MOVED_CPU]), int(summary[REPLAN_MOVED_MEM])
     for v, name in enumerate(names):
-        why = "CYCLE" if int(reason[v]) == 2 else "NOFIT"
+        why = {2: "CYCLE", 3: "SKEW", 4: "QUOTA"}.get(int(reason[v]), "NOFIT")
         if int(assign[v]) != NONE:
             new_plan.assignment[name] = slugs[int(assign[v])]
         else:

@@ -130,14 +130,25 @@ def format_replan_report(report: Replan) -> str:
     lines += [f"  {svc}: {src} -> {dst}" for svc, src, dst in report.moved]
     lines += [f"  {svc}: -> {plan.assignment[svc]}" for svc in report.new]
     lines += [f"  {svc}: {src} -> lost ({why})" for svc, src, why in report.lost]
+    # SPEC.md 2.14: what the kept seats alone leave outside the guarantees; printed only when set
+    if report.skew_excess is not None:
+        lines.append(f"  spread: skew {report.skew_excess} over {plan.spread_topology_key} exceeds max_skew "
+                     f"{plan.spread_max_skew} (kept seats are not evicted)")
+    if report.quota_over:
+        lines.append(f"  quota: usage above the cap in {', '.join(report.quota_over)} (kept seats are not evicted)")
     return "\n".join(lines)
 
 
 def replan_report_to_json(report: Replan, indent: int | None = None) -> str:
-    """``{plan: <plan_to_json's object>, kept, new, moved, lost, moved_cpu_m, moved_mem_mib}``."""
+    """``{plan: <plan_to_json's object>, kept, new, moved, lost, moved_cpu_m, moved_mem_mib}``, and
+    ``skew_excess`` / ``quota_over`` (SPEC.md 2.14) only when set."""
     d = {"plan": json.loads(plan_to_json(report.plan)), "kept": report.kept, "new": report.new,
          "moved": [list(m) for m in report.moved], "lost": [list(x) for x in report.lost],
          "moved_cpu_m": report.moved_cpu_m, "moved_mem_mib": report.moved_mem_mib}
+    if report.skew_excess is not None:
+        d["skew_excess"] = report.skew_excess
+    if report.quota_over:
+        d["quota_over"] = report.quota_over
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
@@ -145,7 +156,8 @@ def replan_report_from_json(text: str) -> Replan:
     d = json.loads(text)
     return Replan(plan_from_json(json.dumps(d["plan"], ensure_ascii=False)), list(d.get("kept") or []),
                   list(d.get("new") or []), [tuple(m) for m in d.get("moved") or []],
-                  [tuple(x) for x in d.get("lost") or []], d.get("moved_cpu_m", 0), d.get("moved_mem_mib", 0))
+                  [tuple(x) for x in d.get("lost") or []], d.get("moved_cpu_m", 0), d.get("moved_mem_mib", 0),
+                  d.get("skew_excess"), list(d.get("quota_over") or []))
 
 
 def format_grow_report(report: GrowReport) -> str:

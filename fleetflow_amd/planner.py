@@ -528,6 +528,48 @@ class Planner:
               "fp_replan_batch")
         return o.assign, o.reason, o.cost, change, summary, o.nodes, o.nc
 
+    def replan_policy(self, cont, nodes, prev, strategy=0, quota=None, quota_used=None, relax_mask=None, preferred=0,
+                      level=None, node_count=None, *, domain=None, max_skew=0, n_hops=None, want_hops=True,
+                      want_why=True, want_used=True, want_change=True, want_summary=True):
+        """replan under the policy's guarantees (SPEC.md 2.14, fp_replan_policy): ``domain`` / ``max_skew``,
+        ``relax_mask`` / ``n_hops`` and ``quota`` / ``quota_used`` as in place_policy_quota, each one optional.
+        A container keeps its node while it fits there under the labels the whole chain still asks for; seats
+        are neither tested against the skew bound or the quota nor evicted, but they count in their domains and
+        are charged.  The others are placed as place_policy_quota places them, on the counts and the usage the
+        seats left.  Without a guarantee it is replan; ``prev`` all NONE is place_policy_quota.  Returns (assign,
+        reason, hops, change, summary, nodes_after, node_count_after, quota_why, quota_used_after); the
+        ``want_*`` switches as in place_policy_quota and replan."""
+        o = _policy_call(None, cont, nodes, strategy, preferred, level, node_count, domain, max_skew,
+                         relax_mask, n_hops, quota, quota_used, want_hops, want_why, want_used)
+        C = o.cont[0].size
+        pv = _u32(prev).reshape(-1)
+        self._need(pv.size == C, "prev must hold C entries")
+        change = np.empty(C, np.uint8) if want_change else None
+        summary = np.empty(_lib.REPLAN_WORDS, np.uint32) if want_summary else None
+        chain = o.chain if o.rm is not None else (None, 0)
+        check(self._L.fp_replan_policy(self._ctx, *o.head[:3], _arg(pv), *o.head[3:], *o.spread, *chain, _arg(o.assign),
+                                       _arg(o.reason), _arg(o.hops), _arg(o.qt), _arg(o.qu), _arg(o.why), _arg(change),
+                                       _arg(summary)), "fp_replan_policy")
+        return o.assign, o.reason, o.hops, change, summary, o.nodes, o.nc, o.why, o.qu
+
+    def replan_batch_policy(self, S, C, N, cont, nodes, prev, strategy, quota=None, quota_used=None, preferred=None,
+                            level=None, node_count=None, scen_base=0, *, domain=None, max_skew=None, relax_mask=None,
+                            n_hops=None, want_hops=True, want_why=True, want_used=True, want_change=True,
+                            want_summary=True):
+        """replan_policy over scenario-major arrays (fp_replan_batch_policy): the arrays of replan_batch and of
+        place_batch_policy_quota.  Returns (assign, reason, hops, cost, change [S*C], summary [S, 8], nodes_after,
+        node_count_after, quota_why [S*C], quota_used_after [S*3])."""
+        o = _policy_call((S, C, N, scen_base), cont, nodes, strategy, preferred, level, node_count, domain,
+                         max_skew, relax_mask, n_hops, quota, quota_used, want_hops, want_why, want_used)
+        pv = _u32(prev).reshape(-1)
+        self._need(pv.size == S * C, "prev must hold S * C entries")
+        change = np.empty(S * C, np.uint8) if want_change else None
+        summary = np.empty((S, _lib.REPLAN_WORDS), np.uint32) if want_summary else None
+        check(self._L.fp_replan_batch_policy(self._ctx, o.head[0], _arg(pv), *o.head[1:], *o.spread, *o.chain,
+                                             _arg(o.hops), _arg(o.qt), _arg(o.qu), _arg(o.why), _arg(change),
+                                             _arg(summary)), "fp_replan_batch_policy")
+        return o.assign, o.reason, o.hops, o.cost, change, summary, o.nodes, o.nc, o.why, o.qu
+
     def feasibility(self, cont, nodes, bitmap=True):
         cont, nodes = _tables(cont, nodes, None, None, False)
         C, N = cont[0].size, nodes[0].size
@@ -812,6 +854,31 @@ class Planner:
         args = [_arg(t) for t in (prev_t, strategy_t, preferred_t, count_t, change_t, summary_t)]
         self._dev(lambda: check(self._L.fp_dev_replan_batch(self._ctx, ct.byref(db.struct()), *args),
                                 "fp_dev_replan_batch"))
+
+    def dev_replan_batch_policy(self, db: "DevBatch", prev_t, strategy_t, quota_t=None, quota_used_t=None,
+                                preferred_t=None, count_t=None, *, domain_t=None, max_skew_t=None, relax_mask_t=None,
+                                n_hops_t=None, hops_t=None, quota_why_t=None, change_t=None, summary_t=None):
+        """fp_dev_replan_batch_policy (SPEC.md 2.14) on device tensors: the tensors of dev_replan_batch and of
+        dev_place_batch_policy_quota.  A strategy, prev, domain or n_hops value out of range is found on the
+        device: nothing is written, ``quota_used_t`` included, and sync() raises FP_EINVAL.  Returns (hops_t,
+        quota_why_t, quota_used_t)."""
+        pairs = _dev_policy_checks(db, strategy_t, preferred_t, count_t, domain_t, max_skew_t, relax_mask_t, n_hops_t,
+                                   hops_t)
+        self._need(prev_t.numel() == db.S * db.C and prev_t.element_size() == 4, "prev_t must hold S * C 32-bit entries")
+        for t in (quota_t, quota_used_t):
+            self._need(t is None or (t.numel() == db.S * _lib.QUOTA_DIMS and t.element_size() == 4),
+                       "quota_t and quota_used_t must hold S * 3 32-bit entries")
+        self._need(quota_why_t is None or (quota_why_t.numel() == db.S * db.C and quota_why_t.element_size() == 1),
+                   "quota_why_t must hold S * C bytes")
+        self._need(change_t is None or (change_t.numel() == db.S * db.C and change_t.element_size() == 1),
+                   "change_t must hold S * C bytes")
+        self._need(summary_t is None or (summary_t.numel() == db.S * _lib.REPLAN_WORDS and summary_t.element_size() == 4),
+                   "summary_t must hold S * 8 32-bit entries")
+        args = [_arg(t) for t in (prev_t, strategy_t, preferred_t, count_t, *pairs, hops_t, quota_t, quota_used_t,
+                                  quota_why_t, change_t, summary_t)]
+        self._dev(lambda: check(self._L.fp_dev_replan_batch_policy(self._ctx, ct.byref(db.struct()), *args),
+                                "fp_dev_replan_batch_policy"))
+        return hops_t, quota_why_t, quota_used_t
 
     def dev_argmin_cost(self, cost_t, out_t):
         self._dev(lambda: check(self._L.fp_dev_argmin_cost(self._ctx, cost_t.data_ptr(), cost_t.numel(),

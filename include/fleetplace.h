@@ -37,6 +37,9 @@
  *                        it still fits there and only the others are placed.  `cordon` "stops new placements,
  *                        existing placements continue" (crates/fleetflow-controlplane/src/model.rs:435-442);
  *                        ServerAllocated is committed and released per placement (model.rs:421-427)
+ *   fp_replan_policy  <- new: the same under the policy's SpreadConstraint, FallbackPolicy and ResourceQuota:
+ *                        the seats are counted and charged, never tested or evicted; only new and moved
+ *                        placements are held to the guarantees (model.rs:38-63)
  *
  * Conventions
  *   - All buffers are caller-owned; no allocation crosses the ABI.
@@ -430,6 +433,35 @@ int fp_replan(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32
 int fp_replan_batch(fp_ctx *ctx, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
                     const uint32_t *preferred_labels, uint32_t *node_count, uint8_t *change_out,
                     uint32_t *summary_out);
+/* Re-planning under the tenant's policy (SPEC.md 2.14): fp_replan with the spread constraint, the fallback chain and
+ * the resource quota of fp_place_policy_quota, whose arguments these are and in whose order they stand; every one of
+ * them is nullable with the meaning it has there (domain NULL or max_skew 0: no constraint; relax_mask NULL or n_hops
+ * 0: no chain; quota NULL: no quota, and quota_used and quota_why_out are not touched).
+ * Pass 1 (seats) is fp_replan's, with the labels tested under the whole chain, req & ~cum[n_hops]; there is NO skew
+ * test and NO quota test: the guarantees gate the admission of new placements, they count what runs and never evict
+ * it (k8s PodTopologySpread and ResourceQuota).  A kept container's hop is the first hop at which prev's labels
+ * match, its quota_why is 0, and it is charged: used[d] += r[d] in all three dimensions (u32, wraps).
+ * Pass 2 places every container that is neither CYCLE nor kept exactly as fp_place_policy_quota would, on the state
+ * pass 1 left: the node table, the counts -- seats count in their domains, on cordoned nodes too -- and the usage
+ * with the seats' charges; a usage the seats put above a cap blocks every non-zero request in that dimension.
+ * Reasons OK, NOFIT, SKEW, QUOTA and CYCLE; change_out and summary_out as fp_replan's, FP_CHANGE_LOST covering every
+ * rejection of a container that had a prev.  So no new or moved placement breaks the skew bound relative to the
+ * current counts or is admitted past a cap, while the seats alone may leave max - min > max_skew or a usage above
+ * a cap.  Without any guarantee the call is fp_replan; with prev all FP_NONE it is fp_place_policy_quota.
+ * The errors are fp_replan's and fp_place_policy_fallback's (a domain id >= FP_SPREAD_MAX_DOMAINS in a scenario
+ * with max_skew != 0, n_hops > FP_FALLBACK_MAX_HOPS: FP_EINVAL); on any error nothing is written, quota_used
+ * included. */
+int fp_replan_policy(fp_ctx *ctx, const fp_containers *c, fp_nodes *nodes, const uint32_t *level, const uint32_t *prev,
+                     uint32_t strategy, uint32_t preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                     uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
+                     uint8_t *reason_out, uint8_t *hops_out, const uint32_t *quota, uint32_t *quota_used,
+                     uint8_t *quota_why_out, uint8_t *change_out, uint32_t *summary_out);
+/* The batch form: the arrays of fp_replan_batch and of fp_place_batch_policy_quota, per scenario. */
+int fp_replan_batch_policy(fp_ctx *ctx, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                           const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                           const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
+                           uint8_t *hops_out, const uint32_t *quota, uint32_t *quota_used, uint8_t *quota_why_out,
+                           uint8_t *change_out, uint32_t *summary_out);
 /* One stage's whole plan, the `fleet up --dry-run` path (crates/fleetflow/src/commands/up.rs:57-136):
  *   perm_out                 A1 legacy start order (engine.rs:64-85, as fp_legacy_order)
  *   level_out, order_out, n_cycle_out   A2 levels and start order (as fp_levelize)
@@ -520,6 +552,16 @@ int fp_dev_grow_sweep(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason
 int fp_dev_replan_batch(fp_ctx *ctx, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
                         const uint32_t *preferred_labels, uint32_t *node_count, uint8_t *change_out,
                         uint32_t *summary_out);
+/* As fp_replan_batch_policy on device pointers.  A strategy, prev, domain or n_hops value out of range is found on
+ * the device before any store: nothing is written, quota_used included, and fp_ctx_sync() reports FP_EINVAL.  The
+ * call takes the FFD order's 24 bytes per container plus the sort's scratch from the context's workspace (which
+ * container was kept is marked in a buffer of the order's); without any guarantee it is fp_dev_replan_batch,
+ * with 256 bytes more when hops_out is given. */
+int fp_dev_replan_batch_policy(fp_ctx *ctx, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
+                               const uint32_t *preferred_labels, uint32_t *node_count, const uint32_t *domain,
+                               const uint32_t *max_skew, const uint32_t *relax_mask, const uint32_t *n_hops,
+                               uint8_t *hops_out, const uint32_t *quota, uint32_t *quota_used,
+                               uint8_t *quota_why_out, uint8_t *change_out, uint32_t *summary_out);
 /* Best plan over a cost vector (device): writes the argmin index to *best_dev. */
 int fp_dev_argmin_cost(fp_ctx *ctx, const uint64_t *cost, uint32_t n, uint32_t *best_dev);
 

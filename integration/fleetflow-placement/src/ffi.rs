@@ -252,6 +252,17 @@ unsafe extern "C" {
     pub fn fp_replan_batch(ctx: *mut fp_ctx, b: *const fp_batch, prev: *const u32, strategy: *const u32,
                            preferred_labels: *const u32, node_count: *mut u32, change_out: *mut u8,
                            summary_out: *mut u32) -> c_int;
+    pub fn fp_replan_policy(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
+                            prev: *const u32, strategy: u32, preferred_labels: u32, node_count: *mut u32,
+                            domain: *const u32, max_skew: u32, relax_mask: *const u32, n_hops: u32,
+                            assign_out: *mut u32, reason_out: *mut u8, hops_out: *mut u8, quota: *const u32,
+                            quota_used: *mut u32, quota_why_out: *mut u8, change_out: *mut u8,
+                            summary_out: *mut u32) -> c_int;
+    pub fn fp_replan_batch_policy(ctx: *mut fp_ctx, b: *const fp_batch, prev: *const u32, strategy: *const u32,
+                                  preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                  max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
+                                  hops_out: *mut u8, quota: *const u32, quota_used: *mut u32,
+                                  quota_why_out: *mut u8, change_out: *mut u8, summary_out: *mut u32) -> c_int;
     pub fn fp_plan_stage(ctx: *mut fp_ctx, g: *const fp_graph, c: *const fp_containers, nodes: *mut fp_nodes,
                          perm_out: *mut u32, level_out: *mut u32, order_out: *mut u32, n_cycle_out: *mut u32,
                          first_out: *mut u32, count_out: *mut u32, assign_out: *mut u32, reason_out: *mut u8)
@@ -295,6 +306,11 @@ unsafe extern "C" {
     pub fn fp_dev_replan_batch(ctx: *mut fp_ctx, b: *const fp_batch, prev: *const u32, strategy: *const u32,
                                preferred_labels: *const u32, node_count: *mut u32, change_out: *mut u8,
                                summary_out: *mut u32) -> c_int;
+    pub fn fp_dev_replan_batch_policy(ctx: *mut fp_ctx, b: *const fp_batch, prev: *const u32, strategy: *const u32,
+                                      preferred_labels: *const u32, node_count: *mut u32, domain: *const u32,
+                                      max_skew: *const u32, relax_mask: *const u32, n_hops: *const u32,
+                                      hops_out: *mut u8, quota: *const u32, quota_used: *mut u32,
+                                      quota_why_out: *mut u8, change_out: *mut u8, summary_out: *mut u32) -> c_int;
     pub fn fp_dev_argmin_cost(ctx: *mut fp_ctx, cost: *const u64, n: u32, best_dev: *mut u32) -> c_int;
     pub fn fp_dev_gen_batch(ctx: *mut fp_ctx, seed: u64, b: *const fp_batch, flags: u32) -> c_int;
 }

@@ -19,6 +19,15 @@ before it, after `warmup` calls of every leg; a round times `steps` calls of eac
 the legs alternate, and the rounds' minimum, median and maximum are kept.  The kernels' own time comes from the
 context's event brackets (FP_K_PLACE, FP_K_SORT) in a separate pass.  No time is a target.  Writes
 profiles/replan_timing.json and prints it.
+
+    python tools/replan_timing.py --policy [...]
+
+The same four legs under the policy (SPEC.md 2.14), with the spread constraint (domain = n % 4, max_skew 4), the
+chain [0x780, 0x78] and a quota on: per scenario, three quarters of the cpu, memory and services its plan uses
+without a cap.  (a) is fp_dev_place_batch_policy_quota, (b) to (d) are fp_dev_replan_batch_policy.  (b) must
+equal (a) in every output, hops, quota_why and the usage included; (c) is theorem D: every placed container KEPT
+on its node with its hop, and the same assignment when (a) rejected nothing for SKEW.  If either fails the
+tool stops before it times anything.  Writes profiles/replan_policy_timing.json.
 """
 import argparse
 import dataclasses
@@ -52,8 +61,10 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "replan_timing.json"))
+    ap.add_argument("--policy", action="store_true", help="under spread + chain + quota (SPEC.md 2.14)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "replan_policy_timing.json" if a.policy else "replan_timing.json")
     S, C, N = a.scenarios, a.containers, a.nodes
     dev = torch.device("cuda", 0)
     props = torch.cuda.get_device_properties(dev)
@@ -73,32 +84,81 @@ def main():
         no_prev = torch.full((S * C,), -1, dtype=torch.int32, device=dev)
         chg = torch.zeros(S * C, dtype=torch.uint8, device=dev)
         summ = torch.zeros(S * _lib.REPLAN_WORDS, dtype=torch.int32, device=dev)
+        if a.policy:
+            out["policy"] = {"domain": "n % 4", "max_skew": 4, "relax_mask": [0x780, 0x78], "n_hops": 2,
+                             "quota": "per scenario, 3/4 of the cpu, memory and services its uncapped plan uses"}
+            pk = dict(domain_t=(torch.arange(S * N, device=dev) % N % 4).to(torch.int32),
+                      max_skew_t=torch.full((S,), 4, dtype=torch.int32, device=dev),
+                      relax_mask_t=torch.tensor([0x780, 0x78, 0, 0] * S, dtype=torch.int32, device=dev),
+                      n_hops_t=torch.full((S,), 2, dtype=torch.int32, device=dev),
+                      hops_t=torch.zeros(S * C, dtype=torch.uint8, device=dev),
+                      quota_why_t=torch.zeros(S * C, dtype=torch.uint8, device=dev))
+            used = torch.zeros(S * _lib.QUOTA_DIMS, dtype=torch.int32, device=dev)
+        else:
+            used = None
+
+        def restore():  # the base state of every call: the node tables (dbg shares db's) and, under the policy, the usage
+            db.restore_nodes(snap)
+            if used is not None:
+                used.zero_()
         for name, sid in STRATEGIES:
             st = torch.full((S,), sid, dtype=torch.int32, device=dev)
             # ---- the answers first ----
-            db.restore_nodes(snap)
-            p.dev_place_batch_policy(db, st)
+            restore()
+            if a.policy:
+                caps = torch.full((S * _lib.QUOTA_DIMS,), -1, dtype=torch.int32, device=dev)
+                p.dev_place_batch_policy_quota(db, st, caps, used, **pk)
+                p.sync()
+                caps = (used.long() * 3 // 4).to(torch.int32)  # below 2^31 on this shape
+                restore()
+                calls = {"a_place": lambda: p.dev_place_batch_policy_quota(db, st, caps, used, **pk),
+                         "b_no_prev": lambda: p.dev_replan_batch_policy(db, no_prev, st, caps, used, **pk, change_t=chg,
+                                                                        summary_t=summ),
+                         "c_fixed_point": lambda: p.dev_replan_batch_policy(db, plan, st, caps, used, **pk, change_t=chg,
+                                                                            summary_t=summ),
+                         "d_grown": lambda: p.dev_replan_batch_policy(dbg, plan, st, caps, used, **pk, change_t=chg,
+                                                                      summary_t=summ)}
+                extra = lambda: (pk["hops_t"].clone(), pk["quota_why_t"].clone(), used.clone())  # noqa: E731
+            else:
+                calls = {"a_place": lambda: p.dev_place_batch_policy(db, st),
+                         "b_no_prev": lambda: p.dev_replan_batch(db, no_prev, st, None, None, chg, summ),
+                         "c_fixed_point": lambda: p.dev_replan_batch(db, plan, st, None, None, chg, summ),
+                         "d_grown": lambda: p.dev_replan_batch(dbg, plan, st, None, None, chg, summ)}
+                extra = lambda: ()  # noqa: E731
+            calls["a_place"]()
             p.sync()
             plan, reason_a, cost_a = db.assign.clone(), db.reason.clone(), db.cost.clone()
-            nodes_a = db.node_snapshot()
-            calls = {"a_place": lambda: p.dev_place_batch_policy(db, st),
-                     "b_no_prev": lambda: p.dev_replan_batch(db, no_prev, st, None, None, chg, summ),
-                     "c_fixed_point": lambda: p.dev_replan_batch(db, plan, st, None, None, chg, summ),
-                     "d_grown": lambda: p.dev_replan_batch(dbg, plan, st, None, None, chg, summ)}
+            nodes_a, extra_a = db.node_snapshot(), extra()
             rec = {"placed": int((plan != -1).sum().item())}
-            db.restore_nodes(snap)
+            if a.policy:
+                rec["reasons"] = dict(zip(("ok", "nofit", "cycle", "skew", "quota"),
+                                          torch.bincount(reason_a.long(), minlength=5).tolist()))
+            restore()
             calls["b_no_prev"]()
             p.sync()
             rec["b_equals_a"] = bool(torch.equal(db.assign, plan) and torch.equal(db.reason, reason_a)
                                      and torch.equal(db.cost, cost_a)
-                                     and all(torch.equal(x, y) for x, y in zip(db.node_snapshot(), nodes_a)))
-            db.restore_nodes(snap)
+                                     and all(torch.equal(x, y) for x, y in zip(db.node_snapshot(), nodes_a))
+                                     and all(torch.equal(x, y) for x, y in zip(extra(), extra_a)))
+            restore()
             calls["c_fixed_point"]()
             p.sync()
-            rec["c_is_fixed_point"] = bool(torch.equal(db.assign, plan) and torch.equal(db.reason, reason_a)
-                                           and bool((chg[plan != -1] == _lib.CHANGE_KEPT).all().item())
-                                           and all(torch.equal(x, y) for x, y in zip(db.node_snapshot(), nodes_a)))
-            db.restore_nodes(snap)
+            was = plan != -1
+            if a.policy:  # theorem D, as far as it goes
+                same = bool(torch.equal(db.assign[was], plan[was]) and (chg[was] == _lib.CHANGE_KEPT).all().item()
+                            and torch.equal(pk["hops_t"][was], extra_a[0][was]))
+                if not bool((reason_a == _lib.REASON_SKEW).any().item()):
+                    same = same and bool(torch.equal(db.assign, plan) and torch.equal(used, extra_a[2])
+                                         and all(torch.equal(x, y) for x, y in zip(db.node_snapshot(), nodes_a)))
+                rec["c_is_theorem_d"] = same
+                rec["c_skew_placed"] = int(((reason_a == _lib.REASON_SKEW) & (db.assign != -1)).sum().item())
+                if not (rec["b_equals_a"] and same):  # a wrong answer is not worth timing
+                    raise SystemExit(f"{name}: b_equals_a = {rec['b_equals_a']}, c_is_theorem_d = {same}: not timed")
+            else:
+                rec["c_is_fixed_point"] = bool(torch.equal(db.assign, plan) and torch.equal(db.reason, reason_a)
+                                               and bool((chg[was] == _lib.CHANGE_KEPT).all().item())
+                                               and all(torch.equal(x, y) for x, y in zip(db.node_snapshot(), nodes_a)))
+            restore()
             calls["d_grown"]()
             p.sync()
             words = summ.view(S, _lib.REPLAN_WORDS)[:, :5].long().sum(0).tolist()
@@ -106,7 +166,7 @@ def main():
             # ---- wall time, the legs alternating ----
             for _ in range(a.warmup):
                 for leg in LEGS:
-                    db.restore_nodes(snap)
+                    restore()
                     calls[leg]()
             p.sync()
             wall = {leg: [] for leg in LEGS}
@@ -114,7 +174,7 @@ def main():
                 for leg in LEGS:
                     t = 0.0
                     for _ in range(a.steps):
-                        db.restore_nodes(snap)
+                        restore()
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
                         calls[leg]()
@@ -125,7 +185,7 @@ def main():
             for leg in LEGS:
                 p.profile(True)
                 for _ in range(a.steps):
-                    db.restore_nodes(snap)
+                    restore()
                     calls[leg]()
                 p.sync()
                 kp, n = p.kernel_stats(_lib.FP_K_PLACE)
