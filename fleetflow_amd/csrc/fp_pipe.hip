@@ -1548,13 +1548,140 @@ __global__ void k_gather_payload(uint32_t S, uint32_t C, const uint32_t *__restr
 }
 
 // The same payload as k_gather_payload with every HBM access coalesced: one workgroup per
-// scenario.  Each thread owns the sorted positions t + 1024 j; per half of them (25 per thread:
-// registers) it keeps their container indices, then streams the scenario's (req, conf) pairs
-// through LDS in chunks of PL_CHUNK and picks its positions' values out of the chunk that holds
-// them (level the same way first, for the CYCLE bits).  k_gather_payload's two random 4-B reads
-// per container ran at the L2 request rate (2.2 ms for 4096 x 50k).  C <= PL_MAX_C.
+// scenario.  Each thread owns the sorted positions t + 1024 j, keeps their container indices in
+// registers, streams the scenario's inputs through LDS in chunks of PL_CHUNK and picks its
+// positions' values out of the chunk that holds them (level first, for the CYCLE bits).
+// k_gather_payload's two random 4-B reads per container ran at the L2 request rate (2.2 ms for
+// 4096 x 50k; round 3's form below 1.12 ms, by field 0.86 ms).  C <= PL_MAX_C.
 constexpr uint32_t PL_THREADS = 1024, PL_H = 25, PL_MAX_C = PL_THREADS * PL_H * 2;
+// FPP_PAYLOAD_BY_FIELD (A/B switch): 1 = the passes of k_payload_lds are split by field, and order, level,
+// conf and req are each read once per scenario; 0 = round 3's kernel, split by position half, which reads
+// (req, conf) and level once per half.
+#ifndef FPP_PAYLOAD_BY_FIELD
+#define FPP_PAYLOAD_BY_FIELD 1
+#endif
+#if FPP_PAYLOAD_BY_FIELD
+// By field: a thread keeps the container indices of all its 2 PL_H positions for the whole kernel, as u16
+// pairs (PL_H registers: an index is below C <= PL_MAX_C < 0xFFFF, and 0xFFFF marks a position past
+// C, which no chunk holds).  level, conf and req then take one pass each through LDS in chunks of
+// PL_CHUNK words: level leaves a CYCLE bit per position, conf is written as soon as its last chunk
+// has been picked and leaves the bit (conf & summ[1]) != 0, req joins the bits and is written with the
+// reason codes.  Per container 4 B of order and 4 B per field are read, 8 B written and s_idx
+// touched where the bit is set, as before.
+constexpr uint32_t PL_ROWS = 2 * PL_H;
+constexpr uint32_t PL_CHUNK = 36 * 1024;  // words of one field: 144 KB of LDS
+constexpr size_t PL_LDS_BYTES = (size_t)PL_CHUNK * 4;
+static_assert(PL_MAX_C < 0xFFFFu, "container indices are kept in 16 bits, 0xFFFF = no position");
+
+// the two indices of pair j, less the chunk's base.  The empty asm keeps the unpacking inside the chunk loop:
+// hoisted out of it, the 2 PL_H unpacked indices live beside the 2 PL_H values and the kernel spills.
+__device__ __forceinline__ void pl_index(uint32_t w, uint32_t a0, uint32_t &d0, uint32_t &d1) {
+    asm volatile("" : "+v"(w));
+    d0 = (w & 0xFFFFu) - a0;
+    d1 = (w >> 16) - a0;
+}
+__device__ __forceinline__ void pl_load_chunk(uint32_t *pl_lds, const uint32_t *__restrict__ src, uint32_t n) {
+    __syncthreads();  // the previous chunk's picks are done
+#pragma unroll 8
+    for (uint32_t i = threadIdx.x; i < n; i += PL_THREADS) pl_lds[i] = __builtin_nontemporal_load(&src[i]);
+    __syncthreads();
+}
+__device__ __forceinline__ void pl_pick_field(uint32_t *pl_lds, const uint32_t *__restrict__ field, uint32_t C,
+                                              const uint32_t (&o)[PL_H], uint32_t (&v)[PL_ROWS]) {
+    for (uint32_t a0 = 0; a0 < C; a0 += PL_CHUNK) {
+        const uint32_t n = C - a0 < PL_CHUNK ? C - a0 : PL_CHUNK;
+        pl_load_chunk(pl_lds, field + a0, n);
+#pragma unroll
+        for (uint32_t j = 0; j < PL_H; ++j) {
+            uint32_t d0, d1;
+            pl_index(o[j], a0, d0, d1);
+            if (d0 < n) v[2 * j] = pl_lds[d0];
+            if (d1 < n) v[2 * j + 1] = pl_lds[d1];
+        }
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_payload_lds(uint32_t C, const uint32_t *__restrict__ order,
+                                                      const uint32_t *__restrict__ req,
+                                                      const uint32_t *__restrict__ conf,
+                                                      const uint32_t *__restrict__ level,
+                                                      const uint32_t *__restrict__ summ,
+                                                      uint32_t *__restrict__ s_req, uint32_t *__restrict__ s_conf,
+                                                      uint32_t *__restrict__ s_idx) {
+    extern __shared__ uint32_t pl_lds[];
+    const uint32_t t = threadIdx.x;
+    const size_t cb = (size_t)blockIdx.x * C;
+    const uint32_t sm0 = summ ? summ[(size_t)blockIdx.x * 4] : 0xFFFFFFFFu;
+    const uint32_t sm1 = summ ? summ[(size_t)blockIdx.x * 4 + 1] : 0u;
+    uint32_t o[PL_H];
+    {
+        uint32_t i[PL_ROWS];  // every load in flight at once; past C the last element, not used
+        const uint32_t *ord = order + cb;
+#pragma unroll
+        for (uint32_t j = 0; j < PL_ROWS; ++j) {
+            const uint32_t p = t + PL_THREADS * j;
+            const uint32_t x = __builtin_nontemporal_load(&ord[p < C ? p : C - 1]);
+            i[j] = p < C ? x & 0xFFFFu : 0xFFFFu;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < PL_H; ++j) o[j] = i[2 * j] | i[2 * j + 1] << 16;
+    }
+    // bit j % 32 of cy0 / cy1 (j < 32 / the rest): position t + 1024 j is a CYCLE member; sc0 / sc1 the same
+    // for (conf & summ[1]) != 0
+    uint32_t cy0 = 0, cy1 = 0;
+    if (level) {
+        for (uint32_t a0 = 0; a0 < C; a0 += PL_CHUNK) {
+            const uint32_t n = C - a0 < PL_CHUNK ? C - a0 : PL_CHUNK;
+            pl_load_chunk(pl_lds, level + cb + a0, n);
+#pragma unroll
+            for (uint32_t j = 0; j < PL_H; ++j) {
+                uint32_t d0, d1;
+                pl_index(o[j], a0, d0, d1);
+                if (d0 < n) (j < 16 ? cy0 : cy1) |= (uint32_t)(pl_lds[d0] == FP_NONE) << ((2 * j) & 31u);
+                if (d1 < n) (j < 16 ? cy0 : cy1) |= (uint32_t)(pl_lds[d1] == FP_NONE) << ((2 * j + 1) & 31u);
+            }
+        }
+    }
+    uint32_t v[PL_ROWS];
+    uint32_t sc0 = 0, sc1 = 0;
+    pl_pick_field(pl_lds, conf + cb, C, o, v);
+    // (each phase takes its positions and their bound from copies of t and C that the compiler cannot see
+    // through: it kept the order loads' 2 PL_H positions, as 64-bit indices in scratch, and their
+    // 2 PL_H lane masks p < C, in spilled SGPRs, for the stores)
+    uint32_t tc = t, Cc = C;
+    asm volatile("" : "+v"(tc), "+s"(Cc));
+    uint32_t *const d_conf = s_conf + cb;
+#pragma unroll
+    for (uint32_t j = 0; j < PL_ROWS; ++j) {
+        const uint32_t p = tc + PL_THREADS * j;
+        if (p < Cc) {
+            __builtin_nontemporal_store(v[j], &d_conf[p]);
+            (j < 32 ? sc0 : sc1) |= (uint32_t)((v[j] & sm1) != 0u) << (j & 31u);
+        }
+    }
+    pl_pick_field(pl_lds, req + cb, C, o, v);
+    uint32_t tr = t, Cr = C;
+    asm volatile("" : "+v"(tr), "+s"(Cr));
+    uint32_t *const d_req = s_req + cb, *const d_idx = s_idx + cb;
+#pragma unroll
+    for (uint32_t j = 0; j < PL_ROWS; ++j) {
+        const uint32_t p = tr + PL_THREADS * j;
+        if (p < Cr) {
+            uint32_t r = v[j];
+            const bool c = ((j < 32 ? cy0 : cy1) >> (j & 31u)) & 1u;
+            const bool x = (r & ~sm0) != 0u || (((j < 32 ? sc0 : sc1) >> (j & 31u)) & 1u);
+            if (c) r = FP_REASON_CYCLE;
+            else if (summ && x) r = FP_REASON_NOFIT;
+            __builtin_nontemporal_store(r, &d_req[p]);
+            if (c || (summ && x)) d_idx[p] |= CYC;
+        }
+    }
+}
+#else
+// Round 3's form: per half of a thread's positions (PL_H indices in registers) the scenario's (req, conf)
+// pairs, and level before them, stream through LDS; both are read once per half.
 constexpr uint32_t PL_CHUNK = 18 * 1024;  // (req, conf) pairs: 144 KB of LDS
+constexpr size_t PL_LDS_BYTES = (size_t)PL_CHUNK * 8;
 __global__ __launch_bounds__(1024) void k_payload_lds(uint32_t C, const uint32_t *__restrict__ order,
                                                       const uint32_t *__restrict__ req,
                                                       const uint32_t *__restrict__ conf,
@@ -1621,6 +1748,7 @@ __global__ __launch_bounds__(1024) void k_payload_lds(uint32_t C, const uint32_t
         }
     }
 }
+#endif  // FPP_PAYLOAD_BY_FIELD
 
 // assign/reason from FFD (sorted) order back to container order, per scenario and per
 // range of container indices held in LDS: every read and write is coalesced.  The
@@ -1654,6 +1782,7 @@ __global__ __launch_bounds__(1024) void k_unsort(uint32_t C, uint32_t H, uint32_
             const uint32_t p = p0 + u * blockDim.x;
             j[u] = p < C ? __builtin_nontemporal_load(&order[cb + p]) : 0xFFFFFFFFu;
             av[u] = p < C ? __builtin_nontemporal_load(&asg_s[cb + p]) : 0u;
+            // (loaded only where av is FP_NONE, after av has arrived: no gain by the rule)
             rv[u] = p < C ? __builtin_nontemporal_load(&rsn_s[cb + p]) : 0;
         }
 #pragma unroll
@@ -2081,7 +2210,7 @@ int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_
     if (ready && C && C <= PL_MAX_C && pl_mode != 0) {
         // k_scen_sort wrote order, cpu, mem and the position words; req / conf / CYCLE bits
         // through LDS, one workgroup per scenario
-        const size_t pl = (size_t)PL_CHUNK * 8;
+        const size_t pl = PL_LDS_BYTES;
         // (a one-sweep variant writing each position in the chunk pass that holds its container
         // -- partial lines per pass -- ran 3.6 ms slower per config-4 step, in a sweep whose inputs
         // were not yet synchronised with the generator: r03k_payload_ab.jsonl; dropped)
