@@ -42,6 +42,9 @@ EXPLAIN_HIST_MIXED, EXPLAIN_HIST_FITS, EXPLAIN_HIST_SELECTED, EXPLAIN_HIST_WORDS
 DRAIN_EVICTED, DRAIN_STRANDED, DRAIN_STRANDED_CPU, DRAIN_STRANDED_MEM = 0, 1, 2, 3
 DRAIN_TARGETS, DRAIN_FIRST_STRANDED, DRAIN_NODES, DRAIN_WORDS = 4, 5, 6, 8
 DRAIN_FIELDS = ("evicted", "stranded", "stranded_cpu", "stranded_mem", "targets", "first_stranded", "nodes")
+# the drain sweep under the policy (SPEC.md 2.15): the word indices of a candidate's policy row, and their names
+DRAIN_STRANDED_SKEW, DRAIN_RELAXED, DRAIN_SKEW_BEFORE, DRAIN_SKEW_AFTER, DRAIN_POLICY_WORDS = 0, 1, 2, 3, 4
+DRAIN_POLICY_FIELDS = ("stranded_skew", "relaxed", "skew_before", "skew_after")
 # scale-out sweep (SPEC.md 2.12): the word indices of a candidate's summary row, their names in order, and the
 # most new servers a candidate may open
 GROW_PENDING, GROW_PLACED, GROW_OPENED, GROW_UNPLACEABLE, GROW_CAPPED = 0, 1, 2, 3, 4
@@ -159,6 +162,13 @@ SIGNATURES = {
                                   ct.c_uint32, ct.c_uint32, u32p, u32p, u8p, u32p]),
     "fp_dev_drain_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, vp, ct.c_uint32,
                                       ct.c_uint32, ct.c_uint32, vp, vp, vp, vp]),
+    "fp_drain_sweep_policy": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, u32p, ct.c_uint32,
+                                         ct.c_uint32, ct.c_uint32, u32p, u32p, ct.c_uint32, u32p, ct.c_uint32, u32p,
+                                         u8p, u8p, u32p, u32p]),
+    # relax_mask (u32p) is a host array in the device entry too
+    "fp_dev_drain_sweep_policy": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, vp, ct.c_uint32,
+                                             ct.c_uint32, ct.c_uint32, vp, vp, ct.c_uint32, u32p, ct.c_uint32, vp,
+                                             vp, vp, vp, vp]),
     "fp_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), u8p, ct.c_uint32, ct.c_uint32, u32p, u32p, u32p, u32p,
                                  ct.c_uint32, u32p, u32p]),
     "fp_dev_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), vp, ct.c_uint32, ct.c_uint32, vp, vp, vp, vp,

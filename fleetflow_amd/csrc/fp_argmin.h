@@ -1,6 +1,6 @@
 // fp_argmin.h -- the block argmin over 64-bit placement keys that the scored placer (fp_policy.hip,
-// SPEC.md 2.6) and the drain sweep (fp_drain.hip, SPEC.md 2.11) share: the 2.6 key layout and the
-// cross-lane helpers.  Device code only; every function is forced inline.
+// SPEC.md 2.6) and the drain sweep (fp_drain.hip, SPEC.md 2.11 and 2.15) share: the key layouts of 2.6, 2.7
+// and 2.8 and the cross-lane helpers.  Device code only; every function is forced inline.
 // This header is where sharing between k_policy and k_drain_sweep stops: moving any more of them into shared
 // functions (the strategy's primary score, the block min with its slots and parity, the winner's update)
 // changes the code of k_policy's instantiations, by reordered opcodes up to hundreds of instructions
@@ -13,6 +13,15 @@ namespace fpd {
 
 constexpr uint64_t KEY_NONE = ~0ull;    // an infeasible node
 constexpr uint32_t KEY_NODE_BITS = 26;  // key = pref_miss << 58 | primary << 26 | node
+
+// SPEC.md 2.8, the variants with a fallback chain: key = hop << 61 | pref_miss << 55 | primary << 23 | node
+constexpr uint32_t KEY_NODE_BITS_FB = 23;
+constexpr uint32_t KEY_HOP_SHIFT = 61;
+// SPEC.md 2.7: a node that fits by 2.3 and fails the skew test.  Real keys are below 0x84 << 56
+// (pref_miss <= 32; with a fallback chain hop <= 4 as well: below 0x91 << 56), so a block minimum of
+// KEY_SKEW says SKEW and one of KEY_NONE says NOFIT
+constexpr uint64_t KEY_SKEW = KEY_NONE - 1;
+constexpr uint32_t DOM_BITS = 6;  // FP_SPREAD_MAX_DOMAINS = 64: a domain id is one lane of a wave
 
 __device__ __forceinline__ uint64_t min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
@@ -46,6 +55,20 @@ __device__ __forceinline__ uint64_t lane64(uint64_t v, int l) {
 __device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
     v = row_min64(v);
     return min64(min64(lane64(v, 0), lane64(v, 16)), min64(lane64(v, 32), lane64(v, 48)));
+}
+
+// the same min over 32-bit values (the domain counts of SPEC.md 2.7), uniform
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t min32(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
+    v = min32(v, dpp32<0xB1>(v));
+    v = min32(v, dpp32<0x4E>(v));
+    v = min32(v, dpp32<0x141>(v));
+    v = min32(v, dpp32<0x140>(v));
+    return min32(min32(bcast(v, 0), bcast(v, 16)), min32(bcast(v, 32), bcast(v, 48)));
 }
 
 }  // namespace fpd

@@ -920,6 +920,66 @@ extern "C" int fp_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes
     return copy_back_all(c, rows, n);
 }
 
+// the drain sweep under the policy (SPEC.md 2.15, fp_drain.hip).  relax_mask is a host array in both entries
+extern "C" int fp_dev_drain_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                         const uint32_t *group, uint32_t n_cand, uint32_t strategy,
+                                         uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                                         uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                         uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
+                                         uint32_t *summary_out, uint32_t *policy_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_drain_policy pol;
+    pol.domain = domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
+    pol.hops_out = hops_out; pol.policy_out = policy_out;
+    return fp_dev_done(c, fp_dev_drain_sweep_impl(c, cs, ns, assign, group, n_cand, strategy, preferred_labels,
+                                                  node_count, assign_out, reason_out, summary_out, pol));
+}
+
+extern "C" int fp_drain_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                     const uint32_t *group, uint32_t n_cand, uint32_t strategy,
+                                     uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                                     uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                     uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
+                                     uint32_t *summary_out, uint32_t *policy_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const size_t C = cs->n, N = ns->n;
+    if (N > FP_POLICY_MAX_NODES || n_cand > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
+    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out || !reason_out))
+        return FP_EINVAL;
+    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !group))
+        return FP_EINVAL;
+    if (n_cand && !summary_out) return FP_EINVAL;
+    if (C && assign_out == assign) return FP_EINVAL;
+    for (size_t n = 0; n < N; ++n)
+        if (group[n] >= n_cand && group[n] != FP_NONE) return FP_EINVAL;
+    for (size_t i = 0; i < C; ++i)
+        if (assign[i] >= N && assign[i] != FP_NONE) return FP_EINVAL;
+    const bool sp = domain && max_skew != 0u;  // otherwise domain is not read
+    for (size_t n = 0; sp && n < N; ++n)
+        if (domain[n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
+    if (C == 0 && n_cand == 0) return FP_OK;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_drain_dev d;
+    fp_drain_policy_dev dp;
+    const int n = fp_drain_policy_rows(cs, ns, assign, group, n_cand, node_count, sp ? domain : nullptr, assign_out,
+                                       reason_out, hops_out, summary_out, policy_out, &d, &dp, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    fp_drain_policy pol;
+    pol.domain = dp.domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
+    pol.hops_out = dp.hops_out; pol.policy_out = dp.policy_out;
+    if (int rc = fp_dev_drain_sweep_impl(c, &d.cs, &d.ns, d.assign, d.group, n_cand, strategy, preferred_labels,
+                                         d.node_count, d.assign_out, d.reason_out, d.summary, pol))
+        return rc;
+    return copy_back_all(c, rows, n);
+}
+
 // scale-out sweep (SPEC.md 2.12, fp_grow.hip)
 extern "C" int fp_dev_grow_sweep(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
                                  uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,

@@ -175,10 +175,22 @@ int fp_dev_place_batch_policy_impl(fp_ctx *c, const fp_batch *b, const fp_policy
 
 // drain what-if sweep (fp_drain.hip, SPEC.md 2.11); every pointer is device memory.  group and assign values
 // out of range are found on the device (FP_EINVAL in the context's error word, nothing written)
+// The sweep under the policy (SPEC.md 2.15): domain [N] device memory, relax_mask [n_hops] HOST memory (read
+// during the call, like the scalars); hops_out [C] and policy_out [n_cand][FP_DRAIN_POLICY_WORDS] device
+// memory, nullable.  All null / zero (the default) is 2.11.  n_hops above FP_FALLBACK_MAX_HOPS is FP_EINVAL at
+// once; a domain id of 64 or more under max_skew != 0 is found on the device with the group and assign values
+struct fp_drain_policy {
+    const uint32_t *domain = nullptr;
+    uint32_t max_skew = 0;
+    const uint32_t *relax_mask = nullptr;
+    uint32_t n_hops = 0;
+    uint8_t *hops_out = nullptr;
+    uint32_t *policy_out = nullptr;
+};
 int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
                             const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred,
                             const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
-                            uint32_t *summary_out);
+                            uint32_t *summary_out, const fp_drain_policy &pol = fp_drain_policy());
 
 // scale-out sweep (fp_grow.hip, SPEC.md 2.12); every pointer is device memory, max_new a host value.  A t_max
 // value above max_new is found on the device (FP_EINVAL in the context's error word, nothing written)

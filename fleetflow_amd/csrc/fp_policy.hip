@@ -86,14 +86,13 @@ using fpd::bcast;
 using fpd::min64;
 using fpd::row_min64;
 using fpd::wave_min64;
-// SPEC.md 2.8, the FB variants: key = hop << 61 | pref_miss << 55 | primary << 23 | node
-constexpr uint32_t KEY_NODE_BITS_FB = 23;
-constexpr uint32_t KEY_HOP_SHIFT = 61;
-// SPEC.md 2.7: a node that fits by 2.3 and fails the skew test.  Real keys are below 0x84 << 56
-// (pref_miss <= 32; with a fallback chain hop <= 4 as well: below 0x91 << 56), so a block minimum of
-// KEY_SKEW says SKEW and one of KEY_NONE says NOFIT
-constexpr uint64_t KEY_SKEW = KEY_NONE - 1;
-constexpr uint32_t DOM_BITS = 6;  // FP_SPREAD_MAX_DOMAINS = 64: a domain id is one lane of a wave
+// the 2.7 and 2.8 layouts (fp_argmin.h): the FB variants' key = hop << 61 | pref_miss << 55 | primary << 23 | node
+using fpd::DOM_BITS;
+using fpd::KEY_HOP_SHIFT;
+using fpd::KEY_NODE_BITS_FB;
+using fpd::KEY_SKEW;  // a node that fits by 2.3 and fails the skew test: SKEW, where KEY_NONE says NOFIT
+using fpd::min32;
+using fpd::wave_min32;
 static_assert((1u << DOM_BITS) == FP_SPREAD_MAX_DOMAINS && FP_SPREAD_MAX_DOMAINS == 64, "one domain per lane");
 static_assert((uint64_t)FP_POLICY_MAX_NODES << DOM_BITS <= (1ull << KEY_NODE_BITS_FB), "node << 6 | domain fits the node field");
 static_assert(FP_FALLBACK_MAX_HOPS == 4 && FP_FALLBACK_MAX_HOPS < (1u << (64 - KEY_HOP_SHIFT)), "the hop fits its field");
@@ -176,20 +175,6 @@ struct PolicyArgs {
     uint32_t *quota_used;                         // [S][3] in/out or null (null starts at zero)
     uint8_t *quota_why;                           // [S][C] or null: the mask of the blocking dimensions
 };
-
-// the min of fp_argmin.h over 32-bit values (the domain counts of SPEC.md 2.7)
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t min32(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
-    v = min32(v, dpp32<0xB1>(v));
-    v = min32(v, dpp32<0x4E>(v));
-    v = min32(v, dpp32<0x141>(v));
-    v = min32(v, dpp32<0x140>(v));
-    return min32(min32(bcast(v, 0), bcast(v, 16)), min32(bcast(v, 32), bcast(v, 48)));
-}
 
 // SP: the hard topology spread of SPEC.md 2.7 (a.domain and a.max_skew given).  SP = false is 2.6 and
 // compiles to what it did before the constraint existed.

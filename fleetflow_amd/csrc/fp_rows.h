@@ -142,6 +142,25 @@ static inline int fp_drain_rows(const fp_containers *cs, const fp_nodes *ns, con
     return n;
 }
 
+// fp_drain_sweep_policy (SPEC.md 2.15): fp_drain_sweep's rows, then the domains (absent without a constraint)
+// and the two further results the caller may ask for.  relax_mask stays on the host
+struct fp_drain_policy_dev {
+    const uint32_t *domain;
+    uint8_t *hops_out;
+    uint32_t *policy_out;
+};
+static inline int fp_drain_policy_rows(const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                       const uint32_t *group, uint32_t n_cand, const uint32_t *node_count,
+                                       const uint32_t *domain, uint32_t *assign_out, uint8_t *reason_out,
+                                       uint8_t *hops_out, uint32_t *summary_out, uint32_t *policy_out, fp_drain_dev *d,
+                                       fp_drain_policy_dev *dp, fp_row *r) {
+    int n = fp_drain_rows(cs, ns, assign, group, n_cand, node_count, assign_out, reason_out, summary_out, d, r);
+    r[n++] = fp_row_in(domain, (size_t)ns->n, &dp->domain);
+    r[n++] = fp_row_opt(hops_out, (size_t)cs->n, &dp->hops_out);
+    r[n++] = fp_row_opt(policy_out, (size_t)n_cand * FP_DRAIN_POLICY_WORDS, &dp->policy_out);
+    return n;
+}
+
 // fp_grow_sweep: the requests, the reasons (absent without a mask), the templates; then the two results
 struct fp_grow_dev {
     fp_containers cs;

@@ -596,17 +596,28 @@ class DrainCandidate:
     stranded_cpu_m: int = 0                # what the stranded services ask for in sum
     stranded_mem_mib: int = 0
     targets: int = 0                       # distinct servers that receive a service
+    # under the policy (SPEC.md 2.15, drain_stage(under_policy=True)); unset otherwise
+    relaxed: dict[str, list[str]] = field(default_factory=dict)   # moved service -> label keys given up (Plan.relaxed)
+    stranded_reason: dict[str, str] = field(default_factory=dict)  # stranded service -> "NOFIT" / "SKEW"
+    skew_before: int | None = None         # max - min of the services per eligible domain without the candidate
+    skew_after: int | None = None          # the same after its moves
 
 
 @dataclass
 class DrainReport:
     """``drain_stage``'s answer: one DrainCandidate per candidate, every one computed independently from the
-    same live state, under the strategy and preferred labels named here."""
+    same live state, under the strategy and preferred labels named here, and with ``under_policy`` under the
+    spread constraint and the fallback chain named here."""
     stage: str
     by: str | None = None                  # the topology key the candidates are the values of; None = servers
     strategy: str | None = None
     preferred: list[str] = field(default_factory=list)
     candidates: list[DrainCandidate] = field(default_factory=list)
+    # the guarantees the moves were held to (SPEC.md 2.15); unset without under_policy
+    spread_topology_key: str | None = None
+    spread_max_skew: int | None = None
+    fallback_relax_order: list[str] = field(default_factory=list)
+    fallback_max_hops: int | None = None
 
 
 def live_tables(flow: Flow, stage_name: str, plan: Plan, policy: PlacementPolicy | None = None):
@@ -642,7 +653,8 @@ def live_tables(flow: Flow, stage_name: str, plan: Plan, policy: PlacementPolicy
 
 
 def drain_stage(flow: Flow, stage_name: str, plan: Plan, by: str | None = None, servers: list[str] | None = None,
-                planner: Planner | None = None, policy: PlacementPolicy | None = None) -> DrainReport:
+                planner: Planner | None = None, policy: PlacementPolicy | None = None,
+                under_policy: bool = False) -> DrainReport:
     """"Can this server, or this whole zone, be taken out?" for a stage that runs as ``plan`` says (SPEC.md
     2.11; the `drain` scheduling state of model.rs:435-442): one ``Planner.drain_sweep`` over the live
     tables of ``live_tables``.  The candidates are
@@ -655,12 +667,27 @@ def drain_stage(flow: Flow, stage_name: str, plan: Plan, by: str | None = None, 
 
     Every candidate is computed independently from the same live state: its services are visited in the
     order (cpu desc, mem desc, stage order) and go to the remaining schedulable servers under the strategy
-    and preferred labels of ``policy`` or, without one, of the policy the plan was made under.  The policy's
-    spread constraint, fallback chain and quota are not applied to moves."""
+    and preferred labels of ``policy`` or, without one, of the policy the plan was made under.  By default
+    the policy's spread constraint and fallback chain are not applied to moves: a move is a SPEC.md 2.6
+    placement.
+
+    ``under_policy=True`` applies them (SPEC.md 2.15, one ``Planner.drain_sweep_policy`` call): the spread
+    constraint and the chain of ``policy`` or, without one, of the policy the plan was made under.  Each
+    candidate's domain counts leave its own servers out, a domain counts while it keeps a target, and servers
+    without the topology key take no move (``replan_domains``).  A quota has nothing to test: a move releases
+    and retakes the same request.  The candidates then carry ``relaxed``, ``stranded_reason``, ``skew_before``
+    and ``skew_after``, and the report the guarantees it ran under."""
     p = planner or default_planner()
     names, nodes, cont, live, assign, count, strategy, pmask = live_tables(flow, stage_name, plan, policy)
     pol_pref = policy.preferred if policy is not None else list(plan.preferred)
     report = DrainReport(stage_name, None, strategy, pol_pref)
+    pol = None
+    if under_policy:
+        pol = policy if policy is not None else _plan_policy(plan)
+        if pol.spread is not None:
+            report.spread_topology_key, report.spread_max_skew = pol.spread
+        if pol.fallback:
+            report.fallback_relax_order, report.fallback_max_hops = list(pol.fallback_relax_order), pol.fallback_max_hops
     if not nodes:
         return report
     slugs = [nd.slug for nd in nodes]
@@ -686,9 +713,22 @@ def drain_stage(flow: Flow, stage_name: str, plan: Plan, by: str | None = None, 
         group = list(range(len(nodes)))
         cand_names = slugs
     n_cand = len(cand_names)
-    out, _, summary = p.drain_sweep(cont, live, assign, group, n_cand, strategy if strategy is not None else 0, pmask,
-                                    count)
-    from ._lib import DRAIN_EVICTED, DRAIN_STRANDED_CPU, DRAIN_STRANDED_MEM, DRAIN_TARGETS
+    from ._lib import (DRAIN_EVICTED, DRAIN_SKEW_AFTER, DRAIN_SKEW_BEFORE, DRAIN_STRANDED_CPU, DRAIN_STRANDED_MEM,
+                       DRAIN_TARGETS, REASON_SKEW)
+    reason = hops = rows = None
+    if pol is None:
+        out, _, summary = p.drain_sweep(cont, live, assign, group, n_cand, strategy if strategy is not None else 0,
+                                        pmask, count)
+    else:
+        domain, max_skew = None, 0
+        if pol.spread is not None:
+            domain, has_key = replan_domains(nodes, pol.spread[0])
+            max_skew = pol.spread[1]
+            live = (*live[:4], [s if k else 0 for s, k in zip(live[4], has_key)])
+        relax = [_stage_labels(names, flow, nodes, pol_pref).key_mask(k) for k in pol.fallback]
+        out, reason, summary, hops, rows = p.drain_sweep_policy(
+            cont, live, assign, group, n_cand, strategy if strategy is not None else 0, pmask, count, domain=domain,
+            max_skew=max_skew, relax_mask=relax)
     evictees: list[list[int]] = [[] for _ in range(n_cand)]
     for v, n in enumerate(assign):
         if n != NONE and group[n] != NONE:
@@ -698,9 +738,18 @@ def drain_stage(flow: Flow, stage_name: str, plan: Plan, by: str | None = None, 
         moves = [(names[v], slugs[assign[v]], slugs[int(out[v])]) for v in evictees[k] if int(out[v]) != NONE]
         stranded = [names[v] for v in evictees[k] if int(out[v]) == NONE]
         row = [int(x) for x in summary[k]]
-        report.candidates.append(DrainCandidate(name, [s for s, g in zip(slugs, group) if g == k], moves, stranded,
-                                                row[DRAIN_EVICTED], row[DRAIN_STRANDED_CPU], row[DRAIN_STRANDED_MEM],
-                                                row[DRAIN_TARGETS]))
+        cand = DrainCandidate(name, [s for s, g in zip(slugs, group) if g == k], moves, stranded,
+                              row[DRAIN_EVICTED], row[DRAIN_STRANDED_CPU], row[DRAIN_STRANDED_MEM], row[DRAIN_TARGETS])
+        if pol is not None:
+            for v in evictees[k]:
+                if int(out[v]) == NONE:
+                    cand.stranded_reason[names[v]] = "SKEW" if int(reason[v]) == REASON_SKEW else "NOFIT"
+                elif int(hops[v]):
+                    required = {lab.split("=", 1)[0] for lab in flow.services.get(names[v], Service()).labels}
+                    cand.relaxed[names[v]] = [key for key in pol.fallback[:int(hops[v])] if key in required]
+            if pol.spread is not None:
+                cand.skew_before, cand.skew_after = int(rows[k][DRAIN_SKEW_BEFORE]), int(rows[k][DRAIN_SKEW_AFTER])
+        report.candidates.append(cand)
     return report
 
 

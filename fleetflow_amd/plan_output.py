@@ -13,7 +13,9 @@ absent without a quota.
 
 ``format_drain_report`` prints a drain sweep (SPEC.md 2.11, ``flow.drain_stage``), one block per candidate,
 and ``drain_report_to_json`` / ``drain_report_from_json`` carry it as
-``{stage, by, placement: {strategy, preferred}, candidates: [{name, servers, moves, stranded, ...}]}``.
+``{stage, by, placement: {strategy, preferred}, candidates: [{name, servers, moves, stranded, ...}]}``; a sweep
+under the policy (SPEC.md 2.15) adds ``placement.spread`` / ``placement.fallback`` and per candidate ``relaxed``,
+``stranded_reason``, ``skew_before`` and ``skew_after``, each only when set.
 
 ``format_grow_report`` prints a scale-out sweep (SPEC.md 2.12, ``flow.grow_stage``), one line per template with
 the services of each new server indented under it where the candidate was detailed, and ``grow_report_to_json``
@@ -95,19 +97,42 @@ def plan_from_json(text: str) -> Plan:
 
 def format_drain_report(report: DrainReport) -> str:
     """One line per candidate, ``drain <name>: <m> services move to <t> servers, <s> stranded``, with the
-    moves (``service: from -> to``) and the stranded services indented under it, in visiting order."""
+    moves (``service: from -> to``) and the stranded services indented under it, in visiting order.  What a
+    sweep under the policy adds (SPEC.md 2.15) is printed only where it is set: ``(relaxed: class)`` behind a
+    move, ``stranded (SKEW)``, and a ``spread:`` line for a candidate whose remaining servers are outside the
+    constraint before anything moves."""
     lines = []
     for c in report.candidates:
         lines.append(f"drain {c.name}: {len(c.moves)} services move to {c.targets} servers, {len(c.stranded)} stranded")
-        lines += [f"  {svc}: {src} -> {dst}" for svc, src, dst in c.moves]
-        lines += [f"  {svc}: stranded" for svc in c.stranded]
+        lines += [f"  {svc}: {src} -> {dst}" + (f" (relaxed: {', '.join(c.relaxed[svc])})" if c.relaxed.get(svc) else "")
+                  for svc, src, dst in c.moves]
+        lines += [f"  {svc}: stranded" + (f" ({c.stranded_reason[svc]})" if svc in c.stranded_reason else "")
+                  for svc in c.stranded]
+        if (c.skew_before is not None and report.spread_max_skew is not None
+                and c.skew_before > report.spread_max_skew):
+            lines.append(f"  spread: skew {c.skew_before} over {report.spread_topology_key} exceeds max_skew "
+                         f"{report.spread_max_skew} (services that stay are not evicted)")
     return "\n".join(lines)
 
 
+_DRAIN_POLICY_FIELDS = ("relaxed", "stranded_reason", "skew_before", "skew_after")
+
+
 def drain_report_to_json(report: DrainReport, indent: int | None = None) -> str:
+    cands = []
+    for c in report.candidates:
+        row = asdict(c)
+        for key in _DRAIN_POLICY_FIELDS:  # SPEC.md 2.15: only when set
+            if not row[key] and row[key] != 0:
+                del row[key]
+        cands.append(row)
     d = {"stage": report.stage, "by": report.by,
          "placement": {"strategy": report.strategy, "preferred": report.preferred},
-         "candidates": [asdict(c) for c in report.candidates]}
+         "candidates": cands}
+    if report.spread_topology_key is not None:
+        d["placement"]["spread"] = {"topology_key": report.spread_topology_key, "max_skew": report.spread_max_skew}
+    if report.fallback_relax_order:
+        d["placement"]["fallback"] = {"relax_order": report.fallback_relax_order, "max_hops": report.fallback_max_hops}
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
@@ -116,8 +141,13 @@ def drain_report_from_json(text: str) -> DrainReport:
     pol = d.get("placement") or {}
     cands = [DrainCandidate(c["name"], list(c["servers"]), [tuple(m) for m in c["moves"]], list(c["stranded"]),
                             c.get("evicted", 0), c.get("stranded_cpu_m", 0), c.get("stranded_mem_mib", 0),
-                            c.get("targets", 0)) for c in d.get("candidates") or []]
-    return DrainReport(d["stage"], d.get("by"), pol.get("strategy"), list(pol.get("preferred") or []), cands)
+                            c.get("targets", 0), {k: list(v) for k, v in (c.get("relaxed") or {}).items()},
+                            dict(c.get("stranded_reason") or {}), c.get("skew_before"), c.get("skew_after"))
+             for c in d.get("candidates") or []]
+    return DrainReport(d["stage"], d.get("by"), pol.get("strategy"), list(pol.get("preferred") or []), cands,
+                       (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"),
+                       list((pol.get("fallback") or {}).get("relax_order") or []),
+                       (pol.get("fallback") or {}).get("max_hops"))
 
 
 def format_replan_report(report: Replan) -> str:

@@ -638,6 +638,42 @@ class Planner:
                                      _arg(summary)), "fp_drain_sweep")
         return out, reason, summary
 
+    def drain_sweep_policy(self, cont, nodes, assign, group, n_cand, strategy=0, preferred=0, node_count=None, *,
+                           domain=None, max_skew=0, relax_mask=()):
+        """The drain sweep under the policy (SPEC.md 2.15, fp_drain_sweep_policy): ``drain_sweep`` with every
+        move held to the spread constraint (``domain`` [N] ids below 64 and ``max_skew``; None or 0 = none,
+        ``domain`` is then not read) and the fallback chain (``relax_mask``: per hop the label bits it gives
+        up, at most 4; empty = none).  Each candidate's domain counts leave its own nodes out and a domain is
+        eligible when it has a target.  There is no quota: a move releases and retakes the same request.
+        Returns (assign_out [C], reason [C] with REASON_SKEW beside REASON_NOFIT, summary [n_cand, 8], hops
+        [C], policy_rows [n_cand, 4]); the policy rows' word indices are _lib.DRAIN_STRANDED_SKEW, .."""
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
+        asg, grp = _u32(assign), _u32(group)
+        nc = _u32(node_count) if node_count is not None else None
+        dom = _u32(domain) if domain is not None else None
+        n_cand, strategy, max_skew = int(n_cand), strategy_id(strategy), int(max_skew)
+        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
+        self._need(asg.size == C, "assign must hold C entries")
+        self._need(grp.size == N, "group must hold N entries")
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        self._need(dom is None or dom.size == N, "domain must hold N entries")
+        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
+        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
+        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+        rm = _u32(relax) if relax else None
+        out = np.empty(C, np.uint32)
+        reason = np.empty(C, np.uint8)
+        hops = np.empty(C, np.uint8)
+        summary = np.empty((n_cand, _lib.DRAIN_WORDS), np.uint32)
+        rows = np.empty((n_cand, _lib.DRAIN_POLICY_WORDS), np.uint32)
+        cs, ns = _pair(cont, nodes)
+        check(self._L.fp_drain_sweep_policy(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(grp), n_cand,
+                                            strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(dom), max_skew,
+                                            _arg(rm), len(relax), _arg(out), _arg(reason), _arg(hops), _arg(summary),
+                                            _arg(rows)), "fp_drain_sweep_policy")
+        return out, reason, summary, hops, rows
+
     def drain(self, cont, nodes, assign, drain_mask, strategy=0, preferred=0, node_count=None):
         """Evacuate the nodes of ``drain_mask`` ([N], non-zero = drained) from a live plan: one drain_sweep
         with a single candidate, and its moves applied on the host to copies of the node table and of the
@@ -758,6 +794,48 @@ class Planner:
             self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(group_t), n_cand, strategy,
             int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(assign_out_t), _arg(reason_t), _arg(summary_t)),
             "fp_dev_drain_sweep"))
+
+    def dev_drain_sweep_policy(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t,
+                               strategy=0, preferred=0, count_t=None, *, domain_t=None, max_skew=0, relax_mask=(),
+                               hops_t=None, policy_t=None):
+        """fp_dev_drain_sweep_policy on device tensors: ``dev_drain_sweep``'s arguments, then ``domain_t`` [N] or
+        None, ``max_skew``, ``relax_mask`` (host values, at most 4: the one array of a dev_* call that is not a
+        tensor) and the optional results ``hops_t`` [C] uint8 and ``policy_t`` [n_cand * 4].  A group, assign or
+        domain value out of range is found on the device: nothing is written and sync() raises FP_EINVAL."""
+        C, N, n_cand, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_cand), strategy_id(strategy)
+        max_skew = int(max_skew)
+        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
+        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
+                   "every container tensor must hold C 32-bit entries")
+        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
+                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
+                   "every node tensor must hold N entries (schedulable N bytes)")
+        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
+        self._need(group_t.numel() == N and group_t.element_size() == 4, "group_t must hold N 32-bit entries")
+        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
+                   "count_t must hold N 32-bit entries")
+        self._need(domain_t is None or (domain_t.numel() == N and domain_t.element_size() == 4),
+                   "domain_t must hold N 32-bit entries")
+        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
+        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
+        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+        self._need(assign_out_t.numel() == C and assign_out_t.element_size() == 4,
+                   "assign_out_t must hold C 32-bit entries")
+        self._need(reason_t.numel() == C and reason_t.element_size() == 1, "reason_t must hold C bytes")
+        self._need(summary_t.numel() == n_cand * _lib.DRAIN_WORDS and summary_t.element_size() == 4,
+                   "summary_t must hold n_cand * 8 32-bit entries")
+        self._need(hops_t is None or (hops_t.numel() == C and hops_t.element_size() == 1), "hops_t must hold C bytes")
+        self._need(policy_t is None or (policy_t.numel() == n_cand * _lib.DRAIN_POLICY_WORDS
+                                        and policy_t.element_size() == 4),
+                   "policy_t must hold n_cand * 4 32-bit entries")
+        rm = _u32(relax) if relax else None  # read during the call
+        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
+        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
+        self._dev(lambda: check(self._L.fp_dev_drain_sweep_policy(
+            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(group_t), n_cand, strategy,
+            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(domain_t), max_skew, _arg(rm), len(relax),
+            _arg(assign_out_t), _arg(reason_t), _arg(hops_t), _arg(summary_t), _arg(policy_t)),
+            "fp_dev_drain_sweep_policy"))
 
     def dev_explain(self, db: "DevBatch", rows_t, sel_t=None, ignore_labels=0, scenario=0):
         """fp_dev_explain on one scenario of ``db`` (offset pointers, as dev_feasibility): ``rows_t``

@@ -29,6 +29,10 @@
  *   fp_drain_sweep    <- new: evacuate each server, or each topology domain, from a live plan: the `drain`
  *                        scheduling state, under which existing placements leave as well (`cordon` only
  *                        stops new ones)  crates/fleetflow-controlplane/src/model.rs:435-442
+ *   fp_drain_sweep_policy <- new: the same sweep with every move held to the policy's SpreadConstraint and
+ *                        FallbackPolicy, on counts that leave the candidate's own servers out (model.rs:47-63;
+ *                        the ResourceQuota of model.rs:38-45 has nothing to test: a move releases and retakes
+ *                        the same request)
  *   fp_grow_sweep     <- new: the new servers of each template (a plan string's size,
  *                        crates/fleetflow-cloud-sakura/src/provider.rs:15-30, with the ServerLabels /
  *                        ServerCapacity a new server would carry, crates/fleetflow-controlplane/src/model.rs:399-419)
@@ -45,7 +49,8 @@
  *   - All buffers are caller-owned; no allocation crosses the ABI.
  *   - fp_* take HOST pointers and are synchronous: on error nothing is written.
  *   - fp_dev_* take DEVICE (HBM) pointers of the context's device and are
- *     asynchronous on the context's stream.  Kernel-side errors of fp_dev_* calls
+ *     asynchronous on the context's stream.  The one deviation: relax_mask of
+ *     fp_dev_drain_sweep_policy is a HOST array, read during the call like a scalar.  Kernel-side errors of fp_dev_* calls
  *     (FP_ECORRUPT input, FP_EDEVICE from the placement pipeline's deadlock guard) are
  *     sticky: the first one raised is kept until fp_ctx_sync() reports it and clears it.
  *     A host-pointer call reports only the errors of its own kernels (it has its own error
@@ -372,12 +377,40 @@ int fp_explain_batch(fp_ctx *ctx, const fp_batch *b, uint32_t reason_mask, const
  * (zeros).  nodes->n or n_cand above FP_POLICY_MAX_NODES is FP_EOVERFLOW; a strategy above
  * FP_STRATEGY_FILL_LOWEST, assign_out == assign, a group[n] that is neither < n_cand nor FP_NONE and an
  * assign[c] that is neither < nodes->n nor FP_NONE are FP_EINVAL; on any error nothing is written.  The
- * policy's spread constraint, fallback chain and quota are not applied to moves. */
+ * policy's spread constraint and fallback chain are not applied to moves here: fp_drain_sweep_policy applies them. */
 enum { FP_DRAIN_EVICTED = 0, FP_DRAIN_STRANDED = 1, FP_DRAIN_STRANDED_CPU = 2, FP_DRAIN_STRANDED_MEM = 3,
        FP_DRAIN_TARGETS = 4, FP_DRAIN_FIRST_STRANDED = 5, FP_DRAIN_NODES = 6, FP_DRAIN_WORDS = 8 };
 int fp_drain_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
                    const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
                    const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out, uint32_t *summary_out);
+/* The drain sweep under the policy (SPEC.md 2.15): fp_drain_sweep with every move held to the tenant's spread
+ * constraint (domain[n] < FP_SPREAD_MAX_DOMAINS, max_skew; fp_place_policy_spread's meanings) and fallback chain
+ * (relax_mask[n_hops], n_hops <= FP_FALLBACK_MAX_HOPS; fp_place_policy_fallback's).  There is no quota input: an
+ * evictee is already charged to its tenant and a move releases and retakes the same request, so admission has
+ * nothing to test.  Candidate k is exactly one fp_place_policy_fallback call over its evictees on the base table
+ * with schedulable[n] &= group[n] != k and node_count[n] = 0 where group[n] == k: its domain counts leave its own
+ * nodes out (what runs there is leaving; cordoned nodes outside it count), a domain is eligible when it has a
+ * target, so a drained zone never holds the minimum down, and each evictee goes to the feasible target with the
+ * smallest (hop, key) that passes the skew test on the candidate's running counts.  A stranded evictee is
+ * FP_REASON_NOFIT when no target fits even under the last hop's requirement and FP_REASON_SKEW when one fits and
+ * none passes; the summary row's STRANDED words and FIRST_STRANDED cover both.  hops_out (nullable) [c->n]: the
+ * hop of a moved evictee, 0 for every other container.  policy_out (nullable) holds one row of
+ * FP_DRAIN_POLICY_WORDS u32 per candidate:
+ *   STRANDED_SKEW  evictees stranded on SKEW          RELAXED  evictees moved at a hop >= 1
+ *   SKEW_BEFORE, SKEW_AFTER  max - min of the domain counts over the candidate's eligible domains, on its base
+ *   counts and after its moves; both 0 when no domain is eligible or max_skew == 0.
+ * A candidate without evictees gets a row of zeros.  domain == NULL or max_skew == 0: no constraint, domain is
+ * not read; relax_mask == NULL or n_hops == 0: no chain; with neither the call is fp_drain_sweep bit for bit,
+ * hops_out all 0 and the policy_out rows all 0.  Errors are fp_drain_sweep's, and n_hops above
+ * FP_FALLBACK_MAX_HOPS or (with max_skew != 0) any domain[n] >= FP_SPREAD_MAX_DOMAINS, the candidate's nodes
+ * included, are FP_EINVAL; on any error nothing is written. */
+enum { FP_DRAIN_STRANDED_SKEW, FP_DRAIN_RELAXED, FP_DRAIN_SKEW_BEFORE, FP_DRAIN_SKEW_AFTER, /* words 0 to 3 */
+       FP_DRAIN_POLICY_WORDS /* 4 */ };
+int fp_drain_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                          const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
+                          const uint32_t *node_count, const uint32_t *domain, uint32_t max_skew,
+                          const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out,
+                          uint8_t *hops_out, uint32_t *summary_out, uint32_t *policy_out);
 /* Scale-out sweep (SPEC.md 2.12): "what do I have to add?", asked of every server template at once.  The pending
  * containers are those whose reason's bit is set in reason_mask (fp_explain_batch's convention; reason_mask == 0
  * selects every container and reason is not read and may be NULL).  Candidate k is a template: a new server has
@@ -539,6 +572,16 @@ int fp_dev_drain_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *node
                        const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
                        const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
                        uint32_t *summary_out);
+/* As fp_drain_sweep_policy on device pointers, with ONE exception to "fp_dev_* take device pointers":
+ * relax_mask is a HOST array of n_hops words, read during the call like the scalars beside it (the cumulative
+ * masks go to the kernel by value); n_hops above FP_FALLBACK_MAX_HOPS is returned directly.  A group, assign or
+ * domain value out of range is found on the device before any store: nothing is written, hops_out and policy_out
+ * included, and fp_ctx_sync() reports FP_EINVAL.  Workspace as fp_dev_drain_sweep. */
+int fp_dev_drain_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                              const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
+                              const uint32_t *node_count, const uint32_t *domain, uint32_t max_skew,
+                              const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
+                              uint8_t *reason_out, uint8_t *hops_out, uint32_t *summary_out, uint32_t *policy_out);
 /* As fp_grow_sweep on device pointers (max_new stays a host value: the kernel's geometry follows it, nothing is
  * read back).  A t_max[k] > max_new is found on the device before any store: nothing is written and fp_ctx_sync()
  * reports FP_EINVAL.  The call takes 28 bytes per container plus the sort's scratch from the context's workspace. */

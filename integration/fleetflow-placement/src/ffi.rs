@@ -56,6 +56,12 @@ pub const FP_DRAIN_TARGETS: usize = 4;
 pub const FP_DRAIN_FIRST_STRANDED: usize = 5;
 pub const FP_DRAIN_NODES: usize = 6;
 pub const FP_DRAIN_WORDS: usize = 8;
+// the drain sweep under the policy (SPEC.md 2.15): the word indices of a candidate's policy row
+pub const FP_DRAIN_STRANDED_SKEW: usize = 0;
+pub const FP_DRAIN_RELAXED: usize = 1;
+pub const FP_DRAIN_SKEW_BEFORE: usize = 2;
+pub const FP_DRAIN_SKEW_AFTER: usize = 3;
+pub const FP_DRAIN_POLICY_WORDS: usize = 4;
 // scale-out sweep (SPEC.md 2.12): the word indices of a candidate's summary row, and the most new servers
 pub const FP_GROW_PENDING: usize = 0;
 pub const FP_GROW_PLACED: usize = 1;
@@ -243,6 +249,11 @@ unsafe extern "C" {
                           group: *const u32, n_cand: u32, strategy: u32, preferred_labels: u32,
                           node_count: *const u32, assign_out: *mut u32, reason_out: *mut u8,
                           summary_out: *mut u32) -> c_int;
+    pub fn fp_drain_sweep_policy(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes,
+                                 assign: *const u32, group: *const u32, n_cand: u32, strategy: u32,
+                                 preferred_labels: u32, node_count: *const u32, domain: *const u32, max_skew: u32,
+                                 relax_mask: *const u32, n_hops: u32, assign_out: *mut u32, reason_out: *mut u8,
+                                 hops_out: *mut u8, summary_out: *mut u32, policy_out: *mut u32) -> c_int;
     pub fn fp_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32, n_cand: u32,
                          t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32, t_max: *const u32,
                          max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
@@ -300,6 +311,13 @@ unsafe extern "C" {
                               group: *const u32, n_cand: u32, strategy: u32, preferred_labels: u32,
                               node_count: *const u32, assign_out: *mut u32, reason_out: *mut u8,
                               summary_out: *mut u32) -> c_int;
+    // relax_mask is a HOST array here too: the one exception to "fp_dev_* take device pointers"
+    pub fn fp_dev_drain_sweep_policy(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes,
+                                     assign: *const u32, group: *const u32, n_cand: u32, strategy: u32,
+                                     preferred_labels: u32, node_count: *const u32, domain: *const u32,
+                                     max_skew: u32, relax_mask: *const u32, n_hops: u32, assign_out: *mut u32,
+                                     reason_out: *mut u8, hops_out: *mut u8, summary_out: *mut u32,
+                                     policy_out: *mut u32) -> c_int;
     pub fn fp_dev_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
                              n_cand: u32, t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32,
                              t_max: *const u32, max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;

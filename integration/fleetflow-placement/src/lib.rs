@@ -162,6 +162,46 @@ impl Planner {
         Ok((out, reason, rows))
     }
 
+    /// The drain sweep under the policy (SPEC.md 2.15, fleetplace.h `fp_drain_sweep_policy`): `drain_sweep` with
+    /// every move held to the spread constraint (`domain` ids below `ffi::FP_SPREAD_MAX_DOMAINS` and `max_skew`;
+    /// None or 0 = none) and the fallback chain (`relax_mask`: per hop the label bits it gives up, at most
+    /// `ffi::FP_FALLBACK_MAX_HOPS`; empty = none).  Each candidate's domain counts leave its own nodes out.
+    /// Returns (the new node, the reason and the hop per container, one row of `ffi::FP_DRAIN_WORDS` and one of
+    /// `ffi::FP_DRAIN_POLICY_WORDS` words per candidate).
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn drain_sweep_policy(&mut self, c: &Containers, nodes: &Nodes, assign: &[u32], group: &[u32], n_cand: u32,
+                              strategy: u32, preferred_labels: u32, node_count: Option<&[u32]>,
+                              domain: Option<&[u32]>, max_skew: u32, relax_mask: &[u32])
+                              -> Result<(Vec<u32>, Vec<u8>, Vec<u8>, Vec<[u32; ffi::FP_DRAIN_WORDS]>,
+                                         Vec<[u32; ffi::FP_DRAIN_POLICY_WORDS]>), PlanError> {
+        let (n, nn) = (c.cpu_m.len(), nodes.cpu_free.len());
+        if !c.all_len(n) || !nodes.all_len(nn) || assign.len() != n || group.len() != nn
+            || node_count.map_or(false, |k| k.len() != nn) || domain.map_or(false, |d| d.len() != nn)
+            || relax_mask.len() > ffi::FP_FALLBACK_MAX_HOPS as usize {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        // the sweep reads the node table only: the mutable pointers of fp_nodes are never written through
+        let ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_ptr() as *mut u32,
+                                 mem_free: nodes.mem_free.as_ptr() as *mut u32, labels: nodes.labels.as_ptr(),
+                                 conflict_used: nodes.conflict_used.as_ptr() as *mut u32,
+                                 schedulable: nodes.schedulable.as_ptr() };
+        let (mut out, mut reason, mut hops) = (vec![0u32; n], vec![0u8; n], vec![0u8; n]);
+        let mut rows = vec![[0u32; ffi::FP_DRAIN_WORDS]; n_cand as usize];
+        let mut prows = vec![[0u32; ffi::FP_DRAIN_POLICY_WORDS]; n_cand as usize];
+        check(unsafe {
+            ffi::fp_drain_sweep_policy(self.ctx, &cs, &ns, assign.as_ptr(), group.as_ptr(), n_cand, strategy,
+                                       preferred_labels, node_count.map_or(std::ptr::null(), |k| k.as_ptr()),
+                                       domain.map_or(std::ptr::null(), |d| d.as_ptr()), max_skew,
+                                       if relax_mask.is_empty() { std::ptr::null() } else { relax_mask.as_ptr() },
+                                       relax_mask.len() as u32, out.as_mut_ptr(), reason.as_mut_ptr(),
+                                       hops.as_mut_ptr(), rows.as_mut_ptr() as *mut u32,
+                                       prows.as_mut_ptr() as *mut u32)
+        })?;
+        Ok((out, reason, hops, rows, prows))
+    }
+
     /// Scale-out sweep (SPEC.md 2.12, fleetplace.h `fp_grow_sweep`): the pending containers are those whose
     /// `reason` has its bit set in `reason_mask` (0 = every container, `reason` may be None); candidate k is a
     /// server template (`t_cpu[k]`, `t_mem[k]`, `t_labels[k]`) of which at most `t_max[k]` (None = `max_new`
