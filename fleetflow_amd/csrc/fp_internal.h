@@ -235,6 +235,10 @@ __host__ __device__ inline void fp_thresholds(uint32_t lo, uint32_t hi, uint32_t
 // the FFD-sorted SoA [S][C] the pipeline streams (fp_pipe.hip)
 struct fp_pipe_soa {
     uint32_t *s_cpu, *s_mem, *s_req, *s_conf, *s_idx;
+    // set by the fused sort (fp_place.hip): k_node_summary ran ahead of it (summ: its rows, null without the
+    // screen) and the sort's last phase wrote s_req, s_conf and the skip bits, so fp_pipe_launch runs neither
+    uint32_t *summ = nullptr;
+    bool payload_done = false;
 };
 int fp_pipe_soa_take(fp_ctx *c, size_t SC, fp_pipe_soa *soa);
 // 1 when the position word carries the bucket indices (bits 21-30)
@@ -244,6 +248,12 @@ uint32_t fp_pipe_kpack(const fp_ctx *c, uint32_t C);
 // thr: the pipeline's bucket thresholds in device memory ([FP_BUCKETS] cpu, then mem)
 // rng: [2] the OR of every container cpu / mem value of the batch (the sort kernels wrote it); the
 // pipeline adds the nodes' and runs the packed kernel when the values pack (null: u32 kernels only)
+// the stage-2 screen's summary rows ([S][4] from the workspace into *summ; null without nodes or the screen)
+// and the nodes' share of rng, enqueued on the context's stream
+int fp_pipe_node_summary(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, const fp_batch *b, uint32_t *rng,
+                         uint32_t **summ);
+// the largest C whose payload gather runs through LDS chunks (0: FP_OPT_PAYLOAD_LDS = 0)
+uint32_t fp_pipe_payload_lds_max_c(const fp_ctx *c);
 int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_base, const uint32_t *order,
                    const void *skeys, uint32_t key_bytes, uint32_t mbits, uint64_t cmax, uint64_t mmax,
                    const uint32_t *cval, const uint32_t *mval, const fp_batch *b, const uint32_t *thr,

@@ -23,6 +23,7 @@
 // clearing bits on placement and a stale mask is always a superset: only
 // candidate groups get the exact check.
 #include "fp_internal.h"
+#include "fp_payload.h"
 // The candidate loop is group-major (below): every register access uses a compile-time
 // group index.  (Round 1's container-major loops and the A/B variants of rounds 2-3 are in git
 // history; DESIGN.md 7 keeps their numbers.)
@@ -1553,53 +1554,14 @@ __global__ void k_gather_payload(uint32_t S, uint32_t C, const uint32_t *__restr
 // positions' values out of the chunk that holds them (level first, for the CYCLE bits).
 // k_gather_payload's two random 4-B reads per container ran at the L2 request rate (2.2 ms for
 // 4096 x 50k; round 3's form below 1.12 ms, by field 0.86 ms).  C <= PL_MAX_C.
-constexpr uint32_t PL_THREADS = 1024, PL_H = 25, PL_MAX_C = PL_THREADS * PL_H * 2;
-// FPP_PAYLOAD_BY_FIELD (A/B switch): 1 = the passes of k_payload_lds are split by field, and order, level,
-// conf and req are each read once per scenario; 0 = round 3's kernel, split by position half, which reads
-// (req, conf) and level once per half.
-#ifndef FPP_PAYLOAD_BY_FIELD
-#define FPP_PAYLOAD_BY_FIELD 1
-#endif
+// The by-field form and its constants live in fp_payload.h: the fused k_scen_sort (fp_place.hip) runs the
+// same passes as its last phase, from the order it still holds in LDS.
+using fpl::PL_THREADS;
+using fpl::PL_H;
+using fpl::PL_MAX_C;
+static_assert(fpl::PL_SKIP == CYC, "fp_payload.h sets the pipeline's skip bit");
 #if FPP_PAYLOAD_BY_FIELD
-// By field: a thread keeps the container indices of all its 2 PL_H positions for the whole kernel, as u16
-// pairs (PL_H registers: an index is below C <= PL_MAX_C < 0xFFFF, and 0xFFFF marks a position past
-// C, which no chunk holds).  level, conf and req then take one pass each through LDS in chunks of
-// PL_CHUNK words: level leaves a CYCLE bit per position, conf is written as soon as its last chunk
-// has been picked and leaves the bit (conf & summ[1]) != 0, req joins the bits and is written with the
-// reason codes.  Per container 4 B of order and 4 B per field are read, 8 B written and s_idx
-// touched where the bit is set, as before.
-constexpr uint32_t PL_ROWS = 2 * PL_H;
-constexpr uint32_t PL_CHUNK = 36 * 1024;  // words of one field: 144 KB of LDS
-constexpr size_t PL_LDS_BYTES = (size_t)PL_CHUNK * 4;
-static_assert(PL_MAX_C < 0xFFFFu, "container indices are kept in 16 bits, 0xFFFF = no position");
-
-// the two indices of pair j, less the chunk's base.  The empty asm keeps the unpacking inside the chunk loop:
-// hoisted out of it, the 2 PL_H unpacked indices live beside the 2 PL_H values and the kernel spills.
-__device__ __forceinline__ void pl_index(uint32_t w, uint32_t a0, uint32_t &d0, uint32_t &d1) {
-    asm volatile("" : "+v"(w));
-    d0 = (w & 0xFFFFu) - a0;
-    d1 = (w >> 16) - a0;
-}
-__device__ __forceinline__ void pl_load_chunk(uint32_t *pl_lds, const uint32_t *__restrict__ src, uint32_t n) {
-    __syncthreads();  // the previous chunk's picks are done
-#pragma unroll 8
-    for (uint32_t i = threadIdx.x; i < n; i += PL_THREADS) pl_lds[i] = __builtin_nontemporal_load(&src[i]);
-    __syncthreads();
-}
-__device__ __forceinline__ void pl_pick_field(uint32_t *pl_lds, const uint32_t *__restrict__ field, uint32_t C,
-                                              const uint32_t (&o)[PL_H], uint32_t (&v)[PL_ROWS]) {
-    for (uint32_t a0 = 0; a0 < C; a0 += PL_CHUNK) {
-        const uint32_t n = C - a0 < PL_CHUNK ? C - a0 : PL_CHUNK;
-        pl_load_chunk(pl_lds, field + a0, n);
-#pragma unroll
-        for (uint32_t j = 0; j < PL_H; ++j) {
-            uint32_t d0, d1;
-            pl_index(o[j], a0, d0, d1);
-            if (d0 < n) v[2 * j] = pl_lds[d0];
-            if (d1 < n) v[2 * j + 1] = pl_lds[d1];
-        }
-    }
-}
+constexpr size_t PL_LDS_BYTES = fpl::PL_FIELD_LDS_BYTES;
 
 __global__ __launch_bounds__(1024) void k_payload_lds(uint32_t C, const uint32_t *__restrict__ order,
                                                       const uint32_t *__restrict__ req,
@@ -1609,73 +1571,7 @@ __global__ __launch_bounds__(1024) void k_payload_lds(uint32_t C, const uint32_t
                                                       uint32_t *__restrict__ s_req, uint32_t *__restrict__ s_conf,
                                                       uint32_t *__restrict__ s_idx) {
     extern __shared__ uint32_t pl_lds[];
-    const uint32_t t = threadIdx.x;
-    const size_t cb = (size_t)blockIdx.x * C;
-    const uint32_t sm0 = summ ? summ[(size_t)blockIdx.x * 4] : 0xFFFFFFFFu;
-    const uint32_t sm1 = summ ? summ[(size_t)blockIdx.x * 4 + 1] : 0u;
-    uint32_t o[PL_H];
-    {
-        uint32_t i[PL_ROWS];  // every load in flight at once; past C the last element, not used
-        const uint32_t *ord = order + cb;
-#pragma unroll
-        for (uint32_t j = 0; j < PL_ROWS; ++j) {
-            const uint32_t p = t + PL_THREADS * j;
-            const uint32_t x = __builtin_nontemporal_load(&ord[p < C ? p : C - 1]);
-            i[j] = p < C ? x & 0xFFFFu : 0xFFFFu;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < PL_H; ++j) o[j] = i[2 * j] | i[2 * j + 1] << 16;
-    }
-    // bit j % 32 of cy0 / cy1 (j < 32 / the rest): position t + 1024 j is a CYCLE member; sc0 / sc1 the same
-    // for (conf & summ[1]) != 0
-    uint32_t cy0 = 0, cy1 = 0;
-    if (level) {
-        for (uint32_t a0 = 0; a0 < C; a0 += PL_CHUNK) {
-            const uint32_t n = C - a0 < PL_CHUNK ? C - a0 : PL_CHUNK;
-            pl_load_chunk(pl_lds, level + cb + a0, n);
-#pragma unroll
-            for (uint32_t j = 0; j < PL_H; ++j) {
-                uint32_t d0, d1;
-                pl_index(o[j], a0, d0, d1);
-                if (d0 < n) (j < 16 ? cy0 : cy1) |= (uint32_t)(pl_lds[d0] == FP_NONE) << ((2 * j) & 31u);
-                if (d1 < n) (j < 16 ? cy0 : cy1) |= (uint32_t)(pl_lds[d1] == FP_NONE) << ((2 * j + 1) & 31u);
-            }
-        }
-    }
-    uint32_t v[PL_ROWS];
-    uint32_t sc0 = 0, sc1 = 0;
-    pl_pick_field(pl_lds, conf + cb, C, o, v);
-    // (each phase takes its positions and their bound from copies of t and C that the compiler cannot see
-    // through: it kept the order loads' 2 PL_H positions, as 64-bit indices in scratch, and their
-    // 2 PL_H lane masks p < C, in spilled SGPRs, for the stores)
-    uint32_t tc = t, Cc = C;
-    asm volatile("" : "+v"(tc), "+s"(Cc));
-    uint32_t *const d_conf = s_conf + cb;
-#pragma unroll
-    for (uint32_t j = 0; j < PL_ROWS; ++j) {
-        const uint32_t p = tc + PL_THREADS * j;
-        if (p < Cc) {
-            __builtin_nontemporal_store(v[j], &d_conf[p]);
-            (j < 32 ? sc0 : sc1) |= (uint32_t)((v[j] & sm1) != 0u) << (j & 31u);
-        }
-    }
-    pl_pick_field(pl_lds, req + cb, C, o, v);
-    uint32_t tr = t, Cr = C;
-    asm volatile("" : "+v"(tr), "+s"(Cr));
-    uint32_t *const d_req = s_req + cb, *const d_idx = s_idx + cb;
-#pragma unroll
-    for (uint32_t j = 0; j < PL_ROWS; ++j) {
-        const uint32_t p = tr + PL_THREADS * j;
-        if (p < Cr) {
-            uint32_t r = v[j];
-            const bool c = ((j < 32 ? cy0 : cy1) >> (j & 31u)) & 1u;
-            const bool x = (r & ~sm0) != 0u || (((j < 32 ? sc0 : sc1) >> (j & 31u)) & 1u);
-            if (c) r = FP_REASON_CYCLE;
-            else if (summ && x) r = FP_REASON_NOFIT;
-            __builtin_nontemporal_store(r, &d_req[p]);
-            if (c || (summ && x)) d_idx[p] |= CYC;
-        }
-    }
+    fpl::pl_by_field<false>(pl_lds, C, order, nullptr, false, req, conf, level, summ, s_req, s_conf, s_idx);
 }
 #else
 // Round 3's form: per half of a thread's positions (PL_H indices in registers) the scenario's (req, conf)
@@ -2158,6 +2054,41 @@ int fp_pipe_soa_take(fp_ctx *c, size_t SC, fp_pipe_soa *soa) {
     return (soa->s_cpu && soa->s_mem && soa->s_req && soa->s_conf && soa->s_idx) ? FP_OK : FP_ENOMEM;
 }
 
+// The stage-2 screen's summary rows and the nodes' share of the batch's OR words (k_node_summary), which
+// depend on the node tables alone: fp_pipe_launch runs it ahead of the payload gather, the fused sort
+// (fp_place.hip) ahead of k_scen_sort, whose last phase reads summ.  *summ: [S][4] from the workspace, or null
+// (no nodes, or FP_OPT_SCREEN = 0: every container enters the pipeline).  The OR words are needed when the
+// packed kernel may run (the same test as fp_pipe_launch's).
+int fp_pipe_node_summary(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, const fp_batch *b, uint32_t *rng,
+                         uint32_t **summ_out) {
+    PipeGeom geo;
+    if (!pipe_geom(c, S, C, N, &geo)) return FP_EOVERFLOW;
+    hipStream_t st = c->stream;
+    uint32_t *summ = nullptr;
+    if (N && fp_opt(c, FP_OPT_SCREEN, 1)) {
+        summ = (uint32_t *)fp_ws_take(c, (size_t)S * 16);
+        if (!summ) return FP_ENOMEM;
+    }
+    launch_fn pkfn = nullptr;
+    if (rng && fp_opt(c, FP_OPT_PACKED, 1) != 0) {
+        const void *k_;
+        pipe_kernel(geo.G, geo.W, wide12_big(S, geo.W, geo.G) && !geo.bounded, true, &pkfn, &k_);
+    }
+    if (N && (summ || pkfn)) {
+        if (summ && pkfn) k_node_summary<true, true><<<S, 256, 0, st>>>(N, b->cpu_free, b->mem_free, b->labels, b->conflict_used, b->schedulable, summ, rng);
+        else if (summ) k_node_summary<true, false><<<S, 256, 0, st>>>(N, b->cpu_free, b->mem_free, b->labels, b->conflict_used, b->schedulable, summ, rng);
+        else k_node_summary<false, true><<<S, 256, 0, st>>>(N, b->cpu_free, b->mem_free, b->labels, b->conflict_used, b->schedulable, summ, rng);
+        FP_HIP(hipGetLastError());
+    }
+    *summ_out = summ;
+    return FP_OK;
+}
+
+// PL_MAX_C for fp_place.hip's choice of the fused sort: the payload runs in LDS chunks up to this C
+uint32_t fp_pipe_payload_lds_max_c(const fp_ctx *c) {
+    return FPP_PAYLOAD_BY_FIELD && fp_opt(c, FP_OPT_PAYLOAD_LDS, 1) != 0 ? PL_MAX_C : 0u;
+}
+
 int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_base, const uint32_t *order,
                    const void *skeys, uint32_t key_bytes, uint32_t mbits, uint64_t cmax, uint64_t mmax,
                    const uint32_t *cval, const uint32_t *mval, const fp_batch *b, const uint32_t *thr,
@@ -2184,13 +2115,6 @@ int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_
     FP_HIP(hipMemsetAsync(ctl, 0, 256 + nlinks * LCTL * 4, st));
     // buckets ride in s_idx when positions fit 21 bits (FP_OPT_KPACK = 0: search per stage)
     const uint32_t kpack = fp_pipe_kpack(c, C);
-    // stage-2 screen (k_node_summary): per-scenario label union / conflict intersection of the
-    // schedulable nodes; FP_OPT_SCREEN = 0 sends every container through the pipeline
-    uint32_t *summ = nullptr;
-    if (N && fp_opt(c, FP_OPT_SCREEN, 1)) {
-        summ = (uint32_t *)fp_ws_take(c, (size_t)S * 16);
-        if (!summ) return FP_ENOMEM;
-    }
     // the packed pair (fp_pipe_pk.h): the batch's node values join the containers' OR (rng, from the sort)
     launch_fn u32fn = nullptr, pkfn = nullptr;
     const bool big = wide12_big(S, W, G) && !geo.bounded;  // (idle flushes of global links need bounded)
@@ -2200,14 +2124,16 @@ int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_
         if (rng && fp_opt(c, FP_OPT_PACKED, 1) != 0) pipe_kernel(G, W, big, true, &pkfn, &k_);
         if (!u32fn) return FP_EOVERFLOW;
     }
-    if (N && (summ || pkfn)) {
-        if (summ && pkfn) k_node_summary<true, true><<<S, 256, 0, st>>>(N, b->cpu_free, b->mem_free, b->labels, b->conflict_used, b->schedulable, summ, rng);
-        else if (summ) k_node_summary<true, false><<<S, 256, 0, st>>>(N, b->cpu_free, b->mem_free, b->labels, b->conflict_used, b->schedulable, summ, rng);
-        else k_node_summary<false, true><<<S, 256, 0, st>>>(N, b->cpu_free, b->mem_free, b->labels, b->conflict_used, b->schedulable, summ, rng);
-        FP_HIP(hipGetLastError());
-    }
+    // stage-2 screen (k_node_summary); the fused sort (fp_place.hip) ran it ahead of itself and the payload
+    // with it: `ready` then carries summ
+    const bool payload_done = ready && ready->payload_done;
+    uint32_t *summ = payload_done ? ready->summ : nullptr;
+    if (!payload_done)
+        if (int rc0 = fp_pipe_node_summary(c, S, C, N, b, rng, &summ)) return rc0;
     const int64_t pl_mode = fp_opt(c, FP_OPT_PAYLOAD_LDS, 1);
-    if (ready && C && C <= PL_MAX_C && pl_mode != 0) {
+    if (payload_done) {
+        // (k_scen_sort's phase P wrote req / conf and the skip bits)
+    } else if (ready && C && C <= PL_MAX_C && pl_mode != 0) {
         // k_scen_sort wrote order, cpu, mem and the position words; req / conf / CYCLE bits
         // through LDS, one workgroup per scenario
         const size_t pl = PL_LDS_BYTES;

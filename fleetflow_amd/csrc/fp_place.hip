@@ -21,6 +21,7 @@
 //                     tiles); lowest feasible node wins, capacity updated in place.
 //   5. k_cost_reduce: packed cost per scenario from the per-segment counters.
 #include "fp_internal.h"
+#include "fp_payload.h"
 
 namespace {
 
@@ -246,6 +247,10 @@ struct ScenSortArgs {
     const uint32_t *scnt;                    // the sample's counts (CN_*)
     const unsigned char *simg;               // the sample's LDS image (k_sort_image), SS_IMG_BYTES
     uint32_t *rng;                           // [2] the batch's OR of every cpu / mem value (CN_ORC)
+    // the fused kernel's phase P (fp_payload.h): the inputs it gathers, the screen's rows (null: no screen)
+    // and the rest of the sorted SoA
+    const uint32_t *req, *conf, *level, *summ;
+    uint32_t *s_req, *s_conf;
 };
 
 // the u16 digit rows are also counted, zeroed and scanned through 32/64-bit views: these
@@ -410,8 +415,9 @@ __device__ void ss_generic(const ScenSortArgs &a, uint16_t *X, uint16_t *WH, uin
 #ifdef FP_PIPE_STATS
 // diagnostics build: k_scen_sort phase cycles summed over workgroups (fp_debug_sort_stats):
 // [0] R (ranks) [1] A0 + offsets [2] A1 [3] B (until the last wave) [4] B busy summed over waves
-// [5] workgroups [6] largest bucket [7] whole kernel
-__device__ unsigned long long g_sort_stats[8];
+// [5] workgroups [6] largest bucket [7] R to B [8] P (the fused kernel's payload phase)
+constexpr int SORT_STATS = 9;
+__device__ unsigned long long g_sort_stats[SORT_STATS];
 #define SS_CLK() __builtin_amdgcn_s_memtime()
 #else
 #define SS_CLK() 0ull
@@ -439,6 +445,13 @@ __device__ __forceinline__ uint32_t ss_block_excl(uint32_t v, uint32_t *part, ui
     return before + inc - v;
 }
 
+// FUSED: phase P follows B in the same workgroup -- the payload gather of fp_payload.h (req, conf, the skip
+// bits), its container indices taken from X, which B left in final order, instead of a second kernel
+// (k_payload_lds) that reads the `order` row back.  Three paths do not leave the order in X and take it from
+// the scenario's `order` row: a bucket above 64 x SS_REG containers (B scatters it straight to HBM; NEXT[3]
+// tells the workgroup), and the generic fallback, reached from pass 0's miss or directly.  From P on the
+// chunk buffer overlays X, LD and every table.
+template <bool FUSED>
 __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ssm[];
     const uint32_t C = a.C;
@@ -641,137 +654,160 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
     };
     uint32_t rr = samp ? rank_pass(0u) : 1u;
     if (rr == 1u) rr = rank_pass(1u);
-    if (rr == 2u) return;  // (ss_generic ORed the scenario's values into a.rng)
-    ss_offsets(WH, HS, HB, t, lane, w);
-    const unsigned long long ck2 = SS_CLK();
+    if (!FUSED && rr == 2u) return;  // (ss_generic ORed the scenario's values into a.rng)
+    if (rr != 2u) {
+        ss_offsets(WH, HS, HB, t, lane, w);
+        const unsigned long long ck2 = SS_CLK();
 
-    // ---- A1: stable scatter by hd, each wave over its own slice (digits from A0's registers) ----
+        // ---- A1: stable scatter by hd, each wave over its own slice (digits from A0's registers) ----
 #pragma unroll
-    for (uint32_t k = 0; k < SS_CHUNKS; ++k) {
-        const uint32_t p0 = s0 + 64 * k;
-        if (p0 >= s1) break;  // wave-uniform
-        const uint32_t p = p0 + lane;
-        const bool valid = p < s1;
-        const uint32_t d = (dvp[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-        const uint64_t m = ss_match(d, valid, hbits);
-        const uint32_t off = myrow[d];
-        if (valid) {
-            if ((m & lt) == 0) myrow[d] = (uint16_t)(off + __popcll(m));
-            X[off + (uint32_t)__popcll(m & lt)] = (uint16_t)p;
+        for (uint32_t k = 0; k < SS_CHUNKS; ++k) {
+            const uint32_t p0 = s0 + 64 * k;
+            if (p0 >= s1) break;  // wave-uniform
+            const uint32_t p = p0 + lane;
+            const bool valid = p < s1;
+            const uint32_t d = (dvp[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+            const uint64_t m = ss_match(d, valid, hbits);
+            const uint32_t off = myrow[d];
+            if (valid) {
+                if ((m & lt) == 0) myrow[d] = (uint16_t)(off + __popcll(m));
+                X[off + (uint32_t)__popcll(m & lt)] = (uint16_t)p;
+            }
         }
-    }
-    __syncthreads();
-    const unsigned long long ck3 = SS_CLK();
-    uint32_t big = 0;
+        __syncthreads();
+        const unsigned long long ck3 = SS_CLK();
+        uint32_t big = 0;
 
-    // ---- B: each hd bucket sorted by ld by one wave and written out ----
-    while (true) {
-        uint32_t d = 0;
-        if (lane == 0) d = atomicAdd(NEXT, 1u);
-        d = (uint32_t)__shfl((int)d, 0);
-        if (d >= dc) break;
-        const uint32_t lo = HS[d], hi = HB[d];
-        if (lo == hi) continue;
-        big = max(big, hi - lo);
-        // the row is zeroed, counted with atomics, scanned and consumed by the same wave: the
-        // fences keep those accesses in order (s_waitcnt lgkmcnt(0), no compiler reordering)
-        reinterpret_cast<ss_u64a *>(myrow)[lane] = 0ull;  // 4 digits per lane
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        const uint32_t cv = CV[d];
-        const uint32_t kbc = a.kpack ? (uint32_t)CB[d] << 21 : 0u;
-        if (hi - lo <= 64 * SS_REG) {
-            // the bucket in registers: count, scan, reorder X[lo, hi) in place, then write the
-            // bucket's window of every output array coalesced
-            uint32_t jv[SS_REG], lv[SS_REG];
-#pragma unroll
-            for (uint32_t k = 0; k < SS_REG; ++k) {
-                const uint32_t p = lo + 64 * k + lane;
-                jv[k] = p < hi ? X[p] : 0u;
-                lv[k] = p < hi ? LD[jv[k]] : 0u;
-                if (p < hi) ss_inc16(myrow, lv[k]);
-            }
+        // ---- B: each hd bucket sorted by ld by one wave and written out ----
+        while (true) {
+            uint32_t d = 0;
+            if (lane == 0) d = atomicAdd(NEXT, 1u);
+            d = (uint32_t)__shfl((int)d, 0);
+            if (d >= dc) break;
+            const uint32_t lo = HS[d], hi = HB[d];
+            if (lo == hi) continue;
+            big = max(big, hi - lo);
+            // the row is zeroed, counted with atomics, scanned and consumed by the same wave: the
+            // fences keep those accesses in order (s_waitcnt lgkmcnt(0), no compiler reordering)
+            reinterpret_cast<ss_u64a *>(myrow)[lane] = 0ull;  // 4 digits per lane
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            ss_row_scan(myrow, lane, lo);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            const uint32_t cv = CV[d];
+            const uint32_t kbc = a.kpack ? (uint32_t)CB[d] << 21 : 0u;
+            if (hi - lo <= 64 * SS_REG) {
+                // the bucket in registers: count, scan, reorder X[lo, hi) in place, then write the
+                // bucket's window of every output array coalesced
+                uint32_t jv[SS_REG], lv[SS_REG];
 #pragma unroll
-            for (uint32_t k = 0; k < SS_REG; ++k) {
-                if (lo + 64 * k >= hi) break;  // wave-uniform
-                const bool valid = lo + 64 * k + lane < hi;
-                const uint64_t m = ss_match(lv[k], valid, lbits);
-                const uint32_t off = myrow[lv[k]];
-                if (valid) {
-                    if ((m & lt) == 0) myrow[lv[k]] = (uint16_t)(off + __popcll(m));
-                    X[off + (uint32_t)__popcll(m & lt)] = (uint16_t)jv[k];
+                for (uint32_t k = 0; k < SS_REG; ++k) {
+                    const uint32_t p = lo + 64 * k + lane;
+                    jv[k] = p < hi ? X[p] : 0u;
+                    lv[k] = p < hi ? LD[jv[k]] : 0u;
+                    if (p < hi) ss_inc16(myrow, lv[k]);
                 }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            for (uint32_t P = lo + lane; P < hi; P += 64) {
-                const uint32_t j = X[P], l = LD[j];
-                a.order[cb + P] = j;
-                a.s_cpu[cb + P] = cv;
-                a.s_mem[cb + P] = MV[l];
-                a.s_idx[cb + P] = P | kbc | (a.kpack ? (uint32_t)MB[l] << 26 : 0u);
-            }
-        } else {  // a large bucket: the same stable order, scattered straight to HBM
-#pragma unroll 4
-            for (uint32_t p = lo + lane; p < hi; p += 64) ss_inc16(myrow, LD[X[p]]);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            ss_row_scan(myrow, lane, lo);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            for (uint32_t p0 = lo; p0 < hi; p0 += 64) {
-                const uint32_t p = p0 + lane;
-                const bool valid = p < hi;
-                const uint32_t j = valid ? X[p] : 0u;
-                const uint32_t l = valid ? LD[j] : 0u;
-                const uint64_t m = ss_match(l, valid, lbits);
-                const uint32_t off = myrow[l];
-                if (valid) {
-                    if ((m & lt) == 0) myrow[l] = (uint16_t)(off + __popcll(m));
-                    const uint32_t P = off + (uint32_t)__popcll(m & lt);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                ss_row_scan(myrow, lane, lo);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+#pragma unroll
+                for (uint32_t k = 0; k < SS_REG; ++k) {
+                    if (lo + 64 * k >= hi) break;  // wave-uniform
+                    const bool valid = lo + 64 * k + lane < hi;
+                    const uint64_t m = ss_match(lv[k], valid, lbits);
+                    const uint32_t off = myrow[lv[k]];
+                    if (valid) {
+                        if ((m & lt) == 0) myrow[lv[k]] = (uint16_t)(off + __popcll(m));
+                        X[off + (uint32_t)__popcll(m & lt)] = (uint16_t)jv[k];
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                for (uint32_t P = lo + lane; P < hi; P += 64) {
+                    const uint32_t j = X[P], l = LD[j];
                     a.order[cb + P] = j;
                     a.s_cpu[cb + P] = cv;
                     a.s_mem[cb + P] = MV[l];
                     a.s_idx[cb + P] = P | kbc | (a.kpack ? (uint32_t)MB[l] << 26 : 0u);
                 }
+            } else {  // a large bucket: the same stable order, scattered straight to HBM
+                if (FUSED && lane == 0) NEXT[3] = 1u;  // X keeps the bucket in hd order only: P reads `order`
+#pragma unroll 4
+                for (uint32_t p = lo + lane; p < hi; p += 64) ss_inc16(myrow, LD[X[p]]);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                ss_row_scan(myrow, lane, lo);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                for (uint32_t p0 = lo; p0 < hi; p0 += 64) {
+                    const uint32_t p = p0 + lane;
+                    const bool valid = p < hi;
+                    const uint32_t j = valid ? X[p] : 0u;
+                    const uint32_t l = valid ? LD[j] : 0u;
+                    const uint64_t m = ss_match(l, valid, lbits);
+                    const uint32_t off = myrow[l];
+                    if (valid) {
+                        if ((m & lt) == 0) myrow[l] = (uint16_t)(off + __popcll(m));
+                        const uint32_t P = off + (uint32_t)__popcll(m & lt);
+                        a.order[cb + P] = j;
+                        a.s_cpu[cb + P] = cv;
+                        a.s_mem[cb + P] = MV[l];
+                        a.s_idx[cb + P] = P | kbc | (a.kpack ? (uint32_t)MB[l] << 26 : 0u);
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        }
+#ifdef FP_PIPE_STATS
+        const unsigned long long ck4 = SS_CLK();
+        if (lane == 0) {
+            atomicAdd(&g_sort_stats[4], ck4 - ck3);
+            atomicMax(&g_sort_stats[6], (unsigned long long)big);
+        }
+        __syncthreads();
+        if (t == 0) {
+            const unsigned long long ck5 = SS_CLK();
+            atomicAdd(&g_sort_stats[0], ck1 - ck0);
+            atomicAdd(&g_sort_stats[1], ck2 - ck1);
+            atomicAdd(&g_sort_stats[2], ck3 - ck2);
+            atomicAdd(&g_sort_stats[3], ck5 - ck3);
+            atomicAdd(&g_sort_stats[5], 1ull);
+            atomicAdd(&g_sort_stats[7], ck5 - ck0);
+        }
+#else
+        (void)ck0; (void)ck1; (void)ck2; (void)ck3; (void)big;
+#endif
+        // the batch's OR words (packed FFD records, fp_pipe_pk.h) from the value tables the digits rank
+        // against: the scenario's own distinct values, or the sample's (a superset of them, and values
+        // of the batch too) -- 2 x <= 256 LDS words by one wave, instead of registers kept live through
+        // A0 (that spilled 162 VGPRs); after B, where the fewest registers are live, and ahead of phase P,
+        // whose chunk buffer overlays the tables
+        if (w == 0) {
+            uint32_t oc = 0, om = 0;
+            for (uint32_t i = lane; i < dc; i += 64) oc |= CV[i];
+            for (uint32_t i = lane; i < dm; i += 64) om |= MV[i];
+            for (int o = 32; o > 0; o >>= 1) {
+                oc |= (uint32_t)__shfl_xor((int)oc, o);
+                om |= (uint32_t)__shfl_xor((int)om, o);
+            }
+            if (lane == 0) {
+                fp_or_new_bits(&a.rng[0], oc);
+                fp_or_new_bits(&a.rng[1], om);
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
+    if constexpr (FUSED) {
+        // ---- P: the payload gather (fp_payload.h) over the order this workgroup just produced.  Every wave
+        // drains its stores of order / s_idx (B, ss_generic) before the barrier; P then reads what other
+        // waves stored -- the `order` row when X does not hold the order, the s_idx words it ORs the skip bit
+        // into -- with agent-scope loads, as ss_generic reads its passes back. ----
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        const unsigned long long ckp = SS_CLK();
+        const bool from_x = rr != 2u && __builtin_amdgcn_readfirstlane((int)NEXT[3]) == 0;  // uniform
+        // (the first chunk load begins with a barrier: every thread has read X, NEXT and the tables by then)
+        fpl::pl_by_field<true>(reinterpret_cast<uint32_t *>(ssm), C, a.order, X, from_x, a.req, a.conf, a.level, a.summ,
+                               a.s_req, a.s_conf, a.s_idx);
 #ifdef FP_PIPE_STATS
-    const unsigned long long ck4 = SS_CLK();
-    if (lane == 0) {
-        atomicAdd(&g_sort_stats[4], ck4 - ck3);
-        atomicMax(&g_sort_stats[6], (unsigned long long)big);
-    }
-    __syncthreads();
-    if (t == 0) {
-        const unsigned long long ck5 = SS_CLK();
-        atomicAdd(&g_sort_stats[0], ck1 - ck0);
-        atomicAdd(&g_sort_stats[1], ck2 - ck1);
-        atomicAdd(&g_sort_stats[2], ck3 - ck2);
-        atomicAdd(&g_sort_stats[3], ck5 - ck3);
-        atomicAdd(&g_sort_stats[5], 1ull);
-        atomicAdd(&g_sort_stats[7], ck5 - ck0);
-    }
+        __syncthreads();
+        if (t == 0) atomicAdd(&g_sort_stats[8], SS_CLK() - ckp);
 #else
-    (void)ck0; (void)ck1; (void)ck2; (void)ck3; (void)big;
+        (void)ckp;
 #endif
-    // the batch's OR words (packed FFD records, fp_pipe_pk.h) from the value tables the digits rank
-    // against: the scenario's own distinct values, or the sample's (a superset of them, and values
-    // of the batch too) -- 2 x <= 256 LDS words by one wave, instead of registers kept live through
-    // A0 (that spilled 162 VGPRs); at the end, where the fewest registers are live
-    if (w == 0) {
-        uint32_t oc = 0, om = 0;
-        for (uint32_t i = lane; i < dc; i += 64) oc |= CV[i];
-        for (uint32_t i = lane; i < dm; i += 64) om |= MV[i];
-        for (int o = 32; o > 0; o >>= 1) {
-            oc |= (uint32_t)__shfl_xor((int)oc, o);
-            om |= (uint32_t)__shfl_xor((int)om, o);
-        }
-        if (lane == 0) {
-            fp_or_new_bits(&a.rng[0], oc);
-            fp_or_new_bits(&a.rng[1], om);
-        }
     }
 }
 
@@ -841,10 +877,10 @@ __global__ __launch_bounds__(1024) void k_sort_image(const uint32_t *__restrict_
 
 #ifdef FP_PIPE_STATS
 extern "C" int fp_debug_sort_stats(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sort_stats), sizeof(unsigned long long) * 8) != hipSuccess)
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sort_stats), sizeof(unsigned long long) * SORT_STATS) != hipSuccess)
         return FP_EDEVICE;
     if (reset) {
-        static const unsigned long long zero[8] = {0};
+        static const unsigned long long zero[SORT_STATS] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_sort_stats), zero, sizeof(zero)) != hipSuccess) return FP_EDEVICE;
     }
     return FP_OK;
@@ -956,9 +992,25 @@ int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b) {
         sa.simg = simg;
         k_sort_image<<<1, 1024, 0, st>>>(rbm, rpre, rval, rcnt, thr, sa.kpack, simg);
         FP_HIP(hipGetLastError());
-        const size_t lds = ss_lds_bytes(C);
-        FP_HIP(hipFuncSetAttribute((const void *)k_scen_sort, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_scen_sort<<<S, 1024, lds, st>>>(sa);
+        // One kernel for sort and payload (FP_OPT_SORT_FUSED = 0: two, as before), wherever k_payload_lds would
+        // have run.  k_node_summary depends on the node tables alone and goes first: phase P reads its rows.
+        const bool fused = FPP_PAYLOAD_BY_FIELD && fp_opt(c, FP_OPT_SORT_FUSED, 1) != 0 && C <= fp_pipe_payload_lds_max_c(c);
+        size_t lds = ss_lds_bytes(C);
+        if (fused) {
+            if (int rs = fp_pipe_node_summary(c, S, C, N, b, sa.rng, &soa.summ)) return rs;
+            soa.payload_done = true;
+            sa.req = b->req_labels; sa.conf = b->conflict; sa.level = b->level; sa.summ = soa.summ;
+            sa.s_req = soa.s_req; sa.s_conf = soa.s_conf;
+            if (lds < fpl::PL_FIELD_LDS_BYTES) lds = fpl::PL_FIELD_LDS_BYTES;
+            static_assert(fpl::PL_FIELD_LDS_BYTES <= SS_LDS_CAP, "the chunk buffer fits the sort's LDS");
+            FP_HIP(hipFuncSetAttribute((const void *)k_scen_sort<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            k_scen_sort<true><<<S, 1024, lds, st>>>(sa);
+        } else {
+            sa.req = sa.conf = sa.level = sa.summ = nullptr;
+            sa.s_req = sa.s_conf = nullptr;
+            FP_HIP(hipFuncSetAttribute((const void *)k_scen_sort<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            k_scen_sort<false><<<S, 1024, lds, st>>>(sa);
+        }
         FP_HIP(hipGetLastError());
         fp_prof_end(c, FP_K_SORT, ev);
         return fp_pipe_launch(c, S, C, N, b->scen_base, order, nullptr, 4, 0, 0, 0, rval, rval + RANK_MAX_VALUE, b,

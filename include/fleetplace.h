@@ -208,7 +208,9 @@ enum fp_option {
     FP_OPT_INDEG_BIN = 21,    /* 0 = levelizer in-degrees by global atomics instead of binned in LDS */
     FP_OPT_PACKED = 22,       /* 0 = FFD on u32 records only; auto = packed (cpu, mem) records when the
                                  batch's values fit them (decided on the device, fp_pipe_pk.h)  */
-    FP_OPT_COUNT = 23
+    FP_OPT_SORT_FUSED = 23,   /* 0 = the per-scenario sort and the LDS-chunked payload as two kernels; auto = one
+                                 kernel (the payload is the sort's last phase), wherever both would run */
+    FP_OPT_COUNT = 24
 };
 int fp_ctx_set_option(fp_ctx *ctx, int option, int64_t value);
 int fp_ctx_get_option(fp_ctx *ctx, int option, int64_t *value);

@@ -30,7 +30,7 @@ def main():
     ghz = ct.c_double(0)
     L.fp_debug_clock_ghz.argtypes = [ct.c_void_p, ct.POINTER(ct.c_double)]
     L.fp_debug_clock_ghz(p._ctx, ct.byref(ghz))
-    buf = (ct.c_ulonglong * 8)()
+    buf = (ct.c_ulonglong * 9)()
     p.profile(True)
     for rep in range(3):
         db.restore_nodes(pristine)
@@ -44,9 +44,11 @@ def main():
     us = lambda x: x / wg / ghz.value / 1e3  # noqa: E731  per workgroup (scenario), microseconds
     print(f"S={S} C={C} N={N} clock {ghz.value:.3f} GHz, sort path avg {sort_ms / max(n, 1):.3f} ms, workgroups {buf[5]}")
     print(f"per scenario us: R {us(buf[0]):.2f}  A0+offsets {us(buf[1]):.2f}  A1 {us(buf[2]):.2f}  "
-          f"B {us(buf[3]):.2f} (busy per wave {us(buf[4]) / 16:.2f})  total {us(buf[7]):.2f}  largest bucket {buf[6]}")
-    print(f"resident: 256 CUs x 1 workgroup -> {S / 256:.0f} rounds x {us(buf[7]):.1f} us = "
-          f"{S / 256 * us(buf[7]) / 1e3:.3f} ms")
+          f"B {us(buf[3]):.2f} (busy per wave {us(buf[4]) / 16:.2f})  R to B {us(buf[7]):.2f}  "
+          f"P (payload, fused kernel) {us(buf[8]):.2f}  largest bucket {buf[6]}")
+    total = us(buf[7]) + us(buf[8])
+    print(f"resident: 256 CUs x 1 workgroup -> {S / 256:.0f} rounds x {total:.1f} us = "
+          f"{S / 256 * total / 1e3:.3f} ms")
 
 
 if __name__ == "__main__":
