@@ -10,6 +10,7 @@
 
 namespace {
 
+// tests/feas_ref.py (feas_plan) restates these and the launch arithmetic below: retune them together
 constexpr int kBlock = 256;   // threads per block (4 waves)
 constexpr int kPer = 4;       // containers per thread: one LDS node read serves 4 x 64 containers (8: slower)
 constexpr int kTile = 1024;   // nodes per LDS chunk

@@ -748,6 +748,10 @@ def test_feasibility_batch_vs_oracle(S, C, N, planner, O):
         ef, ec, _ = O.feasibility(tuple(np.asarray(x)[:k] for x in cont), nodes, want_bitmap=False)
         assert np.array_equal(fh[s * C:s * C + k], ef), s
         assert np.array_equal(ch[s * C:s * C + k], ec), s
+        # and the last k, so that the ragged last block of 1024 containers is looked at
+        ef, ec, _ = O.feasibility(tuple(np.asarray(x)[C - k:] for x in cont), nodes, want_bitmap=False)
+        assert np.array_equal(fh[(s + 1) * C - k:(s + 1) * C], ef), s
+        assert np.array_equal(ch[(s + 1) * C - k:(s + 1) * C], ec), s
 
 
 def test_levelize_deep_chain_three_sort_passes(planner, O):
