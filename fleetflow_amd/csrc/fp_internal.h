@@ -192,6 +192,15 @@ int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
                             const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
                             uint32_t *summary_out, const fp_drain_policy &pol = fp_drain_policy());
 
+// scale-in sweep (fp_shrink.hip, SPEC.md 2.16); every pointer is device memory.  assign and try_order values out
+// of range are found on the device (FP_EINVAL in the context's error word, nothing written)
+// the most containers a call takes: the scan's positions, rounded up to a whole step, stay below 2^31
+constexpr uint32_t FP_SHRINK_MAX_CONTAINERS = 0x7FFF0000u;
+int fp_dev_shrink_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                             const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                             uint32_t preferred, const uint32_t *node_count, uint32_t *assign_out, uint8_t *state_out,
+                             uint32_t *blocker_out, uint32_t *summary_out);
+
 // scale-out sweep (fp_grow.hip, SPEC.md 2.12); every pointer is device memory, max_new a host value.  A t_max
 // value above max_new is found on the device (FP_EINVAL in the context's error word, nothing written)
 int fp_dev_grow_sweep_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,

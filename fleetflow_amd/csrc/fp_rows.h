@@ -161,6 +161,30 @@ static inline int fp_drain_policy_rows(const fp_containers *cs, const fp_nodes *
     return n;
 }
 
+// fp_shrink_sweep (SPEC.md 2.16): the tables, the live plan, the release orders, the counts; then the four results
+struct fp_shrink_dev {
+    fp_containers cs;
+    fp_nodes ns;
+    const uint32_t *assign, *try_order, *node_count;
+    uint32_t *assign_out, *blocker_out, *summary;
+    uint8_t *state_out;
+};
+static inline int fp_shrink_rows(const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                 const uint32_t *try_order, uint32_t n_var, uint32_t n_try, const uint32_t *node_count,
+                                 uint32_t *assign_out, uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out,
+                                 fp_shrink_dev *d, fp_row *r) {
+    const size_t C = cs->n, N = ns->n, V = n_var;
+    int n = fp_tables_rows(cs, ns, &d->cs, &d->ns, r);
+    r[n++] = fp_row_in(assign, C, &d->assign);
+    r[n++] = fp_row_in(try_order, V * n_try, &d->try_order);
+    r[n++] = fp_row_in(node_count, N, &d->node_count);
+    r[n++] = fp_row_out(assign_out, V * C, &d->assign_out);
+    r[n++] = fp_row_out(state_out, V * N, &d->state_out);
+    r[n++] = fp_row_opt(blocker_out, V * N, &d->blocker_out);
+    r[n++] = fp_row_out(summary_out, V * FP_SHRINK_WORDS, &d->summary);
+    return n;
+}
+
 // fp_grow_sweep: the requests, the reasons (absent without a mask), the templates; then the two results
 struct fp_grow_dev {
     fp_containers cs;

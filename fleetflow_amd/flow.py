@@ -754,6 +754,125 @@ def drain_stage(flow: Flow, stage_name: str, plan: Plan, by: str | None = None, 
 
 
 @dataclass
+class ShrinkVariant:
+    """One release order of a scale-in sweep (SPEC.md 2.16): the servers it gives back, what moves so that it
+    can, and the servers it tried and could not free."""
+    name: str                              # the rule's name, or "order<i>" for an explicit list
+    order: list[str]                       # the servers in the order they were tried (slugs)
+    released: list[str]                    # the servers given back, in try order
+    moves: list[tuple[str, str, str]]      # (service, from, to): from = the server of the base plan, to = the final one
+    stayed: list[tuple[str, str]]          # (server, blocker service) for each server whose last attempt failed
+    tried: int = 0                         # attempts made
+    failed: int = 0                        # attempts undone
+    n_moves: int = 0                       # committed moves; a service that moved twice counts twice
+    moved_cpu_m: int = 0                   # what the moved services ask for in sum
+    moved_mem_mib: int = 0
+
+
+@dataclass
+class ShrinkReport:
+    """``shrink_stage``'s answer: one ShrinkVariant per release order, every one computed independently from the
+    same live state under the strategy and preferred labels named here.  ``best`` indexes the variant with the
+    most released servers, then the fewest moved services, then the lowest index (None without variants), and
+    ``plan`` is the plan that variant leaves."""
+    stage: str
+    strategy: str | None = None
+    preferred: list[str] = field(default_factory=list)
+    keep: list[str] = field(default_factory=list)
+    variants: list[ShrinkVariant] = field(default_factory=list)
+    best: int | None = None
+    plan: Plan | None = None
+
+
+SHRINK_RULES = ("fewest", "lightest", "last")
+
+
+def shrink_order(rule: str, nodes: list[Server], cont, assign, keep=()) -> list[int]:
+    """The node indices a rule tries, in order: the servers flagged ``draining`` first, then ``"fewest"`` by
+    running services ascending, ``"lightest"`` by the sum of the running cpu requests ascending, ``"last"`` by
+    node order descending (the reverse of the way first fit fills); ties in node order.  ``keep`` (slugs) are
+    left out."""
+    if rule not in SHRINK_RULES:
+        raise ValueError(f"shrink: unknown order rule '{rule}' (one of {', '.join(SHRINK_RULES)})")
+    count, load = [0] * len(nodes), [0] * len(nodes)
+    for v, n in enumerate(assign):
+        if n != NONE:
+            count[n] += 1
+            load[n] += cont[0][v]
+    held = set(keep)
+    idx = [n for n, nd in enumerate(nodes) if nd.slug not in held]
+    if rule == "fewest":
+        key = lambda n: (not nodes[n].draining, count[n], n)  # noqa: E731
+    elif rule == "lightest":
+        key = lambda n: (not nodes[n].draining, load[n], n)  # noqa: E731
+    else:
+        key = lambda n: (not nodes[n].draining, -n)  # noqa: E731
+    return sorted(idx, key=key)
+
+
+def shrink_stage(flow: Flow, stage_name: str, plan: Plan, orders=None, keep=None, planner: Planner | None = None,
+                 policy: PlacementPolicy | None = None) -> ShrinkReport:
+    """"Which servers can I hand back, and what has to move so that I can?" for a stage that runs as ``plan``
+    says (SPEC.md 2.16): one ``Planner.shrink_sweep`` over the live tables of ``live_tables``, one variant per
+    entry of ``orders``.  An entry is a rule name (``shrink_order``: "fewest", "lightest", "last") or an explicit
+    list of server slugs; the default is all three rules.  ``keep`` (slugs) are never tried, in a rule or in an
+    explicit list; an unknown slug anywhere is a ValueError.
+
+    A variant tries its servers one after the other on the state its earlier releases left: the server's
+    services are visited in the order (cpu desc, mem desc, stage order) and go to the remaining schedulable
+    servers under the strategy and preferred labels of ``policy`` or, without one, of the policy the plan was
+    made under; if one of them finds no server the attempt is undone and the server stays.  The policy's spread
+    constraint, fallback chain and quota are not applied to moves."""
+    import dataclasses
+    from ._lib import (SHRINK_FAILED, SHRINK_MOVED_CPU, SHRINK_MOVED_MEM, SHRINK_MOVES, SHRINK_STATE_FAILED,
+                       SHRINK_STATE_RELEASED, SHRINK_TRIED)
+    p = planner or default_planner()
+    names, nodes, cont, live, assign, count, strategy, pmask = live_tables(flow, stage_name, plan, policy)
+    pol_pref = policy.preferred if policy is not None else list(plan.preferred)
+    keep = list(keep or [])
+    report = ShrinkReport(stage_name, strategy, pol_pref, keep)
+    slugs = [nd.slug for nd in nodes]
+    index = {s: n for n, s in enumerate(slugs)}
+    unknown = [s for s in keep if s not in index]
+    if unknown:
+        raise ValueError(f"shrink: {unknown} are no servers of stage '{stage_name}'")
+    rows, labels = [], []
+    for i, entry in enumerate(SHRINK_RULES if orders is None else orders):
+        if isinstance(entry, str):
+            rows.append(shrink_order(entry, nodes, cont, assign, keep))
+            labels.append(entry)
+        else:
+            unknown = [s for s in entry if s not in index]
+            if unknown:
+                raise ValueError(f"shrink: {unknown} are no servers of stage '{stage_name}'")
+            rows.append([index[s] for s in entry if s not in keep])
+            labels.append(f"order{i}")
+    if not rows:
+        return report
+    n_try = max(len(r) for r in rows)
+    try_order = np.full((len(rows), n_try), NONE, np.uint32)
+    for i, r in enumerate(rows):
+        try_order[i, :len(r)] = r
+    out, state, blocker, summary = p.shrink_sweep(cont, live, assign, try_order, strategy if strategy is not None else 0,
+                                                  pmask, count)
+    visit = sorted(range(len(names)), key=lambda v: (-cont[0][v], -cont[1][v], v))
+    for i, r in enumerate(rows):
+        row = [int(x) for x in summary[i]]
+        freed = [slugs[n] for n in dict.fromkeys(r) if int(state[i][n]) == SHRINK_STATE_RELEASED]
+        moves = [(names[v], slugs[assign[v]], slugs[int(out[i][v])]) for v in visit if int(out[i][v]) != assign[v]]
+        stayed = [(slugs[n], names[int(blocker[i][n])]) for n in dict.fromkeys(r) if int(state[i][n]) == SHRINK_STATE_FAILED]
+        report.variants.append(ShrinkVariant(labels[i], [slugs[n] for n in r], freed, moves, stayed, row[SHRINK_TRIED],
+                                             row[SHRINK_FAILED], row[SHRINK_MOVES], row[SHRINK_MOVED_CPU],
+                                             row[SHRINK_MOVED_MEM]))
+    report.best = min(range(len(rows)), key=lambda i: (-len(report.variants[i].released), len(report.variants[i].moves), i))
+    assignment = dict(plan.assignment)
+    for svc, _, dst in report.variants[report.best].moves:
+        assignment[svc] = dst
+    report.plan = dataclasses.replace(plan, assignment=assignment)
+    return report
+
+
+@dataclass
 class GrowCandidate:
     """One candidate of a scale-out sweep (SPEC.md 2.12): a server template and what adding servers of it does
     for the plan's unplaced services."""

@@ -21,6 +21,10 @@ under the policy (SPEC.md 2.15) adds ``placement.spread`` / ``placement.fallback
 the services of each new server indented under it where the candidate was detailed, and ``grow_report_to_json``
 / ``grow_report_from_json`` carry it as ``{stage, max_new, pending, candidates: [{name, cpu_m, ...}]}``.
 
+``format_shrink_report`` prints a scale-in sweep (SPEC.md 2.16, ``flow.shrink_stage``), one block per release order,
+and ``shrink_report_to_json`` / ``shrink_report_from_json`` carry it as ``{stage, placement: {strategy, preferred},
+keep, best, plan, variants: [{name, order, released, moves, stayed, ...}]}`` with ``plan`` in ``plan_to_json``'s form.
+
 ``format_replan_report`` prints a re-plan (SPEC.md 2.13, ``flow.replan_stage``): one line of counts, then the
 moves, the new and the lost services, and ``replan_report_to_json`` / ``replan_report_from_json`` carry it as
 ``{plan, kept, new, moved, lost, moved_cpu_m, moved_mem_mib}`` with ``plan`` in ``plan_to_json``'s form.
@@ -42,7 +46,8 @@ import json
 from dataclasses import asdict
 
 from ._lib import QUOTA_NAMES
-from .flow import U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, GrowCandidate, GrowReport, Plan, Replan, Why
+from .flow import (U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, GrowCandidate, GrowReport, Plan, Replan,
+                   ShrinkReport, ShrinkVariant, Why)
 from .parser import FlowError
 
 
@@ -148,6 +153,43 @@ def drain_report_from_json(text: str) -> DrainReport:
                        (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"),
                        list((pol.get("fallback") or {}).get("relax_order") or []),
                        (pol.get("fallback") or {}).get("max_hops"))
+
+
+def format_shrink_report(report: ShrinkReport) -> str:
+    """One line per release order, ``shrink <name>: <r> of <t> servers released, <m> services move (<cpu>m cpu,
+    <mem> MiB), <f> attempts undone``, marked ``(best)`` where it is, with the released servers
+    (``released: a, b``), the moves (``service: from -> to``) and the servers that stayed (``server: stays
+    (blocked by service)``) indented under it."""
+    lines = []
+    for i, v in enumerate(report.variants):
+        lines.append(f"shrink {v.name}: {len(v.released)} of {v.tried} servers released, {len(v.moves)} services move "
+                     f"({v.moved_cpu_m}m cpu, {v.moved_mem_mib} MiB), {v.failed} attempts undone"
+                     + (" (best)" if i == report.best else ""))
+        if v.released:
+            lines.append(f"  released: {', '.join(v.released)}")
+        lines += [f"  {svc}: {src} -> {dst}" for svc, src, dst in v.moves]
+        lines += [f"  {srv}: stays (blocked by {svc})" for srv, svc in v.stayed]
+    return "\n".join(lines)
+
+
+def shrink_report_to_json(report: ShrinkReport, indent: int | None = None) -> str:
+    d = {"stage": report.stage, "placement": {"strategy": report.strategy, "preferred": report.preferred},
+         "keep": report.keep, "best": report.best,
+         "plan": None if report.plan is None else json.loads(plan_to_json(report.plan)),
+         "variants": [asdict(v) for v in report.variants]}
+    return json.dumps(d, ensure_ascii=False, indent=indent)
+
+
+def shrink_report_from_json(text: str) -> ShrinkReport:
+    d = json.loads(text)
+    pol = d.get("placement") or {}
+    variants = [ShrinkVariant(v["name"], list(v["order"]), list(v["released"]), [tuple(m) for m in v["moves"]],
+                              [tuple(x) for x in v["stayed"]], v.get("tried", 0), v.get("failed", 0), v.get("n_moves", 0),
+                              v.get("moved_cpu_m", 0), v.get("moved_mem_mib", 0)) for v in d.get("variants") or []]
+    plan = d.get("plan")
+    return ShrinkReport(d["stage"], pol.get("strategy"), list(pol.get("preferred") or []), list(d.get("keep") or []),
+                        variants, d.get("best"),
+                        None if plan is None else plan_from_json(json.dumps(plan, ensure_ascii=False)))
 
 
 def format_replan_report(report: Replan) -> str:

@@ -701,6 +701,35 @@ class Planner:
             nc[n:n + 1] += np.uint32(1)
         return out, reason, nodes, nc, summary[0]
 
+    def shrink_sweep(self, cont, nodes, assign, try_order, strategy=0, preferred=0, node_count=None):
+        """Scale-in sweep (SPEC.md 2.16, fp_shrink_sweep): ``nodes`` is the live table, ``assign`` [C] the node
+        each container runs on (NONE = not running), ``try_order`` [n_var, n_try] one release order per row (node
+        indices; NONE entries are skipped, so rows may be ragged).  Every variant starts from the base state and
+        tries its nodes in order: the containers now on the node are re-placed on the schedulable nodes that are
+        not released under ``strategy`` / ``preferred`` (SPEC.md 2.6) and ``node_count`` ([N] or None = zeros);
+        when all fit the node is released, otherwise the attempt is undone.  Inputs are not mutated.  Returns
+        (assign_out [n_var, C], state [n_var, N] of _lib.SHRINK_STATE_*, blocker [n_var, N], summary [n_var, 8]);
+        summary's word indices are _lib.SHRINK_*."""
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
+        asg = _u32(assign)
+        tro = _u32(try_order)
+        self._need(tro.ndim == 2, "try_order must be [n_var, n_try]")
+        n_var, n_try = tro.shape
+        nc = _u32(node_count) if node_count is not None else None
+        strategy = strategy_id(strategy)
+        self._need(asg.size == C, "assign must hold C entries")
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        out = np.empty((n_var, C), np.uint32)
+        state = np.empty((n_var, N), np.uint8)
+        blocker = np.empty((n_var, N), np.uint32)
+        summary = np.empty((n_var, _lib.SHRINK_WORDS), np.uint32)
+        cs, ns = _pair(cont, nodes)
+        check(self._L.fp_shrink_sweep(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(tro), n_var, n_try,
+                                      strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(out), _arg(state),
+                                      _arg(blocker), _arg(summary)), "fp_shrink_sweep")
+        return out, state, blocker, summary
+
     def grow_sweep(self, cont, reason, templates, max_new, reason_mask=1 << _lib.REASON_NOFIT, t_max=None,
                    want_assign=False):
         """Scale-out sweep (SPEC.md 2.12, fp_grow_sweep): the pending containers are those of ``cont`` whose
@@ -794,6 +823,40 @@ class Planner:
             self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(group_t), n_cand, strategy,
             int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(assign_out_t), _arg(reason_t), _arg(summary_t)),
             "fp_dev_drain_sweep"))
+
+    def dev_shrink_sweep(self, cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t,
+                         strategy=0, preferred=0, count_t=None, blocker_t=None):
+        """fp_dev_shrink_sweep on device tensors: ``cont_t``, ``nodes_t``, ``assign_t`` and ``count_t`` as in
+        ``dev_drain_sweep``, ``try_order_t`` [n_var * n_try]; out: ``assign_out_t`` [n_var * C], ``state_t``
+        [n_var * N] uint8, ``summary_t`` [n_var * 8] and ``blocker_t`` [n_var * N] or None.  An assign or
+        try_order value out of range is found on the device: nothing is written and sync() raises FP_EINVAL."""
+        C, N, n_var, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_var), strategy_id(strategy)
+        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
+                   "every container tensor must hold C 32-bit entries")
+        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
+                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
+                   "every node tensor must hold N entries (schedulable N bytes)")
+        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
+        self._need(0 <= n_var <= 0xFFFFFFFF, "n_var must be a u32")
+        self._need(try_order_t.element_size() == 4 and (try_order_t.numel() % n_var == 0 if n_var
+                                                        else try_order_t.numel() == 0),
+                   "try_order_t must hold n_var rows of 32-bit entries")
+        n_try = try_order_t.numel() // n_var if n_var else 0
+        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
+                   "count_t must hold N 32-bit entries")
+        self._need(assign_out_t.numel() == n_var * C and assign_out_t.element_size() == 4,
+                   "assign_out_t must hold n_var * C 32-bit entries")
+        self._need(state_t.numel() == n_var * N and state_t.element_size() == 1, "state_t must hold n_var * N bytes")
+        self._need(blocker_t is None or (blocker_t.numel() == n_var * N and blocker_t.element_size() == 4),
+                   "blocker_t must hold n_var * N 32-bit entries")
+        self._need(summary_t.numel() == n_var * _lib.SHRINK_WORDS and summary_t.element_size() == 4,
+                   "summary_t must hold n_var * 8 32-bit entries")
+        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
+        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
+        self._dev(lambda: check(self._L.fp_dev_shrink_sweep(
+            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(try_order_t), n_var, n_try, strategy,
+            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(assign_out_t), _arg(state_t), _arg(blocker_t),
+            _arg(summary_t)), "fp_dev_shrink_sweep"))
 
     def dev_drain_sweep_policy(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t,
                                strategy=0, preferred=0, count_t=None, *, domain_t=None, max_skew=0, relax_mask=(),

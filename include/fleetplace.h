@@ -33,6 +33,9 @@
  *                        FallbackPolicy, on counts that leave the candidate's own servers out (model.rs:47-63;
  *                        the ResourceQuota of model.rs:38-45 has nothing to test: a move releases and retakes
  *                        the same request)
+ *   fp_shrink_sweep   <- new: the servers a live plan can give back when they are tried in a given order, for
+ *                        many orders at once: the `drain` state applied server after server, each release on
+ *                        the state the earlier ones left  crates/fleetflow-controlplane/src/model.rs:435-442
  *   fp_grow_sweep     <- new: the new servers of each template (a plan string's size,
  *                        crates/fleetflow-cloud-sakura/src/provider.rs:15-30, with the ServerLabels /
  *                        ServerCapacity a new server would carry, crates/fleetflow-controlplane/src/model.rs:399-419)
@@ -413,6 +416,38 @@ int fp_drain_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nodes *n
                           const uint32_t *node_count, const uint32_t *domain, uint32_t max_skew,
                           const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out, uint8_t *reason_out,
                           uint8_t *hops_out, uint32_t *summary_out, uint32_t *policy_out);
+/* Scale-in sweep (SPEC.md 2.16): "which servers can I hand back, and what has to move so that I can?", asked of
+ * every release order at once.  containers, nodes (the LIVE table), assign, strategy, preferred_labels and
+ * node_count are fp_drain_sweep's.  Variant v is a release order try_order[v][0 .. n_try): node indices, FP_NONE
+ * entries are skipped (ragged rows).  Every variant starts from the base state and is independent of the others.
+ * Its entries are visited in order; an entry naming a node the variant already released is skipped; every other
+ * entry is an ATTEMPT on its node n: the containers now on n are visited in fp_place's order and each goes to the
+ * feasible node with the smallest fp_place_policy key among the targets (schedulable, not released, not n), on
+ * the state the variant's committed attempts and this attempt's earlier moves left.  When every one finds a
+ * target the attempt COMMITS (n is released; an attempt without containers commits with zero moves; a cordoned n
+ * is attempted like any other).  At the first container no target takes (the BLOCKER) the attempt is UNDONE: the
+ * state is exactly what it was before the attempt and n stays a target; a later entry naming n is a fresh attempt.
+ *   assign_out  [n_var][c->n]      the variant's final assignment
+ *   state_out   [n_var][nodes->n]  u8 per node: NEVER (not attempted), RELEASED, FAILED (its last attempt failed)
+ *   blocker_out [n_var][nodes->n]  nullable: the blocker of a node in state FAILED, else FP_NONE
+ *   summary_out [n_var][FP_SHRINK_WORDS]:
+ *     RELEASED  nodes released      TRIED  attempts      FAILED  attempts undone (RELEASED + FAILED == TRIED)
+ *     MOVES  committed moves, a container counts once per move      MOVED  containers with assign_out != assign
+ *     MOVED_CPU, MOVED_MEM  the sums of the MOVED containers' requests (u32, wrap)
+ *     FIRST_FAILED  the node of the first failed attempt, else FP_NONE
+ * nodes->n above FP_POLICY_MAX_NODES, n_var above 65535 or c->n above 0x7FFF0000 (2^31 - 2^16: the positions the
+ * kernel scans stay below 2^31) is FP_EOVERFLOW; a strategy above
+ * FP_STRATEGY_FILL_LOWEST, assign_out == assign and an assign or try_order value that is neither < nodes->n nor
+ * FP_NONE are FP_EINVAL;
+ * on any error nothing is written.  n_var == 0 is FP_OK.  Zones as candidates, the policy's spread constraint,
+ * fallback chain and quota, and the choice of the order are not part of this call. */
+enum { FP_SHRINK_RELEASED = 0, FP_SHRINK_TRIED = 1, FP_SHRINK_FAILED = 2, FP_SHRINK_MOVES = 3, FP_SHRINK_MOVED = 4,
+       FP_SHRINK_MOVED_CPU = 5, FP_SHRINK_MOVED_MEM = 6, FP_SHRINK_FIRST_FAILED = 7, FP_SHRINK_WORDS = 8 };
+enum { FP_SHRINK_STATE_NEVER = 0, FP_SHRINK_STATE_RELEASED = 1, FP_SHRINK_STATE_FAILED = 2 };
+int fp_shrink_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                    const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                    uint32_t preferred_labels, const uint32_t *node_count, uint32_t *assign_out, uint8_t *state_out,
+                    uint32_t *blocker_out, uint32_t *summary_out);
 /* Scale-out sweep (SPEC.md 2.12): "what do I have to add?", asked of every server template at once.  The pending
  * containers are those whose reason's bit is set in reason_mask (fp_explain_batch's convention; reason_mask == 0
  * selects every container and reason is not read and may be NULL).  Candidate k is a template: a new server has
@@ -584,6 +619,15 @@ int fp_dev_drain_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_node
                               const uint32_t *node_count, const uint32_t *domain, uint32_t max_skew,
                               const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
                               uint8_t *reason_out, uint8_t *hops_out, uint32_t *summary_out, uint32_t *policy_out);
+/* As fp_shrink_sweep on device pointers (every output included).  An assign or try_order value out of range is
+ * found on the device before any store: nothing is written and fp_ctx_sync() reports FP_EINVAL.  The call takes
+ * the FFD order's 24 bytes per container plus the sort's scratch and 12 bytes per container and variant (one of
+ * the three words rounded up to a multiple of 16384 containers, of 1024 with at most 64 nodes) from the context's
+ * workspace. */
+int fp_dev_shrink_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                        const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                        uint32_t preferred_labels, const uint32_t *node_count, uint32_t *assign_out,
+                        uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out);
 /* As fp_grow_sweep on device pointers (max_new stays a host value: the kernel's geometry follows it, nothing is
  * read back).  A t_max[k] > max_new is found on the device before any store: nothing is written and fp_ctx_sync()
  * reports FP_EINVAL.  The call takes 28 bytes per container plus the sort's scratch from the context's workspace. */

@@ -56,6 +56,19 @@ pub const FP_DRAIN_TARGETS: usize = 4;
 pub const FP_DRAIN_FIRST_STRANDED: usize = 5;
 pub const FP_DRAIN_NODES: usize = 6;
 pub const FP_DRAIN_WORDS: usize = 8;
+// scale-in sweep (SPEC.md 2.16): the word indices of a variant's summary row and the values of a node's state
+pub const FP_SHRINK_RELEASED: usize = 0;
+pub const FP_SHRINK_TRIED: usize = 1;
+pub const FP_SHRINK_FAILED: usize = 2;
+pub const FP_SHRINK_MOVES: usize = 3;
+pub const FP_SHRINK_MOVED: usize = 4;
+pub const FP_SHRINK_MOVED_CPU: usize = 5;
+pub const FP_SHRINK_MOVED_MEM: usize = 6;
+pub const FP_SHRINK_FIRST_FAILED: usize = 7;
+pub const FP_SHRINK_WORDS: usize = 8;
+pub const FP_SHRINK_STATE_NEVER: u8 = 0;
+pub const FP_SHRINK_STATE_RELEASED: u8 = 1;
+pub const FP_SHRINK_STATE_FAILED: u8 = 2;
 // the drain sweep under the policy (SPEC.md 2.15): the word indices of a candidate's policy row
 pub const FP_DRAIN_STRANDED_SKEW: usize = 0;
 pub const FP_DRAIN_RELAXED: usize = 1;
@@ -255,6 +268,10 @@ unsafe extern "C" {
                                  preferred_labels: u32, node_count: *const u32, domain: *const u32, max_skew: u32,
                                  relax_mask: *const u32, n_hops: u32, assign_out: *mut u32, reason_out: *mut u8,
                                  hops_out: *mut u8, summary_out: *mut u32, policy_out: *mut u32) -> c_int;
+    pub fn fp_shrink_sweep(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes, assign: *const u32,
+                           try_order: *const u32, n_var: u32, n_try: u32, strategy: u32, preferred_labels: u32,
+                           node_count: *const u32, assign_out: *mut u32, state_out: *mut u8, blocker_out: *mut u32,
+                           summary_out: *mut u32) -> c_int;
     pub fn fp_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32, n_cand: u32,
                          t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32, t_max: *const u32,
                          max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
@@ -319,6 +336,10 @@ unsafe extern "C" {
                                      max_skew: u32, relax_mask: *const u32, n_hops: u32, assign_out: *mut u32,
                                      reason_out: *mut u8, hops_out: *mut u8, summary_out: *mut u32,
                                      policy_out: *mut u32) -> c_int;
+    pub fn fp_dev_shrink_sweep(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes,
+                               assign: *const u32, try_order: *const u32, n_var: u32, n_try: u32, strategy: u32,
+                               preferred_labels: u32, node_count: *const u32, assign_out: *mut u32,
+                               state_out: *mut u8, blocker_out: *mut u32, summary_out: *mut u32) -> c_int;
     pub fn fp_dev_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
                              n_cand: u32, t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32,
                              t_max: *const u32, max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;

@@ -162,6 +162,40 @@ impl Planner {
         Ok((out, reason, rows))
     }
 
+    /// Scale-in sweep (SPEC.md 2.16, fleetplace.h `fp_shrink_sweep`): `nodes` is the live table, `assign` the
+    /// node each container runs on, `try_order` one release order per variant, `n_try` entries each
+    /// (`ffi::FP_NONE` entries are skipped).  Every variant tries its nodes in order from the same base state; an
+    /// attempt whose containers all find another node releases its node, any other is undone.  No input is
+    /// changed.  Returns per variant (the final node per container, the state per node (`ffi::FP_SHRINK_STATE_*`),
+    /// the blocker per node, its row of `ffi::FP_SHRINK_WORDS` words).
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn shrink_sweep(&mut self, c: &Containers, nodes: &Nodes, assign: &[u32], try_order: &[u32], n_try: u32,
+                        strategy: u32, preferred_labels: u32, node_count: Option<&[u32]>)
+                        -> Result<(Vec<u32>, Vec<u8>, Vec<u32>, Vec<[u32; ffi::FP_SHRINK_WORDS]>), PlanError> {
+        let (n, nn) = (c.cpu_m.len(), nodes.cpu_free.len());
+        let n_var = if n_try == 0 { 0 } else { try_order.len() / n_try as usize };
+        if !c.all_len(n) || !nodes.all_len(nn) || assign.len() != n || try_order.len() != n_var * n_try as usize
+            || n_var > u32::MAX as usize || node_count.map_or(false, |k| k.len() != nn) {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        // fp_shrink_sweep reads the node table only: the mutable pointers of fp_nodes are never written through
+        let ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_ptr() as *mut u32,
+                                 mem_free: nodes.mem_free.as_ptr() as *mut u32, labels: nodes.labels.as_ptr(),
+                                 conflict_used: nodes.conflict_used.as_ptr() as *mut u32,
+                                 schedulable: nodes.schedulable.as_ptr() };
+        let (mut out, mut state, mut blocker) = (vec![0u32; n_var * n], vec![0u8; n_var * nn], vec![0u32; n_var * nn]);
+        let mut rows = vec![[0u32; ffi::FP_SHRINK_WORDS]; n_var];
+        check(unsafe {
+            ffi::fp_shrink_sweep(self.ctx, &cs, &ns, assign.as_ptr(), try_order.as_ptr(), n_var as u32, n_try, strategy,
+                                 preferred_labels, node_count.map_or(std::ptr::null(), |k| k.as_ptr()),
+                                 out.as_mut_ptr(), state.as_mut_ptr(), blocker.as_mut_ptr(),
+                                 rows.as_mut_ptr() as *mut u32)
+        })?;
+        Ok((out, state, blocker, rows))
+    }
+
     /// The drain sweep under the policy (SPEC.md 2.15, fleetplace.h `fp_drain_sweep_policy`): `drain_sweep` with
     /// every move held to the spread constraint (`domain` ids below `ffi::FP_SPREAD_MAX_DOMAINS` and `max_skew`;
     /// None or 0 = none) and the fallback chain (`relax_mask`: per hop the label bits it gives up, at most
