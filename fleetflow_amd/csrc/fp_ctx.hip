@@ -964,6 +964,69 @@ extern "C" int fp_shrink_sweep(fp_ctx *c, const fp_containers *cs, const fp_node
     return copy_back_all(c, rows, n);
 }
 
+// the scale-in sweep under the policy (SPEC.md 2.17, fp_shrink.hip).  relax_mask is a host array in both entries
+extern "C" int fp_dev_shrink_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                          const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                                          uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                                          uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                          uint32_t *assign_out, uint8_t *state_out, uint32_t *blocker_out,
+                                          uint32_t *summary_out, uint8_t *hops_out, uint8_t *blocker_reason_out,
+                                          uint32_t *policy_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_shrink_policy pol;
+    pol.domain = domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
+    pol.hops_out = hops_out; pol.blocker_reason_out = blocker_reason_out; pol.policy_out = policy_out;
+    return fp_dev_done(c, fp_dev_shrink_sweep_impl(c, cs, ns, assign, try_order, n_var, n_try, strategy, preferred_labels,
+                                                   node_count, assign_out, state_out, blocker_out, summary_out, pol));
+}
+
+extern "C" int fp_shrink_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                      const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                                      uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                                      uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                      uint32_t *assign_out, uint8_t *state_out, uint32_t *blocker_out,
+                                      uint32_t *summary_out, uint8_t *hops_out, uint8_t *blocker_reason_out,
+                                      uint32_t *policy_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const size_t C = cs->n, N = ns->n;
+    if (N > FP_POLICY_MAX_NODES || n_var > 65535u || C > FP_SHRINK_MAX_CONTAINERS) return FP_EOVERFLOW;
+    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (n_var == 0) return FP_OK;
+    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out)) return FP_EINVAL;
+    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !state_out))
+        return FP_EINVAL;
+    if ((n_try && !try_order) || !summary_out) return FP_EINVAL;
+    if (C && assign_out == assign) return FP_EINVAL;
+    for (size_t i = 0; i < C; ++i)
+        if (assign[i] >= N && assign[i] != FP_NONE) return FP_EINVAL;
+    for (size_t i = 0; i < (size_t)n_var * n_try; ++i)
+        if (try_order[i] >= N && try_order[i] != FP_NONE) return FP_EINVAL;
+    const bool sp = domain && max_skew != 0u;  // otherwise domain is not read
+    for (size_t n = 0; sp && n < N; ++n)
+        if (domain[n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_shrink_dev d;
+    fp_shrink_policy_dev dp;
+    const int n = fp_shrink_policy_rows(cs, ns, assign, try_order, n_var, n_try, node_count, sp ? domain : nullptr,
+                                        assign_out, state_out, blocker_out, summary_out, hops_out, blocker_reason_out,
+                                        policy_out, &d, &dp, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    fp_shrink_policy pol;
+    pol.domain = dp.domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
+    pol.hops_out = dp.hops_out; pol.blocker_reason_out = dp.blocker_reason_out; pol.policy_out = dp.policy_out;
+    if (int rc = fp_dev_shrink_sweep_impl(c, &d.cs, &d.ns, d.assign, d.try_order, n_var, n_try, strategy,
+                                          preferred_labels, d.node_count, d.assign_out, d.state_out, d.blocker_out,
+                                          d.summary, pol))
+        return rc;
+    return copy_back_all(c, rows, n);
+}
+
 // the drain sweep under the policy (SPEC.md 2.15, fp_drain.hip).  relax_mask is a host array in both entries
 extern "C" int fp_dev_drain_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
                                          const uint32_t *group, uint32_t n_cand, uint32_t strategy,

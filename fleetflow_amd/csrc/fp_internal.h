@@ -192,14 +192,27 @@ int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
                             const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
                             uint32_t *summary_out, const fp_drain_policy &pol = fp_drain_policy());
 
+// what a scale-in sweep under the policy has besides the sweep's own arguments (SPEC.md 2.17).  Not ABI: the
+// exports of fp_ctx.hip fill it in.  domain and the three results are device memory, relax_mask a HOST array
+struct fp_shrink_policy {
+    const uint32_t *domain = nullptr;      // [N]; null or max_skew == 0: no constraint
+    uint32_t max_skew = 0;
+    const uint32_t *relax_mask = nullptr;  // [n_hops]; null or n_hops == 0: no chain
+    uint32_t n_hops = 0;
+    uint8_t *hops_out = nullptr;           // [n_var][C] or null
+    uint8_t *blocker_reason_out = nullptr; // [n_var][N] or null
+    uint32_t *policy_out = nullptr;        // [n_var][FP_SHRINK_POLICY_WORDS] or null
+};
 // scale-in sweep (fp_shrink.hip, SPEC.md 2.16); every pointer is device memory.  assign and try_order values out
-// of range are found on the device (FP_EINVAL in the context's error word, nothing written)
+// of range are found on the device (FP_EINVAL in the context's error word, nothing written).  pol (SPEC.md 2.17):
+// the spread constraint, the fallback chain and the three further results; domain and the results are device
+// memory, relax_mask a host array
 // the most containers a call takes: the scan's positions, rounded up to a whole step, stay below 2^31
 constexpr uint32_t FP_SHRINK_MAX_CONTAINERS = 0x7FFF0000u;
 int fp_dev_shrink_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
                              const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
                              uint32_t preferred, const uint32_t *node_count, uint32_t *assign_out, uint8_t *state_out,
-                             uint32_t *blocker_out, uint32_t *summary_out);
+                             uint32_t *blocker_out, uint32_t *summary_out, const fp_shrink_policy &pol = fp_shrink_policy());
 
 // scale-out sweep (fp_grow.hip, SPEC.md 2.12); every pointer is device memory, max_new a host value.  A t_max
 // value above max_new is found on the device (FP_EINVAL in the context's error word, nothing written)

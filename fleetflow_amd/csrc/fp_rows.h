@@ -185,6 +185,29 @@ static inline int fp_shrink_rows(const fp_containers *cs, const fp_nodes *ns, co
     return n;
 }
 
+// fp_shrink_sweep_policy (SPEC.md 2.17): fp_shrink_sweep's rows, then the domains (absent without a constraint)
+// and the three further results the caller may ask for.  relax_mask stays on the host
+struct fp_shrink_policy_dev {
+    const uint32_t *domain;
+    uint8_t *hops_out, *blocker_reason_out;
+    uint32_t *policy_out;
+};
+static inline int fp_shrink_policy_rows(const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                        const uint32_t *try_order, uint32_t n_var, uint32_t n_try,
+                                        const uint32_t *node_count, const uint32_t *domain, uint32_t *assign_out,
+                                        uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out,
+                                        uint8_t *hops_out, uint8_t *blocker_reason_out, uint32_t *policy_out,
+                                        fp_shrink_dev *d, fp_shrink_policy_dev *dp, fp_row *r) {
+    const size_t V = n_var;
+    int n = fp_shrink_rows(cs, ns, assign, try_order, n_var, n_try, node_count, assign_out, state_out, blocker_out,
+                           summary_out, d, r);
+    r[n++] = fp_row_in(domain, (size_t)ns->n, &dp->domain);
+    r[n++] = fp_row_opt(hops_out, V * cs->n, &dp->hops_out);
+    r[n++] = fp_row_opt(blocker_reason_out, V * ns->n, &dp->blocker_reason_out);
+    r[n++] = fp_row_opt(policy_out, V * FP_SHRINK_POLICY_WORDS, &dp->policy_out);
+    return n;
+}
+
 // fp_grow_sweep: the requests, the reasons (absent without a mask), the templates; then the two results
 struct fp_grow_dev {
     fp_containers cs;

@@ -767,12 +767,19 @@ class ShrinkVariant:
     n_moves: int = 0                       # committed moves; a service that moved twice counts twice
     moved_cpu_m: int = 0                   # what the moved services ask for in sum
     moved_mem_mib: int = 0
+    # under the policy (SPEC.md 2.17, shrink_stage(under_policy=True)); unset otherwise.  A server the bound rule
+    # kept has no blocker service: its ``stayed`` entry is (server, None)
+    relaxed: dict[str, list[str]] = field(default_factory=dict)  # moved service -> label keys given up (Plan.relaxed)
+    stayed_reason: dict[str, str] = field(default_factory=dict)  # server that stayed -> "NOFIT" / "SKEW" / "BOUND"
+    skew_before: int | None = None         # max - min of the services per eligible domain on the live state
+    skew_after: int | None = None          # the same on the state the variant leaves
 
 
 @dataclass
 class ShrinkReport:
     """``shrink_stage``'s answer: one ShrinkVariant per release order, every one computed independently from the
-    same live state under the strategy and preferred labels named here.  ``best`` indexes the variant with the
+    same live state under the strategy and preferred labels named here, and with ``under_policy`` under the
+    spread constraint and the fallback chain named here.  ``best`` indexes the variant with the
     most released servers, then the fewest moved services, then the lowest index (None without variants), and
     ``plan`` is the plan that variant leaves."""
     stage: str
@@ -782,6 +789,11 @@ class ShrinkReport:
     variants: list[ShrinkVariant] = field(default_factory=list)
     best: int | None = None
     plan: Plan | None = None
+    # the guarantees the moves were held to (SPEC.md 2.17); unset without under_policy
+    spread_topology_key: str | None = None
+    spread_max_skew: int | None = None
+    fallback_relax_order: list[str] = field(default_factory=list)
+    fallback_max_hops: int | None = None
 
 
 SHRINK_RULES = ("fewest", "lightest", "last")
@@ -811,7 +823,7 @@ def shrink_order(rule: str, nodes: list[Server], cont, assign, keep=()) -> list[
 
 
 def shrink_stage(flow: Flow, stage_name: str, plan: Plan, orders=None, keep=None, planner: Planner | None = None,
-                 policy: PlacementPolicy | None = None) -> ShrinkReport:
+                 policy: PlacementPolicy | None = None, under_policy: bool = False) -> ShrinkReport:
     """"Which servers can I hand back, and what has to move so that I can?" for a stage that runs as ``plan``
     says (SPEC.md 2.16): one ``Planner.shrink_sweep`` over the live tables of ``live_tables``, one variant per
     entry of ``orders``.  An entry is a rule name (``shrink_order``: "fewest", "lightest", "last") or an explicit
@@ -821,16 +833,32 @@ def shrink_stage(flow: Flow, stage_name: str, plan: Plan, orders=None, keep=None
     A variant tries its servers one after the other on the state its earlier releases left: the server's
     services are visited in the order (cpu desc, mem desc, stage order) and go to the remaining schedulable
     servers under the strategy and preferred labels of ``policy`` or, without one, of the policy the plan was
-    made under; if one of them finds no server the attempt is undone and the server stays.  The policy's spread
-    constraint, fallback chain and quota are not applied to moves."""
+    made under; if one of them finds no server the attempt is undone and the server stays.  By default the
+    policy's spread constraint and fallback chain are not applied to moves: a move is a SPEC.md 2.6 placement.
+
+    ``under_policy=True`` applies them (SPEC.md 2.17, one ``Planner.shrink_sweep_policy`` call): the spread
+    constraint and the chain of ``policy`` or, without one, of the policy the plan was made under.  The domain
+    counts leave the released servers and the tried one out, a domain counts while it keeps a target, servers
+    without the topology key take no move (``replan_domains``), and a release that would take the stage out of
+    ``max_skew``, or further out, is refused although every move passed (the bound rule).  A quota has nothing
+    to test: a move releases and retakes the same request.  The variants then carry ``relaxed``,
+    ``stayed_reason``, ``skew_before`` and ``skew_after``, the report the guarantees it ran under, and the best
+    order's plan ``relaxed`` for the services it moved."""
     import dataclasses
-    from ._lib import (SHRINK_FAILED, SHRINK_MOVED_CPU, SHRINK_MOVED_MEM, SHRINK_MOVES, SHRINK_STATE_FAILED,
-                       SHRINK_STATE_RELEASED, SHRINK_TRIED)
+    from ._lib import (REASON_SKEW, SHRINK_FAILED, SHRINK_MOVED_CPU, SHRINK_MOVED_MEM, SHRINK_MOVES, SHRINK_SKEW_AFTER,
+                       SHRINK_SKEW_BEFORE, SHRINK_STATE_FAILED, SHRINK_STATE_RELEASED, SHRINK_TRIED)
     p = planner or default_planner()
     names, nodes, cont, live, assign, count, strategy, pmask = live_tables(flow, stage_name, plan, policy)
     pol_pref = policy.preferred if policy is not None else list(plan.preferred)
     keep = list(keep or [])
     report = ShrinkReport(stage_name, strategy, pol_pref, keep)
+    pol = None
+    if under_policy:
+        pol = policy if policy is not None else _plan_policy(plan)
+        if pol.spread is not None:
+            report.spread_topology_key, report.spread_max_skew = pol.spread
+        if pol.fallback:
+            report.fallback_relax_order, report.fallback_max_hops = list(pol.fallback_relax_order), pol.fallback_max_hops
     slugs = [nd.slug for nd in nodes]
     index = {s: n for n, s in enumerate(slugs)}
     unknown = [s for s in keep if s not in index]
@@ -853,22 +881,50 @@ def shrink_stage(flow: Flow, stage_name: str, plan: Plan, orders=None, keep=None
     try_order = np.full((len(rows), n_try), NONE, np.uint32)
     for i, r in enumerate(rows):
         try_order[i, :len(r)] = r
-    out, state, blocker, summary = p.shrink_sweep(cont, live, assign, try_order, strategy if strategy is not None else 0,
-                                                  pmask, count)
+    hops = why = prows = None
+    if pol is None:
+        out, state, blocker, summary = p.shrink_sweep(cont, live, assign, try_order,
+                                                      strategy if strategy is not None else 0, pmask, count)
+    else:
+        domain, max_skew = None, 0
+        if pol.spread is not None:
+            domain, has_key = replan_domains(nodes, pol.spread[0])
+            max_skew = pol.spread[1]
+            live = (*live[:4], [s if k else 0 for s, k in zip(live[4], has_key)])
+        relax = [_stage_labels(names, flow, nodes, pol_pref).key_mask(k) for k in pol.fallback]
+        out, state, blocker, summary, hops, why, prows = p.shrink_sweep_policy(
+            cont, live, assign, try_order, strategy if strategy is not None else 0, pmask, count, domain=domain,
+            max_skew=max_skew, relax_mask=relax)
     visit = sorted(range(len(names)), key=lambda v: (-cont[0][v], -cont[1][v], v))
     for i, r in enumerate(rows):
         row = [int(x) for x in summary[i]]
         freed = [slugs[n] for n in dict.fromkeys(r) if int(state[i][n]) == SHRINK_STATE_RELEASED]
         moves = [(names[v], slugs[assign[v]], slugs[int(out[i][v])]) for v in visit if int(out[i][v]) != assign[v]]
-        stayed = [(slugs[n], names[int(blocker[i][n])]) for n in dict.fromkeys(r) if int(state[i][n]) == SHRINK_STATE_FAILED]
-        report.variants.append(ShrinkVariant(labels[i], [slugs[n] for n in r], freed, moves, stayed, row[SHRINK_TRIED],
-                                             row[SHRINK_FAILED], row[SHRINK_MOVES], row[SHRINK_MOVED_CPU],
-                                             row[SHRINK_MOVED_MEM]))
+        held = [n for n in dict.fromkeys(r) if int(state[i][n]) == SHRINK_STATE_FAILED]
+        stayed = [(slugs[n], names[int(blocker[i][n])] if int(blocker[i][n]) != NONE else None) for n in held]
+        var = ShrinkVariant(labels[i], [slugs[n] for n in r], freed, moves, stayed, row[SHRINK_TRIED],
+                            row[SHRINK_FAILED], row[SHRINK_MOVES], row[SHRINK_MOVED_CPU], row[SHRINK_MOVED_MEM])
+        if pol is not None:
+            for n in held:
+                var.stayed_reason[slugs[n]] = ("BOUND" if int(blocker[i][n]) == NONE
+                                               else "SKEW" if int(why[i][n]) == REASON_SKEW else "NOFIT")
+            for v in visit:
+                if int(out[i][v]) != assign[v] and int(hops[i][v]):
+                    required = {lab.split("=", 1)[0] for lab in flow.services.get(names[v], Service()).labels}
+                    var.relaxed[names[v]] = [key for key in pol.fallback[:int(hops[i][v])] if key in required]
+            if pol.spread is not None:
+                var.skew_before, var.skew_after = int(prows[i][SHRINK_SKEW_BEFORE]), int(prows[i][SHRINK_SKEW_AFTER])
+        report.variants.append(var)
     report.best = min(range(len(rows)), key=lambda i: (-len(report.variants[i].released), len(report.variants[i].moves), i))
+    best = report.variants[report.best]
     assignment = dict(plan.assignment)
-    for svc, _, dst in report.variants[report.best].moves:
+    for svc, _, dst in best.moves:
         assignment[svc] = dst
     report.plan = dataclasses.replace(plan, assignment=assignment)
+    if pol is not None:  # a moved service carries the keys its last move gave up, and no others
+        relaxed = {svc: keys for svc, keys in plan.relaxed.items() if svc not in {m[0] for m in best.moves}}
+        relaxed.update(best.relaxed)
+        report.plan = dataclasses.replace(report.plan, relaxed=relaxed)
     return report
 
 

@@ -23,7 +23,9 @@ the services of each new server indented under it where the candidate was detail
 
 ``format_shrink_report`` prints a scale-in sweep (SPEC.md 2.16, ``flow.shrink_stage``), one block per release order,
 and ``shrink_report_to_json`` / ``shrink_report_from_json`` carry it as ``{stage, placement: {strategy, preferred},
-keep, best, plan, variants: [{name, order, released, moves, stayed, ...}]}`` with ``plan`` in ``plan_to_json``'s form.
+keep, best, plan, variants: [{name, order, released, moves, stayed, ...}]}`` with ``plan`` in ``plan_to_json``'s form;
+a sweep under the policy (SPEC.md 2.17) adds ``placement.spread`` / ``placement.fallback`` and per variant ``relaxed``,
+``stayed_reason``, ``skew_before`` and ``skew_after``, each only when set.
 
 ``format_replan_report`` prints a re-plan (SPEC.md 2.13, ``flow.replan_stage``): one line of counts, then the
 moves, the new and the lost services, and ``replan_report_to_json`` / ``replan_report_from_json`` carry it as
@@ -159,7 +161,10 @@ def format_shrink_report(report: ShrinkReport) -> str:
     """One line per release order, ``shrink <name>: <r> of <t> servers released, <m> services move (<cpu>m cpu,
     <mem> MiB), <f> attempts undone``, marked ``(best)`` where it is, with the released servers
     (``released: a, b``), the moves (``service: from -> to``) and the servers that stayed (``server: stays
-    (blocked by service)``) indented under it."""
+    (blocked by service)``) indented under it.  What a sweep under the policy adds (SPEC.md 2.17) is printed only
+    where it is set: ``(relaxed: class)`` behind a move, ``stays (blocked by service, SKEW)``, ``stays (bound
+    rule: ...)`` for a server whose services all found a place and whose release the spread constraint refuses,
+    and a ``spread:`` line with the skew before and after."""
     lines = []
     for i, v in enumerate(report.variants):
         lines.append(f"shrink {v.name}: {len(v.released)} of {v.tried} servers released, {len(v.moves)} services move "
@@ -167,16 +172,40 @@ def format_shrink_report(report: ShrinkReport) -> str:
                      + (" (best)" if i == report.best else ""))
         if v.released:
             lines.append(f"  released: {', '.join(v.released)}")
-        lines += [f"  {svc}: {src} -> {dst}" for svc, src, dst in v.moves]
-        lines += [f"  {srv}: stays (blocked by {svc})" for srv, svc in v.stayed]
+        lines += [f"  {svc}: {src} -> {dst}" + (f" (relaxed: {', '.join(v.relaxed[svc])})" if v.relaxed.get(svc) else "")
+                  for svc, src, dst in v.moves]
+        for srv, svc in v.stayed:
+            why = v.stayed_reason.get(srv)
+            if svc is None:
+                lines.append(f"  {srv}: stays (bound rule: its release would leave the skew over "
+                             f"{report.spread_topology_key} above max_skew {report.spread_max_skew} and above what it is)")
+            else:
+                lines.append(f"  {srv}: stays (blocked by {svc}" + (f", {why}" if why else "") + ")")
+        if v.skew_before is not None:
+            lines.append(f"  spread: skew over {report.spread_topology_key} {v.skew_before} -> {v.skew_after} "
+                         f"(max_skew {report.spread_max_skew})")
     return "\n".join(lines)
 
 
+_SHRINK_POLICY_FIELDS = ("relaxed", "stayed_reason", "skew_before", "skew_after")
+
+
 def shrink_report_to_json(report: ShrinkReport, indent: int | None = None) -> str:
+    variants = []
+    for v in report.variants:
+        row = asdict(v)
+        for key in _SHRINK_POLICY_FIELDS:  # SPEC.md 2.17: only when set
+            if not row[key] and row[key] != 0:
+                del row[key]
+        variants.append(row)
     d = {"stage": report.stage, "placement": {"strategy": report.strategy, "preferred": report.preferred},
          "keep": report.keep, "best": report.best,
          "plan": None if report.plan is None else json.loads(plan_to_json(report.plan)),
-         "variants": [asdict(v) for v in report.variants]}
+         "variants": variants}
+    if report.spread_topology_key is not None:
+        d["placement"]["spread"] = {"topology_key": report.spread_topology_key, "max_skew": report.spread_max_skew}
+    if report.fallback_relax_order:
+        d["placement"]["fallback"] = {"relax_order": report.fallback_relax_order, "max_hops": report.fallback_max_hops}
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
@@ -185,11 +214,17 @@ def shrink_report_from_json(text: str) -> ShrinkReport:
     pol = d.get("placement") or {}
     variants = [ShrinkVariant(v["name"], list(v["order"]), list(v["released"]), [tuple(m) for m in v["moves"]],
                               [tuple(x) for x in v["stayed"]], v.get("tried", 0), v.get("failed", 0), v.get("n_moves", 0),
-                              v.get("moved_cpu_m", 0), v.get("moved_mem_mib", 0)) for v in d.get("variants") or []]
+                              v.get("moved_cpu_m", 0), v.get("moved_mem_mib", 0),
+                              {k: list(x) for k, x in (v.get("relaxed") or {}).items()},
+                              dict(v.get("stayed_reason") or {}), v.get("skew_before"), v.get("skew_after"))
+                for v in d.get("variants") or []]
     plan = d.get("plan")
     return ShrinkReport(d["stage"], pol.get("strategy"), list(pol.get("preferred") or []), list(d.get("keep") or []),
                         variants, d.get("best"),
-                        None if plan is None else plan_from_json(json.dumps(plan, ensure_ascii=False)))
+                        None if plan is None else plan_from_json(json.dumps(plan, ensure_ascii=False)),
+                        (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"),
+                        list((pol.get("fallback") or {}).get("relax_order") or []),
+                        (pol.get("fallback") or {}).get("max_hops"))
 
 
 def format_replan_report(report: Replan) -> str:

@@ -730,6 +730,48 @@ class Planner:
                                       _arg(blocker), _arg(summary)), "fp_shrink_sweep")
         return out, state, blocker, summary
 
+    def shrink_sweep_policy(self, cont, nodes, assign, try_order, strategy=0, preferred=0, node_count=None, *,
+                            domain=None, max_skew=0, relax_mask=()):
+        """The scale-in sweep under the policy (SPEC.md 2.17, fp_shrink_sweep_policy): ``shrink_sweep`` with every
+        move held to the spread constraint (``domain`` [N] ids below 64 and ``max_skew``; None or 0 = none,
+        ``domain`` is then not read) and the fallback chain (``relax_mask``: per hop the label bits it gives
+        up, at most 4; empty = none).  The domain counts leave the released nodes and the attempt's own node
+        out, a domain is eligible while it holds a target, and under a constraint an attempt whose containers
+        all found a target commits only when the skew it leaves is within ``max_skew`` or no larger than before
+        (the bound rule).  There is no quota: a move releases and retakes the same request.  Returns (assign_out
+        [n_var, C], state [n_var, N], blocker [n_var, N], summary [n_var, 8], hops [n_var, C], blocker_reason
+        [n_var, N] with REASON_SKEW beside REASON_NOFIT, policy_rows [n_var, 4]); the policy rows' word indices
+        are _lib.SHRINK_FAILED_SKEW, .."""
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
+        asg = _u32(assign)
+        tro = _u32(try_order)
+        self._need(tro.ndim == 2, "try_order must be [n_var, n_try]")
+        n_var, n_try = tro.shape
+        nc = _u32(node_count) if node_count is not None else None
+        dom = _u32(domain) if domain is not None else None
+        strategy, max_skew = strategy_id(strategy), int(max_skew)
+        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
+        self._need(asg.size == C, "assign must hold C entries")
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        self._need(dom is None or dom.size == N, "domain must hold N entries")
+        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
+        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+        rm = _u32(relax) if relax else None
+        out = np.empty((n_var, C), np.uint32)
+        state = np.empty((n_var, N), np.uint8)
+        blocker = np.empty((n_var, N), np.uint32)
+        summary = np.empty((n_var, _lib.SHRINK_WORDS), np.uint32)
+        hops = np.empty((n_var, C), np.uint8)
+        why = np.empty((n_var, N), np.uint8)
+        rows = np.empty((n_var, _lib.SHRINK_POLICY_WORDS), np.uint32)
+        cs, ns = _pair(cont, nodes)
+        check(self._L.fp_shrink_sweep_policy(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(tro), n_var, n_try,
+                                             strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(dom), max_skew,
+                                             _arg(rm), len(relax), _arg(out), _arg(state), _arg(blocker), _arg(summary),
+                                             _arg(hops), _arg(why), _arg(rows)), "fp_shrink_sweep_policy")
+        return out, state, blocker, summary, hops, why, rows
+
     def grow_sweep(self, cont, reason, templates, max_new, reason_mask=1 << _lib.REASON_NOFIT, t_max=None,
                    want_assign=False):
         """Scale-out sweep (SPEC.md 2.12, fp_grow_sweep): the pending containers are those of ``cont`` whose
@@ -857,6 +899,57 @@ class Planner:
             self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(try_order_t), n_var, n_try, strategy,
             int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(assign_out_t), _arg(state_t), _arg(blocker_t),
             _arg(summary_t)), "fp_dev_shrink_sweep"))
+
+    def dev_shrink_sweep_policy(self, cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t,
+                                strategy=0, preferred=0, count_t=None, blocker_t=None, *, domain_t=None, max_skew=0,
+                                relax_mask=(), hops_t=None, blocker_reason_t=None, policy_t=None):
+        """fp_dev_shrink_sweep_policy on device tensors: ``dev_shrink_sweep``'s arguments, then ``domain_t`` [N] or
+        None, ``max_skew``, ``relax_mask`` (host values, at most 4) and the optional results ``hops_t`` [n_var * C]
+        uint8, ``blocker_reason_t`` [n_var * N] uint8 and ``policy_t`` [n_var * 4].  An assign, try_order or
+        domain value out of range is found on the device: nothing is written and sync() raises FP_EINVAL."""
+        C, N, n_var, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_var), strategy_id(strategy)
+        max_skew = int(max_skew)
+        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
+        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
+                   "every container tensor must hold C 32-bit entries")
+        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
+                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
+                   "every node tensor must hold N entries (schedulable N bytes)")
+        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
+        self._need(0 <= n_var <= 0xFFFFFFFF, "n_var must be a u32")
+        self._need(try_order_t.element_size() == 4 and (try_order_t.numel() % n_var == 0 if n_var
+                                                        else try_order_t.numel() == 0),
+                   "try_order_t must hold n_var rows of 32-bit entries")
+        n_try = try_order_t.numel() // n_var if n_var else 0
+        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
+                   "count_t must hold N 32-bit entries")
+        self._need(domain_t is None or (domain_t.numel() == N and domain_t.element_size() == 4),
+                   "domain_t must hold N 32-bit entries")
+        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
+        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+        self._need(assign_out_t.numel() == n_var * C and assign_out_t.element_size() == 4,
+                   "assign_out_t must hold n_var * C 32-bit entries")
+        self._need(state_t.numel() == n_var * N and state_t.element_size() == 1, "state_t must hold n_var * N bytes")
+        self._need(blocker_t is None or (blocker_t.numel() == n_var * N and blocker_t.element_size() == 4),
+                   "blocker_t must hold n_var * N 32-bit entries")
+        self._need(summary_t.numel() == n_var * _lib.SHRINK_WORDS and summary_t.element_size() == 4,
+                   "summary_t must hold n_var * 8 32-bit entries")
+        self._need(hops_t is None or (hops_t.numel() == n_var * C and hops_t.element_size() == 1),
+                   "hops_t must hold n_var * C bytes")
+        self._need(blocker_reason_t is None or (blocker_reason_t.numel() == n_var * N
+                                                and blocker_reason_t.element_size() == 1),
+                   "blocker_reason_t must hold n_var * N bytes")
+        self._need(policy_t is None or (policy_t.numel() == n_var * _lib.SHRINK_POLICY_WORDS
+                                        and policy_t.element_size() == 4),
+                   "policy_t must hold n_var * 4 32-bit entries")
+        rm = _u32(relax) if relax else None  # read during the call
+        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
+        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
+        self._dev(lambda: check(self._L.fp_dev_shrink_sweep_policy(
+            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(try_order_t), n_var, n_try, strategy,
+            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(domain_t), max_skew, _arg(rm), len(relax),
+            _arg(assign_out_t), _arg(state_t), _arg(blocker_t), _arg(summary_t), _arg(hops_t), _arg(blocker_reason_t),
+            _arg(policy_t)), "fp_dev_shrink_sweep_policy"))
 
     def dev_drain_sweep_policy(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t,
                                strategy=0, preferred=0, count_t=None, *, domain_t=None, max_skew=0, relax_mask=(),

@@ -36,6 +36,9 @@
  *   fp_shrink_sweep   <- new: the servers a live plan can give back when they are tried in a given order, for
  *                        many orders at once: the `drain` state applied server after server, each release on
  *                        the state the earlier ones left  crates/fleetflow-controlplane/src/model.rs:435-442
+ *   fp_shrink_sweep_policy <- new: the same sweep with every move held to the policy's SpreadConstraint and
+ *                        FallbackPolicy (model.rs:47-63) and every release to the bound rule: a server is given
+ *                        back only if that leaves the skew within max_skew or no larger than it was
  *   fp_grow_sweep     <- new: the new servers of each template (a plan string's size,
  *                        crates/fleetflow-cloud-sakura/src/provider.rs:15-30, with the ServerLabels /
  *                        ServerCapacity a new server would carry, crates/fleetflow-controlplane/src/model.rs:399-419)
@@ -448,6 +451,39 @@ int fp_shrink_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, 
                     const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
                     uint32_t preferred_labels, const uint32_t *node_count, uint32_t *assign_out, uint8_t *state_out,
                     uint32_t *blocker_out, uint32_t *summary_out);
+/* The scale-in sweep under the policy (SPEC.md 2.17): fp_shrink_sweep with every move held to the tenant's spread
+ * constraint (domain[n] < FP_SPREAD_MAX_DOMAINS, max_skew; fp_place_policy_spread's meanings) and fallback chain
+ * (relax_mask[n_hops], n_hops <= FP_FALLBACK_MAX_HOPS; fp_place_policy_fallback's).  There is no quota input: a
+ * move releases and retakes the same request.  An attempt on n is one fp_place_policy_fallback call over the
+ * containers now on n, on the variant's current table with n and the released nodes unschedulable and their
+ * node_count 0, cut at its first rejected container (the BLOCKER, whose reason is FP_REASON_NOFIT or
+ * FP_REASON_SKEW as in fp_drain_sweep_policy).  A domain counts for the minimum while it holds a target of the
+ * attempt.  BOUND RULE (under a spread constraint only): with skew(S) = max - min of the per-domain sums of the
+ * running node_count over the unreleased nodes, taken over the domains that hold a schedulable unreleased node (0
+ * without one), an attempt whose containers all found a target commits iff
+ *     skew(after) <= max_skew || skew(after) <= skew(before)
+ * where `before` is the state before the attempt (n counts) and `after` the state the commit would leave (n
+ * released); otherwise it is undone like any failure, with blocker FP_NONE and reason FP_REASON_SKEW.
+ *   hops_out           [n_var][c->n]      nullable: the hop of the container's last committed move, else 0
+ *   blocker_reason_out [n_var][nodes->n]  nullable: FP_REASON_NOFIT / FP_REASON_SKEW for a node in state FAILED,
+ *                                         else 0
+ *   policy_out         [n_var][FP_SHRINK_POLICY_WORDS]  nullable:
+ *     FAILED_SKEW  undone attempts whose reason is SKEW (blocker or bound rule)
+ *     RELAXED      committed moves at a hop >= 1, counted like MOVES
+ *     SKEW_BEFORE, SKEW_AFTER  skew of the base and of the final state; 0 without a constraint
+ * domain == NULL or max_skew == 0: no constraint and domain is not read; relax_mask == NULL or n_hops == 0: no
+ * chain; with neither the four results of fp_shrink_sweep are bit for bit that call's, hops_out and policy_out are
+ * zeros and blocker_reason_out is FP_REASON_NOFIT on the FAILED nodes.  Errors: fp_shrink_sweep's, and FP_EINVAL
+ * for n_hops > FP_FALLBACK_MAX_HOPS or (with max_skew != 0) any domain[n] >= FP_SPREAD_MAX_DOMAINS; on any error
+ * nothing is written. */
+enum { FP_SHRINK_FAILED_SKEW, FP_SHRINK_RELAXED, FP_SHRINK_SKEW_BEFORE, FP_SHRINK_SKEW_AFTER, /* words 0 to 3 */
+       FP_SHRINK_POLICY_WORDS /* 4 */ };
+int fp_shrink_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                           const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                           uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                           uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
+                           uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out, uint8_t *hops_out,
+                           uint8_t *blocker_reason_out, uint32_t *policy_out);
 /* Scale-out sweep (SPEC.md 2.12): "what do I have to add?", asked of every server template at once.  The pending
  * containers are those whose reason's bit is set in reason_mask (fp_explain_batch's convention; reason_mask == 0
  * selects every container and reason is not read and may be NULL).  Candidate k is a template: a new server has
@@ -628,6 +664,16 @@ int fp_dev_shrink_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nod
                         const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
                         uint32_t preferred_labels, const uint32_t *node_count, uint32_t *assign_out,
                         uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out);
+/* As fp_shrink_sweep_policy on device pointers (every output included; relax_mask stays a HOST array of n_hops
+ * words: the masks go to the kernel by value); n_hops above FP_FALLBACK_MAX_HOPS is returned directly.  An assign,
+ * try_order or domain value out of range is found on the device before any store: nothing is written and
+ * fp_ctx_sync() reports FP_EINVAL.  The workspace is fp_dev_shrink_sweep's. */
+int fp_dev_shrink_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                               const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                               uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                               uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
+                               uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out, uint8_t *hops_out,
+                               uint8_t *blocker_reason_out, uint32_t *policy_out);
 /* As fp_grow_sweep on device pointers (max_new stays a host value: the kernel's geometry follows it, nothing is
  * read back).  A t_max[k] > max_new is found on the device before any store: nothing is written and fp_ctx_sync()
  * reports FP_EINVAL.  The call takes 28 bytes per container plus the sort's scratch from the context's workspace. */

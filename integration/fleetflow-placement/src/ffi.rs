@@ -75,6 +75,12 @@ pub const FP_DRAIN_RELAXED: usize = 1;
 pub const FP_DRAIN_SKEW_BEFORE: usize = 2;
 pub const FP_DRAIN_SKEW_AFTER: usize = 3;
 pub const FP_DRAIN_POLICY_WORDS: usize = 4;
+// the scale-in sweep under the policy (SPEC.md 2.17): the word indices of a variant's policy row
+pub const FP_SHRINK_FAILED_SKEW: usize = 0;
+pub const FP_SHRINK_RELAXED: usize = 1;
+pub const FP_SHRINK_SKEW_BEFORE: usize = 2;
+pub const FP_SHRINK_SKEW_AFTER: usize = 3;
+pub const FP_SHRINK_POLICY_WORDS: usize = 4;
 // scale-out sweep (SPEC.md 2.12): the word indices of a candidate's summary row, and the most new servers
 pub const FP_GROW_PENDING: usize = 0;
 pub const FP_GROW_PLACED: usize = 1;
@@ -272,6 +278,12 @@ unsafe extern "C" {
                            try_order: *const u32, n_var: u32, n_try: u32, strategy: u32, preferred_labels: u32,
                            node_count: *const u32, assign_out: *mut u32, state_out: *mut u8, blocker_out: *mut u32,
                            summary_out: *mut u32) -> c_int;
+    pub fn fp_shrink_sweep_policy(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes,
+                                  assign: *const u32, try_order: *const u32, n_var: u32, n_try: u32, strategy: u32,
+                                  preferred_labels: u32, node_count: *const u32, domain: *const u32, max_skew: u32,
+                                  relax_mask: *const u32, n_hops: u32, assign_out: *mut u32, state_out: *mut u8,
+                                  blocker_out: *mut u32, summary_out: *mut u32, hops_out: *mut u8,
+                                  blocker_reason_out: *mut u8, policy_out: *mut u32) -> c_int;
     pub fn fp_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32, n_cand: u32,
                          t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32, t_max: *const u32,
                          max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
@@ -340,6 +352,13 @@ unsafe extern "C" {
                                assign: *const u32, try_order: *const u32, n_var: u32, n_try: u32, strategy: u32,
                                preferred_labels: u32, node_count: *const u32, assign_out: *mut u32,
                                state_out: *mut u8, blocker_out: *mut u32, summary_out: *mut u32) -> c_int;
+    pub fn fp_dev_shrink_sweep_policy(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes,
+                                      assign: *const u32, try_order: *const u32, n_var: u32, n_try: u32,
+                                      strategy: u32, preferred_labels: u32, node_count: *const u32,
+                                      domain: *const u32, max_skew: u32, relax_mask: *const u32, n_hops: u32,
+                                      assign_out: *mut u32, state_out: *mut u8, blocker_out: *mut u32,
+                                      summary_out: *mut u32, hops_out: *mut u8, blocker_reason_out: *mut u8,
+                                      policy_out: *mut u32) -> c_int;
     pub fn fp_dev_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
                              n_cand: u32, t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32,
                              t_max: *const u32, max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;

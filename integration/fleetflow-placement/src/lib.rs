@@ -196,6 +196,48 @@ impl Planner {
         Ok((out, state, blocker, rows))
     }
 
+    /// The scale-in sweep under the policy (SPEC.md 2.17, fleetplace.h `fp_shrink_sweep_policy`): `shrink_sweep`
+    /// with every move held to the spread constraint (`domain` ids below `ffi::FP_SPREAD_MAX_DOMAINS` and
+    /// `max_skew`; None or 0 = none) and the fallback chain (`relax_mask`: per hop the label bits it gives up, at
+    /// most `ffi::FP_FALLBACK_MAX_HOPS`; empty = none), and every release to the bound rule.  Returns per variant
+    /// (the final node and the hop of the last move per container, the state, the blocker and the blocker's
+    /// reason per node, its row of `ffi::FP_SHRINK_WORDS` and its row of `ffi::FP_SHRINK_POLICY_WORDS` words).
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn shrink_sweep_policy(&mut self, c: &Containers, nodes: &Nodes, assign: &[u32], try_order: &[u32], n_try: u32,
+                               strategy: u32, preferred_labels: u32, node_count: Option<&[u32]>,
+                               domain: Option<&[u32]>, max_skew: u32, relax_mask: &[u32])
+                               -> Result<(Vec<u32>, Vec<u8>, Vec<u8>, Vec<u32>, Vec<u8>, Vec<[u32; ffi::FP_SHRINK_WORDS]>,
+                                          Vec<[u32; ffi::FP_SHRINK_POLICY_WORDS]>), PlanError> {
+        let (n, nn) = (c.cpu_m.len(), nodes.cpu_free.len());
+        let n_var = if n_try == 0 { 0 } else { try_order.len() / n_try as usize };
+        if !c.all_len(n) || !nodes.all_len(nn) || assign.len() != n || try_order.len() != n_var * n_try as usize
+            || n_var > u32::MAX as usize || node_count.map_or(false, |k| k.len() != nn)
+            || domain.map_or(false, |d| d.len() != nn) || relax_mask.len() > ffi::FP_FALLBACK_MAX_HOPS as usize {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        // the sweep reads the node table only: the mutable pointers of fp_nodes are never written through
+        let ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_ptr() as *mut u32,
+                                 mem_free: nodes.mem_free.as_ptr() as *mut u32, labels: nodes.labels.as_ptr(),
+                                 conflict_used: nodes.conflict_used.as_ptr() as *mut u32,
+                                 schedulable: nodes.schedulable.as_ptr() };
+        let (mut out, mut state, mut blocker) = (vec![0u32; n_var * n], vec![0u8; n_var * nn], vec![0u32; n_var * nn]);
+        let (mut hops, mut why) = (vec![0u8; n_var * n], vec![0u8; n_var * nn]);
+        let mut rows = vec![[0u32; ffi::FP_SHRINK_WORDS]; n_var];
+        let mut prows = vec![[0u32; ffi::FP_SHRINK_POLICY_WORDS]; n_var];
+        check(unsafe {
+            ffi::fp_shrink_sweep_policy(self.ctx, &cs, &ns, assign.as_ptr(), try_order.as_ptr(), n_var as u32, n_try,
+                                        strategy, preferred_labels, node_count.map_or(std::ptr::null(), |k| k.as_ptr()),
+                                        domain.map_or(std::ptr::null(), |d| d.as_ptr()), max_skew,
+                                        if relax_mask.is_empty() { std::ptr::null() } else { relax_mask.as_ptr() },
+                                        relax_mask.len() as u32, out.as_mut_ptr(), state.as_mut_ptr(),
+                                        blocker.as_mut_ptr(), rows.as_mut_ptr() as *mut u32, hops.as_mut_ptr(),
+                                        why.as_mut_ptr(), prows.as_mut_ptr() as *mut u32)
+        })?;
+        Ok((out, hops, state, blocker, why, rows, prows))
+    }
+
     /// The drain sweep under the policy (SPEC.md 2.15, fleetplace.h `fp_drain_sweep_policy`): `drain_sweep` with
     /// every move held to the spread constraint (`domain` ids below `ffi::FP_SPREAD_MAX_DOMAINS` and `max_skew`;
     /// None or 0 = none) and the fallback chain (`relax_mask`: per hop the label bits it gives up, at most
