@@ -60,6 +60,10 @@ GROW_PENDING, GROW_PLACED, GROW_OPENED, GROW_UNPLACEABLE, GROW_CAPPED = 0, 1, 2,
 GROW_LEFT_CPU, GROW_LEFT_MEM, GROW_FIRST_UNPLACED, GROW_WORDS = 5, 6, 7, 8
 GROW_FIELDS = ("pending", "placed", "opened", "unplaceable", "capped", "left_cpu", "left_mem", "first_unplaced")
 GROW_MAX_NEW = 8192
+# the scale-out sweep under the policy (SPEC.md 2.18): the word indices of a candidate's policy row, and their names
+GROW_ON_LIVE, GROW_RELAXED, GROW_STUCK_SKEW, GROW_STUCK_QUOTA, GROW_SKEW_BEFORE, GROW_SKEW_AFTER = 0, 1, 2, 3, 4, 5
+GROW_POLICY_WORDS = 8
+GROW_POLICY_FIELDS = ("on_live", "relaxed", "stuck_skew", "stuck_quota", "skew_before", "skew_after")
 # re-planning a running stage (SPEC.md 2.13): enum fp_change with its names in value order, and the word indices
 # of a scenario's summary row (words 0..4 count the change values)
 CHANGE_KEPT, CHANGE_NEW, CHANGE_MOVED, CHANGE_LOST, CHANGE_ABSENT = 0, 1, 2, 3, 4
@@ -192,6 +196,14 @@ SIGNATURES = {
                                  ct.c_uint32, u32p, u32p]),
     "fp_dev_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), vp, ct.c_uint32, ct.c_uint32, vp, vp, vp, vp,
                                      ct.c_uint32, vp, vp]),
+    "fp_grow_sweep_policy": (ct.c_int, [vp, ct.POINTER(FpContainers), u8p, ct.c_uint32, ct.POINTER(FpNodes), u32p,
+                                        ct.c_uint32, u32p, u32p, u32p, u32p, ct.c_uint32, ct.c_uint32, ct.c_uint32,
+                                        u32p, u32p, ct.c_uint32, u32p, ct.c_uint32, u32p, u32p, u32p, u32p, u32p,
+                                        u8p, u8p]),
+    # relax_mask, quota and quota_used (u32p) are host arrays in the device entry too
+    "fp_dev_grow_sweep_policy": (ct.c_int, [vp, ct.POINTER(FpContainers), vp, ct.c_uint32, ct.POINTER(FpNodes), vp,
+                                            ct.c_uint32, vp, vp, vp, vp, ct.c_uint32, ct.c_uint32, ct.c_uint32,
+                                            vp, vp, ct.c_uint32, u32p, ct.c_uint32, u32p, u32p, vp, vp, vp, vp, vp]),
     "fp_replan": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, u32p, ct.c_uint32, ct.c_uint32,
                              u32p, u32p, u8p, u8p, u32p]),
     "fp_replan_batch": (ct.c_int, [vp, ct.POINTER(FpBatch), u32p, u32p, u32p, u32p, u8p, u32p]),

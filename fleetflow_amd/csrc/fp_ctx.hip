@@ -1122,3 +1122,72 @@ extern "C" int fp_grow_sweep(fp_ctx *c, const fp_containers *cs, const uint8_t *
         return rc;
     return copy_back_all(c, rows, n);
 }
+
+// the scale-out sweep under the policy (SPEC.md 2.18, fp_grow.hip).  relax_mask, quota and quota_used are host
+// arrays in both entries
+extern "C" int fp_dev_grow_sweep_policy(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
+                                        const fp_nodes *ns, const uint32_t *node_count, uint32_t n_cand,
+                                        const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                                        const uint32_t *t_max, uint32_t max_new, uint32_t strategy,
+                                        uint32_t preferred_labels, const uint32_t *domain, const uint32_t *t_domain,
+                                        uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                        const uint32_t *quota, const uint32_t *quota_used, uint32_t *summary_out,
+                                        uint32_t *policy_out, uint32_t *assign_out, uint8_t *hops_out,
+                                        uint8_t *reason_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_grow_policy pol;
+    pol.node_count = node_count; pol.strategy = strategy; pol.preferred = preferred_labels;
+    pol.domain = domain; pol.t_domain = t_domain; pol.max_skew = max_skew;
+    pol.relax_mask = relax_mask; pol.n_hops = n_hops; pol.quota = quota; pol.quota_used = quota_used;
+    pol.policy_out = policy_out; pol.hops_out = hops_out; pol.reason_out = reason_out;
+    return fp_dev_done(c, fp_dev_grow_sweep_policy_impl(c, cs, reason, reason_mask, ns, n_cand, t_cpu, t_mem, t_labels,
+                                                        t_max, max_new, summary_out, assign_out, pol));
+}
+
+extern "C" int fp_grow_sweep_policy(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
+                                    const fp_nodes *ns, const uint32_t *node_count, uint32_t n_cand,
+                                    const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                                    const uint32_t *t_max, uint32_t max_new, uint32_t strategy,
+                                    uint32_t preferred_labels, const uint32_t *domain, const uint32_t *t_domain,
+                                    uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                    const uint32_t *quota, const uint32_t *quota_used, uint32_t *summary_out,
+                                    uint32_t *policy_out, uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const size_t C = cs->n, N = ns->n;
+    if (n_cand > 65535u || max_new > FP_GROW_MAX_NEW || N + max_new > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
+    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (reason_mask && !reason) return FP_EINVAL;
+    const bool sp = t_domain && max_skew != 0u;  // otherwise neither domain array is read
+    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict)) return FP_EINVAL;
+    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable)) return FP_EINVAL;
+    if (N && sp && !domain) return FP_EINVAL;
+    if (n_cand && (!t_cpu || !t_mem || !t_labels || !summary_out)) return FP_EINVAL;
+    for (size_t k = 0; k < n_cand; ++k)
+        if ((t_max && t_max[k] > max_new) || (sp && t_domain[k] >= (uint32_t)FP_SPREAD_MAX_DOMAINS)) return FP_EINVAL;
+    for (size_t n = 0; sp && n < N; ++n)
+        if (domain[n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
+    if (n_cand == 0) return FP_OK;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_grow_dev d;
+    fp_grow_policy_dev dp;
+    const int n = fp_grow_policy_rows(cs, reason, reason_mask, ns, node_count, n_cand, t_cpu, t_mem, t_labels, t_max,
+                                      sp ? domain : nullptr, sp ? t_domain : nullptr, summary_out, policy_out,
+                                      assign_out, hops_out, reason_out, &d, &dp, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    fp_grow_policy pol;
+    pol.node_count = dp.node_count; pol.strategy = strategy; pol.preferred = preferred_labels;
+    pol.domain = dp.domain; pol.t_domain = dp.t_domain; pol.max_skew = max_skew;
+    pol.relax_mask = relax_mask; pol.n_hops = n_hops; pol.quota = quota; pol.quota_used = quota_used;
+    pol.policy_out = dp.policy_out; pol.hops_out = dp.hops_out; pol.reason_out = dp.reason_out;
+    if (int rc = fp_dev_grow_sweep_policy_impl(c, &d.cs, d.reason, reason_mask, &dp.ns, n_cand, d.t_cpu, d.t_mem,
+                                               d.t_labels, d.t_max, max_new, d.summary, d.assign_out, pol))
+        return rc;
+    return copy_back_all(c, rows, n);
+}

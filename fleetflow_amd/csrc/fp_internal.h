@@ -220,6 +220,31 @@ int fp_dev_grow_sweep_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *re
                            uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                            const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
 
+// what a scale-out sweep under the policy has besides the sweep's own arguments (SPEC.md 2.18).  Not ABI: the
+// exports of fp_ctx.hip fill it in.  node_count, the domains and the three results are device memory; relax_mask,
+// quota and quota_used are HOST arrays, read during the call
+struct fp_grow_policy {
+    const uint32_t *node_count = nullptr;  // [N] or null (zeros)
+    uint32_t strategy = 0, preferred = 0;
+    const uint32_t *domain = nullptr;      // [N]
+    const uint32_t *t_domain = nullptr;    // [n_cand]; null or max_skew == 0: no constraint
+    uint32_t max_skew = 0;
+    const uint32_t *relax_mask = nullptr;  // [n_hops]; null or n_hops == 0: no chain
+    uint32_t n_hops = 0;
+    const uint32_t *quota = nullptr;       // [3] or null: no quota
+    const uint32_t *quota_used = nullptr;  // [3] or null (zeros); read only
+    uint32_t *policy_out = nullptr;        // [n_cand][FP_GROW_POLICY_WORDS] or null
+    uint8_t *hops_out = nullptr;           // [n_cand][C] or null
+    uint8_t *reason_out = nullptr;         // [n_cand][C] or null
+};
+// the scale-out sweep under the policy (fp_grow.hip, SPEC.md 2.18): ns is the live table (device memory, read
+// only).  A t_max value above max_new and, under a constraint, a domain or t_domain value of 64 or more are found
+// on the device (FP_EINVAL in the context's error word, nothing written)
+int fp_dev_grow_sweep_policy_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
+                                  const fp_nodes *ns, uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem,
+                                  const uint32_t *t_labels, const uint32_t *t_max, uint32_t max_new,
+                                  uint32_t *summary_out, uint32_t *assign_out, const fp_grow_policy &pol);
+
 // re-planning a running stage (fp_replan.hip, SPEC.md 2.13); every pointer is device memory.  Of `o` the call
 // reads strategy, preferred and node_count.  A strategy that is no fp_strategy value and a prev value out of
 // range are found on the device (FP_EINVAL in the context's error word, nothing written)

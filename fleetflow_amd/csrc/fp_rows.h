@@ -235,3 +235,48 @@ static inline int fp_grow_rows(const fp_containers *cs, const uint8_t *reason, u
     r[n++] = fp_row_opt(assign_out, K * C, &d->assign_out);
     return n;
 }
+
+// fp_grow_sweep_policy (SPEC.md 2.18): fp_grow_sweep's inputs, the live table with its counts and domains, the
+// templates' domains (both domain rows absent without a constraint); then the five results.  relax_mask, quota
+// and quota_used stay on the host
+struct fp_grow_policy_dev {
+    fp_nodes ns;
+    const uint32_t *node_count, *domain, *t_domain;
+    uint32_t *policy_out;
+    uint8_t *hops_out, *reason_out;
+};
+static inline int fp_grow_policy_rows(const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
+                                      const fp_nodes *ns, const uint32_t *node_count, uint32_t n_cand,
+                                      const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                                      const uint32_t *t_max, const uint32_t *domain, const uint32_t *t_domain,
+                                      uint32_t *summary_out, uint32_t *policy_out, uint32_t *assign_out,
+                                      uint8_t *hops_out, uint8_t *reason_out, fp_grow_dev *d, fp_grow_policy_dev *dp,
+                                      fp_row *r) {
+    const size_t C = cs->n, N = ns->n, K = n_cand;
+    d->cs = *cs;
+    dp->ns = *ns;
+    int n = 0;
+    r[n++] = fp_row_in(cs->cpu_m, C, &d->cs.cpu_m);
+    r[n++] = fp_row_in(cs->mem_mib, C, &d->cs.mem_mib);
+    r[n++] = fp_row_in(cs->req_labels, C, &d->cs.req_labels);
+    r[n++] = fp_row_in(cs->conflict, C, &d->cs.conflict);
+    r[n++] = fp_row_in(reason_mask ? reason : nullptr, C, &d->reason);
+    r[n++] = fp_row_in(ns->cpu_free, N, &dp->ns.cpu_free);
+    r[n++] = fp_row_in(ns->mem_free, N, &dp->ns.mem_free);
+    r[n++] = fp_row_in(ns->labels, N, &dp->ns.labels);
+    r[n++] = fp_row_in(ns->conflict_used, N, &dp->ns.conflict_used);
+    r[n++] = fp_row_in(ns->schedulable, N, &dp->ns.schedulable);
+    r[n++] = fp_row_in(node_count, N, &dp->node_count);
+    r[n++] = fp_row_in(domain, N, &dp->domain);
+    r[n++] = fp_row_in(t_cpu, K, &d->t_cpu);
+    r[n++] = fp_row_in(t_mem, K, &d->t_mem);
+    r[n++] = fp_row_in(t_labels, K, &d->t_labels);
+    r[n++] = fp_row_in(t_max, K, &d->t_max);
+    r[n++] = fp_row_in(t_domain, K, &dp->t_domain);
+    r[n++] = fp_row_out(summary_out, K * FP_GROW_WORDS, &d->summary);
+    r[n++] = fp_row_opt(policy_out, K * FP_GROW_POLICY_WORDS, &dp->policy_out);
+    r[n++] = fp_row_opt(assign_out, K * C, &d->assign_out);
+    r[n++] = fp_row_opt(hops_out, K * C, &dp->hops_out);
+    r[n++] = fp_row_opt(reason_out, K * C, &dp->reason_out);
+    return n;
+}

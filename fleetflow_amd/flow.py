@@ -948,6 +948,16 @@ class GrowCandidate:
     # the services of each new server in visiting order (cpu desc, mem desc, stage order); None where the
     # candidate was not detailed
     servers: list[list[str]] | None = None
+    # under the policy (SPEC.md 2.18, grow_stage(under_policy=True)); unset otherwise
+    on_live: int | None = None             # pending services that land on an EXISTING server
+    relaxed: dict[str, list[str]] = field(default_factory=dict)  # placed service -> label keys given up (Plan.relaxed)
+    stuck_skew: int | None = None          # pending services some server fits and none takes within the skew
+    stuck_quota: int | None = None         # pending services the quota refuses
+    skew_before: int | None = None         # max - min of the services per eligible domain, the new servers' included
+    skew_after: int | None = None          # the same after the placements
+    domain: str | None = None              # the template's "key=value" under the constraint's topology key
+    moved_in: list[tuple[str, str]] = field(default_factory=list)  # (service, existing server) in visiting order
+    no_topology_key: bool = False          # under a constraint a template without the key is no candidate
 
 
 @dataclass
@@ -958,17 +968,124 @@ class GrowReport:
     max_new: int = 0
     pending: list[str] = field(default_factory=list)  # the plan's NOFIT services, stage order
     candidates: list[GrowCandidate] = field(default_factory=list)
+    # the policy the answer was held to (SPEC.md 2.18); unset without under_policy, where ``pending`` holds the
+    # plan's NOFIT and SKEW services
+    under_policy: bool = False
+    strategy: str | None = None
+    preferred: list[str] = field(default_factory=list)
+    spread_topology_key: str | None = None
+    spread_max_skew: int | None = None
+    fallback_relax_order: list[str] = field(default_factory=list)
+    fallback_max_hops: int | None = None
+    quota: tuple | None = None
+    quota_used: tuple | None = None
+
+
+def _grow_stage_policy(flow: Flow, stage_name: str, plan: Plan, catalogue: list[Server], max_new: int, p: Planner,
+                       policy: PlacementPolicy | None) -> GrowReport:
+    """``grow_stage(under_policy=True)``: SPEC.md 2.18, one ``Planner.grow_sweep_policy`` call."""
+    from ._lib import (FP_SPREAD_MAX_DOMAINS, GROW_CAPPED, GROW_FIRST_UNPLACED, GROW_LEFT_CPU, GROW_LEFT_MEM, GROW_ON_LIVE,
+                       GROW_OPENED, GROW_PENDING, GROW_PLACED, GROW_SKEW_AFTER, GROW_SKEW_BEFORE, GROW_STUCK_QUOTA,
+                       GROW_STUCK_SKEW, GROW_UNPLACEABLE, REASON_NOFIT, REASON_OK, REASON_SKEW)
+    pol = policy if policy is not None else _plan_policy(plan)
+    names, nodes, cont, live, _, count, strategy, pmask = live_tables(flow, stage_name, plan, pol)
+    ld = _stage_labels(names, flow, nodes, pol.preferred)
+    code = {"NOFIT": REASON_NOFIT, "SKEW": REASON_SKEW}
+    reason = [code.get(plan.rejected.get(n), REASON_OK) for n in names]
+    report = GrowReport(stage_name, int(max_new), [n for n, r in zip(names, reason) if r != REASON_OK], [], True,
+                        strategy, pol.preferred)
+    if pol.fallback:
+        report.fallback_relax_order, report.fallback_max_hops = list(pol.fallback_relax_order), pol.fallback_max_hops
+    used = tuple(plan.quota_used) if plan.quota_used is not None else (0, 0, 0)
+    if pol.quota is not None:
+        report.quota, report.quota_used = pol.quota, used
+    domain, max_skew, t_value = None, 0, [None] * len(catalogue)
+    cand = list(range(len(catalogue)))  # the templates that are candidates, catalogue order
+    t_domain = None
+    if pol.spread is not None:
+        key, max_skew = pol.spread
+        report.spread_topology_key, report.spread_max_skew = key, max_skew
+        domain, has_key = replan_domains(nodes, key)
+        live = (*live[:4], [s if k else 0 for s, k in zip(live[4], has_key)])
+        prefix = key + "="
+        ids = {}
+        for nd, d, k in zip(nodes, domain, has_key):
+            if k:
+                ids.setdefault(next(lab for lab in nd.labels if lab.startswith(prefix)), d)
+        nxt = max(domain, default=-1) + 1  # past the spare id of the servers without the key
+        t_value = [next((lab for lab in t.labels if lab.startswith(prefix)), None) for t in catalogue]
+        cand = [k for k, v in enumerate(t_value) if v is not None]
+        t_domain = []
+        for k in cand:
+            if t_value[k] not in ids:
+                ids[t_value[k]] = nxt
+                nxt += 1
+            t_domain.append(ids[t_value[k]])
+        if nxt > FP_SPREAD_MAX_DOMAINS:
+            raise ValueError(f"spread constraint: the stage and the catalogue have {nxt} distinct domains under "
+                             f"'{key}' (at most {FP_SPREAD_MAX_DOMAINS})")
+    known = [[lab for lab in t.labels if lab in ld.bits] for t in catalogue]
+    for t, labs, value in zip(catalogue, known, t_value):
+        c = GrowCandidate(t.slug, t.cpu_m, t.mem_mib, labs, int(max_new), len(report.pending))
+        c.domain, c.no_topology_key = value, pol.spread is not None and value is None
+        report.candidates.append(c)
+    if not cand:
+        return report
+    tpl = ([catalogue[k].cpu_m for k in cand], [catalogue[k].mem_mib for k in cand], [ld.mask(known[k]) for k in cand])
+    relax = [ld.key_mask(k) for k in pol.fallback]
+    summary, rows, assign, hops, _ = p.grow_sweep_policy(
+        cont, reason, live, tpl, max_new, (1 << REASON_NOFIT) | (1 << REASON_SKEW), None,
+        strategy if strategy is not None else 0, pmask, count, domain=domain, t_domain=t_domain, max_skew=max_skew,
+        relax_mask=relax, quota=pol.quota, quota_used=used if pol.quota is not None else None, want_assign=True)
+    visit = sorted((v for v, r in enumerate(reason) if r != REASON_OK), key=lambda v: (-cont[0][v], -cont[1][v], v))
+    N = len(nodes)
+    for j, k in enumerate(cand):
+        c, row, prow = report.candidates[k], [int(x) for x in summary[j]], [int(x) for x in rows[j]]
+        first = row[GROW_FIRST_UNPLACED]
+        c.pending, c.placed, c.opened, c.unplaceable, c.capped = (row[GROW_PENDING], row[GROW_PLACED], row[GROW_OPENED],
+                                                                  row[GROW_UNPLACEABLE], row[GROW_CAPPED])
+        c.left_cpu_m, c.left_mem_mib = row[GROW_LEFT_CPU], row[GROW_LEFT_MEM]
+        c.first_unplaced = names[first] if first != NONE else None
+        c.on_live, c.stuck_skew, c.stuck_quota = prow[GROW_ON_LIVE], prow[GROW_STUCK_SKEW], prow[GROW_STUCK_QUOTA]
+        if pol.spread is not None:
+            c.skew_before, c.skew_after = prow[GROW_SKEW_BEFORE], prow[GROW_SKEW_AFTER]
+        c.servers = [[] for _ in range(c.opened)]
+        for v in visit:
+            n = int(assign[j][v])
+            if n == NONE:
+                continue
+            if n < N:
+                c.moved_in.append((names[v], nodes[n].slug))
+            else:
+                c.servers[n - N].append(names[v])  # the new servers used are [N, N + opened)
+            if int(hops[j][v]):
+                required = {lab.split("=", 1)[0] for lab in flow.services.get(names[v], Service()).labels}
+                c.relaxed[names[v]] = [key for key in pol.fallback[:int(hops[j][v])] if key in required]
+    return report
 
 
 def grow_stage(flow: Flow, stage_name: str, plan: Plan, catalogue: list[Server], max_new: int = 64,
-               planner: Planner | None = None) -> GrowReport:
+               planner: Planner | None = None, policy: PlacementPolicy | None = None,
+               under_policy: bool = False) -> GrowReport:
     """"What do I have to add?" for a stage planned as ``plan`` says (SPEC.md 2.12): the pending services are
     the plan's NOFIT rejections, with their full required labels, and every ``Server`` of ``catalogue``
     (``registry.plan_template``) is a template of which up to ``max_new`` new servers may be opened, first
     fit.  Template labels go through the stage's label dictionary; a label nothing in the stage uses is
     dropped.  One ``Planner.grow_sweep`` covers the catalogue; a second one, with the per-server lists,
     covers the templates that place every pending service or, when none does, the one that places the most
-    (the first of them in catalogue order)."""
+    (the first of them in catalogue order).  The policy's strategy, preferred labels, spread constraint,
+    fallback chain and quota are not applied by default.
+
+    ``under_policy=True`` applies them (SPEC.md 2.18, one ``Planner.grow_sweep_policy`` call): those of
+    ``policy`` or, without one, of the policy the plan was made under, with the quota's usage the plan left.
+    The pending services are then the plan's NOFIT **and SKEW** rejections, and each template's servers are
+    added behind the live tables of ``live_tables``, so a pending service may land on an existing server
+    (``GrowCandidate.moved_in``).  Under a spread constraint a template stands in the domain its
+    ``topology_key=value`` label names, in the stage's numbering; a value the stage does not have is a new
+    domain (a 65th is a ValueError), and a template without the key is no candidate: it is reported with
+    nothing placed and ``no_topology_key``.  Every candidate is detailed."""
+    if under_policy:
+        return _grow_stage_policy(flow, stage_name, plan, catalogue, max_new, planner or default_planner(), policy)
     from ._lib import (GROW_CAPPED, GROW_FIRST_UNPLACED, GROW_LEFT_CPU, GROW_LEFT_MEM, GROW_OPENED, GROW_PENDING,
                        GROW_PLACED, GROW_UNPLACEABLE, REASON_NOFIT, REASON_OK)
     p = planner or default_planner()

@@ -270,27 +270,72 @@ def replan_report_from_json(text: str) -> Replan:
 def format_grow_report(report: GrowReport) -> str:
     """One line per template, ``grow <name>: <opened> new servers take <placed> of <pending> services, <u> fit
     no such server, <c> over the cap of <max>``, with the services of each new server (``+<ordinal>: a, b``)
-    indented under it where the candidate was detailed."""
+    indented under it where the candidate was detailed.  Under the policy (SPEC.md 2.18) the line goes on with
+    ``; <n> on existing servers, <r> relaxed, <s> held by the skew, <q> by the quota`` and, under a constraint,
+    `` [<key=value>: skew <before> -> <after>]``; the services that land on existing servers follow as
+    ``service: -> server``, and a template without the topology key prints ``no candidate: no <key> label``."""
     lines = []
     for c in report.candidates:
-        lines.append(f"grow {c.name}: {c.opened} new servers take {c.placed} of {c.pending} services, "
-                     f"{c.unplaceable} fit no such server, {c.capped} over the cap of {c.max_new}")
+        if report.under_policy and c.no_topology_key:
+            lines.append(f"grow {c.name}: no candidate: no {report.spread_topology_key} label")
+            continue
+        line = (f"grow {c.name}: {c.opened} new servers take {c.placed} of {c.pending} services, "
+                f"{c.unplaceable} fit no such server, {c.capped} over the cap of {c.max_new}")
+        if report.under_policy:
+            line += (f"; {c.on_live or 0} on existing servers, {len(c.relaxed)} relaxed, {c.stuck_skew or 0} held by the "
+                     f"skew, {c.stuck_quota or 0} by the quota")
+            if c.skew_before is not None:
+                line += f" [{c.domain}: skew {c.skew_before} -> {c.skew_after}]"
+        lines.append(line)
         lines += [f"  +{j}: {', '.join(svcs)}" for j, svcs in enumerate(c.servers or [])]
+        lines += [f"  {svc}: -> {dst}" for svc, dst in c.moved_in]
     return "\n".join(lines)
 
 
+# GrowCandidate's fields of SPEC.md 2.18: present in the JSON of a report made under the policy only
+_GROW_POLICY_FIELDS = ("on_live", "relaxed", "stuck_skew", "stuck_quota", "skew_before", "skew_after", "domain", "moved_in",
+                       "no_topology_key")
+
+
 def grow_report_to_json(report: GrowReport, indent: int | None = None) -> str:
-    d = {"stage": report.stage, "max_new": report.max_new, "pending": report.pending,
-         "candidates": [asdict(c) for c in report.candidates]}
+    """``{stage, max_new, pending, candidates}``; a report made under the policy (SPEC.md 2.18) adds
+    ``placement`` (strategy, preferred, and spread / fallback / quota when set) and the candidates' policy fields."""
+    cands = [asdict(c) for c in report.candidates]
+    if not report.under_policy:
+        for c in cands:
+            for k in _GROW_POLICY_FIELDS:
+                c.pop(k, None)
+    d = {"stage": report.stage, "max_new": report.max_new, "pending": report.pending, "candidates": cands}
+    if report.under_policy:
+        pol = {"strategy": report.strategy, "preferred": report.preferred}
+        if report.spread_topology_key is not None:
+            pol["spread"] = {"topology_key": report.spread_topology_key, "max_skew": report.spread_max_skew}
+        if report.fallback_relax_order:
+            pol["fallback"] = {"relax_order": report.fallback_relax_order, "max_hops": report.fallback_max_hops}
+        if report.quota is not None:
+            pol["quota"] = {"caps": list(report.quota), "used": list(report.quota_used or (0, 0, 0))}
+        d["placement"] = pol
     return json.dumps(d, ensure_ascii=False, indent=indent)
 
 
 def grow_report_from_json(text: str) -> GrowReport:
     d = json.loads(text)
     cands = [GrowCandidate(**{**c, "labels": list(c["labels"]),
-                              "servers": None if c.get("servers") is None else [list(s) for s in c["servers"]]})
+                              "servers": None if c.get("servers") is None else [list(s) for s in c["servers"]],
+                              "relaxed": {k: list(v) for k, v in (c.get("relaxed") or {}).items()},
+                              "moved_in": [tuple(m) for m in c.get("moved_in") or []]})
              for c in d.get("candidates") or []]
-    return GrowReport(d["stage"], d.get("max_new", 0), list(d.get("pending") or []), cands)
+    report = GrowReport(d["stage"], d.get("max_new", 0), list(d.get("pending") or []), cands)
+    pol = d.get("placement")
+    if pol is not None:
+        report.under_policy, report.strategy, report.preferred = True, pol.get("strategy"), list(pol.get("preferred") or [])
+        report.spread_topology_key = (pol.get("spread") or {}).get("topology_key")
+        report.spread_max_skew = (pol.get("spread") or {}).get("max_skew")
+        report.fallback_relax_order = list((pol.get("fallback") or {}).get("relax_order") or [])
+        report.fallback_max_hops = (pol.get("fallback") or {}).get("max_hops")
+        if pol.get("quota") is not None:
+            report.quota, report.quota_used = tuple(pol["quota"]["caps"]), tuple(pol["quota"]["used"])
+    return report
 
 
 def get_network_name(project: str, stage: str) -> str:

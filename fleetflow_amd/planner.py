@@ -804,7 +804,125 @@ class Planner:
                                     _arg(assign)), "fp_grow_sweep")
         return summary, assign
 
+    def grow_sweep_policy(self, cont, reason, nodes, templates, max_new, reason_mask=1 << _lib.REASON_NOFIT,
+                          t_max=None, strategy=0, preferred=0, node_count=None, *, domain=None, t_domain=None,
+                          max_skew=0, relax_mask=(), quota=None, quota_used=None, want_assign=False):
+        """The scale-out sweep under the policy (SPEC.md 2.18, fp_grow_sweep_policy): ``grow_sweep`` where
+        candidate k is one ``place_policy_quota`` of the pending containers on the live table ``nodes`` (read
+        only, N may be 0; ``node_count`` [N] or None = zeros) followed by ``t_max[k]`` empty servers of the
+        template, under ``strategy`` / ``preferred`` (SPEC.md 2.6), the spread constraint (``domain`` [N] and
+        ``t_domain`` [n_cand] ids below 64, ``max_skew``; ``t_domain`` None or ``max_skew`` 0 = none, neither is
+        then read), the fallback chain (``relax_mask``, at most 4 hops; empty = none) and the quota (``quota`` =
+        (cpu_m, mem_mib, services) with None = no cap, ``quota_used`` what the tenant holds, read only; None = no
+        quota).  N + ``max_new`` <= FP_POLICY_MAX_NODES.  Inputs are not mutated.  Returns (summary [n_cand, 8],
+        policy_rows [n_cand, 8], assign, hops, reason): the policy rows' word indices are _lib.GROW_ON_LIVE, ..;
+        the last three are [n_cand, C] with ``want_assign`` (assign = the node in the combined table, N + j the
+        j-th new server, NONE for every container that is not pending or not placed), else None."""
+        cont = tuple(_u32(x) for x in cont)
+        C = cont[0].size
+        self._need(len(cont) == 4 and all(x.size == C for x in cont), "every container array must hold C entries")
+        cf, mf, lab, cu = (_u32(x).reshape(-1) for x in nodes[:4])
+        live = (cf, mf, lab, cu, _u8(nodes[4]).reshape(-1))
+        N = cf.size
+        self._need(all(x.size == N for x in live), "every node array must hold N entries")
+        tpl = tuple(_u32(x).reshape(-1) for x in templates)
+        self._need(len(tpl) == 3, "templates must be (t_cpu, t_mem, t_labels)")
+        n_cand = tpl[0].size
+        self._need(all(x.size == n_cand for x in tpl), "every template array must hold n_cand entries")
+        rs = _u8(reason) if reason is not None else None
+        reason_mask, max_new, max_skew, strategy = int(reason_mask), int(max_new), int(max_skew), strategy_id(strategy)
+        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
+        self._need(reason_mask == 0 or rs is None or rs.size == C, "reason must hold C entries")
+        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
+        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
+        tm = _u32(t_max).reshape(-1) if t_max is not None else None
+        self._need(tm is None or tm.size == n_cand, "t_max must hold n_cand entries")
+        nc = _u32(node_count).reshape(-1) if node_count is not None else None
+        self._need(nc is None or nc.size == N, "node_count must hold N entries")
+        dom = _u32(domain).reshape(-1) if domain is not None else None
+        td = _u32(t_domain).reshape(-1) if t_domain is not None else None
+        self._need(dom is None or dom.size == N, "domain must hold N entries")
+        self._need(td is None or td.size == n_cand, "t_domain must hold n_cand entries")
+        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
+        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+        rm = _u32(relax) if relax else None
+        qt = _quota_rows(quota, 1) if quota is not None else None
+        qu = _u32(quota_used).reshape(-1) if quota_used is not None else None
+        self._need(qu is None or qu.size == _lib.QUOTA_DIMS, "quota_used must hold 3 entries")
+        summary = np.empty((n_cand, _lib.GROW_WORDS), np.uint32)
+        rows = np.empty((n_cand, _lib.GROW_POLICY_WORDS), np.uint32)
+        assign = np.empty((n_cand, C), np.uint32) if want_assign else None
+        hops = np.empty((n_cand, C), np.uint8) if want_assign else None
+        why = np.empty((n_cand, C), np.uint8) if want_assign else None
+        cs = FpContainers(C, *(_ptr(x) for x in cont))
+        ns = FpNodes(N, *(_ptr(x) for x in live))
+        check(self._L.fp_grow_sweep_policy(
+            self._ctx, ct.byref(cs), _arg(rs if reason_mask else None), reason_mask, ct.byref(ns), _arg(nc), n_cand,
+            _arg(tpl[0]), _arg(tpl[1]), _arg(tpl[2]), _arg(tm), max_new, strategy, int(preferred) & 0xFFFFFFFF,
+            _arg(dom), _arg(td), max_skew, _arg(rm), len(relax), _arg(qt), _arg(qu), _arg(summary), _arg(rows),
+            _arg(assign), _arg(hops), _arg(why)), "fp_grow_sweep_policy")
+        return summary, rows, assign, hops, why
+
     # -- device-pointer API -------------------------------------------------------------
+    def dev_grow_sweep_policy(self, cont_t, reason_t, nodes_t, templates_t, max_new, summary_t,
+                              reason_mask=1 << _lib.REASON_NOFIT, t_max_t=None, strategy=0, preferred=0, count_t=None, *,
+                              domain_t=None, t_domain_t=None, max_skew=0, relax_mask=(), quota=None, quota_used=None,
+                              policy_t=None, assign_out_t=None, hops_t=None, reason_out_t=None):
+        """fp_dev_grow_sweep_policy on device tensors: ``dev_grow_sweep``'s arguments, ``nodes_t`` = the live table
+        (cpu_free, mem_free, labels, conflict_used [N] int32 storage, schedulable [N] uint8) with ``count_t`` [N]
+        or None, ``domain_t`` [N] and ``t_domain_t`` [n_cand] or None, and the optional results ``policy_t``
+        [n_cand * 8], ``assign_out_t`` [n_cand * C], ``hops_t`` and ``reason_out_t`` [n_cand * C] uint8.
+        ``max_new``, ``max_skew``, ``relax_mask``, ``quota`` and ``quota_used`` are host values.  A t_max above
+        max_new or a domain value out of range is found on the device: nothing is written and sync() raises
+        FP_EINVAL."""
+        C, N = cont_t[0].numel(), nodes_t[0].numel()
+        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
+                   "every container tensor must hold C 32-bit entries")
+        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
+                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
+                   "every node tensor must hold N entries (schedulable N bytes)")
+        self._need(len(templates_t) == 3, "templates_t must be (t_cpu, t_mem, t_labels)")
+        n_cand = templates_t[0].numel()
+        self._need(all(t.numel() == n_cand and t.element_size() == 4 for t in templates_t),
+                   "every template tensor must hold n_cand 32-bit entries")
+        reason_mask, max_new, max_skew, strategy = int(reason_mask), int(max_new), int(max_skew), strategy_id(strategy)
+        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
+        self._need(reason_mask == 0 or reason_t is None or (reason_t.numel() == C and reason_t.element_size() == 1),
+                   "reason_t must hold C bytes")
+        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
+        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
+        self._need(t_max_t is None or (t_max_t.numel() == n_cand and t_max_t.element_size() == 4),
+                   "t_max_t must hold n_cand 32-bit entries")
+        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
+                   "count_t must hold N 32-bit entries")
+        self._need(domain_t is None or (domain_t.numel() == N and domain_t.element_size() == 4),
+                   "domain_t must hold N 32-bit entries")
+        self._need(t_domain_t is None or (t_domain_t.numel() == n_cand and t_domain_t.element_size() == 4),
+                   "t_domain_t must hold n_cand 32-bit entries")
+        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
+        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+        self._need(summary_t.numel() == n_cand * _lib.GROW_WORDS and summary_t.element_size() == 4,
+                   "summary_t must hold n_cand * 8 32-bit entries")
+        self._need(policy_t is None or (policy_t.numel() == n_cand * _lib.GROW_POLICY_WORDS
+                                        and policy_t.element_size() == 4),
+                   "policy_t must hold n_cand * 8 32-bit entries")
+        self._need(assign_out_t is None or (assign_out_t.numel() == n_cand * C and assign_out_t.element_size() == 4),
+                   "assign_out_t must hold n_cand * C 32-bit entries")
+        for name, x in (("hops_t", hops_t), ("reason_out_t", reason_out_t)):
+            self._need(x is None or (x.numel() == n_cand * C and x.element_size() == 1),
+                       f"{name} must hold n_cand * C bytes")
+        rm = _u32(relax) if relax else None  # the three host arrays are read during the call
+        qt = _quota_rows(quota, 1) if quota is not None else None
+        qu = _u32(quota_used).reshape(-1) if quota_used is not None else None
+        self._need(qu is None or qu.size == _lib.QUOTA_DIMS, "quota_used must hold 3 entries")
+        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
+        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
+        self._dev(lambda: check(self._L.fp_dev_grow_sweep_policy(
+            self._ctx, ct.byref(cs), _arg(reason_t if reason_mask else None), reason_mask, ct.byref(ns), _arg(count_t),
+            n_cand, *(_arg(t) for t in templates_t), _arg(t_max_t), max_new, strategy, int(preferred) & 0xFFFFFFFF,
+            _arg(domain_t), _arg(t_domain_t), max_skew, _arg(rm), len(relax), _arg(qt), _arg(qu), _arg(summary_t),
+            _arg(policy_t), _arg(assign_out_t), _arg(hops_t), _arg(reason_out_t)), "fp_dev_grow_sweep_policy"))
+
     def dev_grow_sweep(self, cont_t, reason_t, templates_t, max_new, summary_t, reason_mask=1 << _lib.REASON_NOFIT,
                        t_max_t=None, assign_out_t=None):
         """fp_dev_grow_sweep on device tensors: ``cont_t`` = (cpu, mem, req, conf) [C] each (int32 storage of

@@ -501,13 +501,58 @@ int fp_shrink_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nodes *
  * of the new server a placed pending container got, FP_NONE for every other container.  No input is written.
  * n_cand > 65535 or max_new > FP_GROW_MAX_NEW is FP_EOVERFLOW; reason == NULL with reason_mask != 0 and a
  * t_max[k] > max_new are FP_EINVAL; on any error nothing is written.  Only first fit; preferred labels, the
- * spread constraint, the fallback chain and the quota are not applied. */
+ * spread constraint, the fallback chain and the quota are not applied: fp_grow_sweep_policy applies them. */
 enum { FP_GROW_PENDING = 0, FP_GROW_PLACED = 1, FP_GROW_OPENED = 2, FP_GROW_UNPLACEABLE = 3, FP_GROW_CAPPED = 4,
        FP_GROW_LEFT_CPU = 5, FP_GROW_LEFT_MEM = 6, FP_GROW_FIRST_UNPLACED = 7, FP_GROW_WORDS = 8 };
 #define FP_GROW_MAX_NEW 8192u
 int fp_grow_sweep(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
                   uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                   const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
+/* The scale-out sweep under the policy (SPEC.md 2.18): "what do I have to add, and WHERE?", for a tenant whose
+ * PlacementPolicy carries a strategy, preferred labels, a spread constraint, a fallback chain and a quota.
+ * c, reason, reason_mask, the templates, t_max and max_new are fp_grow_sweep's.  nodes is the LIVE table (read
+ * only; nodes->n may be 0), node_count its counts (nullable: zeros), domain[n] the live nodes' topology domains and
+ * t_domain[k] the domain a new server of template k stands in (both < FP_SPREAD_MAX_DOMAINS; a new domain is an id
+ * no live node has).  relax_mask[n_hops] is fp_place_policy_fallback's; quota[FP_QUOTA_DIMS] and
+ * quota_used[FP_QUOTA_DIMS] are fp_place_policy_quota's, both nullable, quota_used READ ONLY here: a pending
+ * container is not charged to its tenant yet, so admission has something to test.
+ * Candidate k is computed independently and writes no input.  It is exactly one fp_place_policy_quota call over the
+ * pending containers on the live table followed by M = t_max[k] template nodes (cpu_free = t_cpu[k], mem_free =
+ * t_mem[k], labels = t_labels[k], conflict_used = 0, schedulable, node_count = 0, domain = t_domain[k]) under the
+ * call's strategy, preferred labels, constraint, chain, quota and usage.  So the template's domain is eligible as
+ * soon as M >= 1, a new domain starts at count 0, and a pending container may land on a LIVE node (filling a
+ * starved domain raises the minimum and reopens the domains the skew test had closed).
+ * summary_out is fp_grow_sweep's row, read by the reason that call gives:
+ *   PLACED  reason OK, on a live or a new node          OPENED  new nodes that received a container: [N, N + OPENED)
+ *   UNPLACEABLE  reason NOFIT and cpu_m > t_cpu || mem_mib > t_mem || (t_labels & req') != req', with
+ *                req' = req_labels & ~cum[n_hops]        CAPPED  reason NOFIT otherwise
+ *   LEFT_CPU, LEFT_MEM  summed over the OPENED new servers     FIRST_UNPLACED  the first pending with reason != 0
+ * policy_out (nullable) holds one row of FP_GROW_POLICY_WORDS u32 per candidate:
+ *   ON_LIVE  placed on a node < nodes->n     RELAXED  placed at a hop >= 1
+ *   STUCK_SKEW  reason SKEW                   STUCK_QUOTA  reason QUOTA
+ *   SKEW_BEFORE, SKEW_AFTER  max - min of the domain counts over the eligible domains of the combined table,
+ *   before and after; 0 without a constraint or without an eligible domain.  Words 6 and 7 are written as 0.
+ * PENDING == PLACED + UNPLACEABLE + CAPPED + STUCK_SKEW + STUCK_QUOTA.  The nullable [n_cand][c->n] results:
+ * assign_out = the node in the combined table (nodes->n + j is the j-th new server), FP_NONE for every container
+ * that is not pending or not placed; hops_out = the hop, else 0; reason_out = the reason, 0 for every container
+ * that is not pending or placed.  With nothing pending every row is zeros with FIRST_UNPLACED = FP_NONE.
+ * t_domain == NULL or max_skew == 0: no constraint, neither domain array is read; relax_mask == NULL or n_hops ==
+ * 0: no chain; quota == NULL: no quota, quota_used is not read.  With nodes->n == 0, first fit, no preferred labels
+ * and none of the three, summary_out and assign_out are fp_grow_sweep's bit for bit.
+ * Errors: fp_grow_sweep's, with nodes->n + max_new > FP_POLICY_MAX_NODES as FP_EOVERFLOW; a strategy above
+ * FP_STRATEGY_FILL_LOWEST, n_hops > FP_FALLBACK_MAX_HOPS, domain == NULL with a constraint and nodes->n != 0, and
+ * (with max_skew != 0) any domain[n] or t_domain[k] >= FP_SPREAD_MAX_DOMAINS, whatever t_max[k] is, are FP_EINVAL;
+ * on any error nothing is written. */
+enum { FP_GROW_ON_LIVE, FP_GROW_RELAXED, FP_GROW_STUCK_SKEW, FP_GROW_STUCK_QUOTA, FP_GROW_SKEW_BEFORE,
+       FP_GROW_SKEW_AFTER, /* words 0 to 5 */ FP_GROW_POLICY_WORD6, FP_GROW_POLICY_WORD7, /* written as 0 */
+       FP_GROW_POLICY_WORDS /* 8 */ };
+int fp_grow_sweep_policy(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
+                         const fp_nodes *nodes, const uint32_t *node_count, uint32_t n_cand, const uint32_t *t_cpu,
+                         const uint32_t *t_mem, const uint32_t *t_labels, const uint32_t *t_max, uint32_t max_new,
+                         uint32_t strategy, uint32_t preferred_labels, const uint32_t *domain,
+                         const uint32_t *t_domain, uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                         const uint32_t *quota, const uint32_t *quota_used, uint32_t *summary_out,
+                         uint32_t *policy_out, uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out);
 /* Re-planning a running stage (SPEC.md 2.13): fp_place_policy that knows where each container runs now.  nodes is
  * the BASE table (everything deducted except these containers' own requests) and is updated in place; prev[c] is
  * the node container c runs on, < nodes->n, or FP_NONE.  Pass 1 (seats) visits the containers in fp_place's order
@@ -680,6 +725,20 @@ int fp_dev_shrink_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nod
 int fp_dev_grow_sweep(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
                       uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                       const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out);
+/* As fp_grow_sweep_policy on device pointers, with the exceptions of fp_dev_drain_sweep_policy and one more:
+ * relax_mask (n_hops words), quota and quota_used (FP_QUOTA_DIMS words each) are HOST arrays, read during the call
+ * like the scalars beside them; max_new stays a host value and the geometry follows nodes->n + max_new.  A strategy
+ * above FP_STRATEGY_FILL_LOWEST and n_hops above FP_FALLBACK_MAX_HOPS are returned directly.  A t_max[k] > max_new
+ * or a domain / t_domain value out of range is found on the device before any store: nothing is written and
+ * fp_ctx_sync() reports FP_EINVAL.  Workspace as fp_dev_grow_sweep. */
+int fp_dev_grow_sweep_policy(fp_ctx *ctx, const fp_containers *c, const uint8_t *reason, uint32_t reason_mask,
+                             const fp_nodes *nodes, const uint32_t *node_count, uint32_t n_cand,
+                             const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
+                             const uint32_t *t_max, uint32_t max_new, uint32_t strategy, uint32_t preferred_labels,
+                             const uint32_t *domain, const uint32_t *t_domain, uint32_t max_skew,
+                             const uint32_t *relax_mask, uint32_t n_hops, const uint32_t *quota,
+                             const uint32_t *quota_used, uint32_t *summary_out, uint32_t *policy_out,
+                             uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out);
 /* As fp_replan_batch on device pointers (change_out and summary_out included).  A strategy that is no fp_strategy
  * value and a prev value out of range are found on the device before any store: nothing is written and
  * fp_ctx_sync() reports FP_EINVAL.  The call takes the FFD order's 24 bytes per container plus the sort's scratch

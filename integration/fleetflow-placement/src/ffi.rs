@@ -92,6 +92,14 @@ pub const FP_GROW_LEFT_MEM: usize = 6;
 pub const FP_GROW_FIRST_UNPLACED: usize = 7;
 pub const FP_GROW_WORDS: usize = 8;
 pub const FP_GROW_MAX_NEW: u32 = 8192;
+// the scale-out sweep under the policy (SPEC.md 2.18): the word indices of a candidate's policy row
+pub const FP_GROW_ON_LIVE: usize = 0;
+pub const FP_GROW_RELAXED: usize = 1;
+pub const FP_GROW_STUCK_SKEW: usize = 2;
+pub const FP_GROW_STUCK_QUOTA: usize = 3;
+pub const FP_GROW_SKEW_BEFORE: usize = 4;
+pub const FP_GROW_SKEW_AFTER: usize = 5;
+pub const FP_GROW_POLICY_WORDS: usize = 8;
 // re-planning a running stage (SPEC.md 2.13): enum fp_change, and the word indices of a scenario's summary row
 pub const FP_CHANGE_KEPT: u8 = 0;
 pub const FP_CHANGE_NEW: u8 = 1;
@@ -287,6 +295,13 @@ unsafe extern "C" {
     pub fn fp_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32, n_cand: u32,
                          t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32, t_max: *const u32,
                          max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
+    pub fn fp_grow_sweep_policy(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
+                                nodes: *const fp_nodes, node_count: *const u32, n_cand: u32, t_cpu: *const u32,
+                                t_mem: *const u32, t_labels: *const u32, t_max: *const u32, max_new: u32,
+                                strategy: u32, preferred_labels: u32, domain: *const u32, t_domain: *const u32,
+                                max_skew: u32, relax_mask: *const u32, n_hops: u32, quota: *const u32,
+                                quota_used: *const u32, summary_out: *mut u32, policy_out: *mut u32,
+                                assign_out: *mut u32, hops_out: *mut u8, reason_out: *mut u8) -> c_int;
     pub fn fp_replan(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *mut fp_nodes, level: *const u32,
                      prev: *const u32, strategy: u32, preferred_labels: u32, node_count: *mut u32,
                      assign_out: *mut u32, reason_out: *mut u8, change_out: *mut u8, summary_out: *mut u32) -> c_int;
@@ -362,6 +377,13 @@ unsafe extern "C" {
     pub fn fp_dev_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
                              n_cand: u32, t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32,
                              t_max: *const u32, max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
+    pub fn fp_dev_grow_sweep_policy(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
+                                    nodes: *const fp_nodes, node_count: *const u32, n_cand: u32, t_cpu: *const u32,
+                                    t_mem: *const u32, t_labels: *const u32, t_max: *const u32, max_new: u32,
+                                    strategy: u32, preferred_labels: u32, domain: *const u32, t_domain: *const u32,
+                                    max_skew: u32, relax_mask: *const u32, n_hops: u32, quota: *const u32,
+                                    quota_used: *const u32, summary_out: *mut u32, policy_out: *mut u32,
+                                    assign_out: *mut u32, hops_out: *mut u8, reason_out: *mut u8) -> c_int;
     pub fn fp_dev_replan_batch(ctx: *mut fp_ctx, b: *const fp_batch, prev: *const u32, strategy: *const u32,
                                preferred_labels: *const u32, node_count: *mut u32, change_out: *mut u8,
                                summary_out: *mut u32) -> c_int;

@@ -307,6 +307,58 @@ impl Planner {
         Ok((rows, assign))
     }
 
+    /// The scale-out sweep under the policy (SPEC.md 2.18, fleetplace.h `fp_grow_sweep_policy`): `grow_sweep` where
+    /// candidate k is one `place_policy_quota` of the pending containers on the live table `nodes` (read only, may
+    /// be empty; `node_count` None = zeros) followed by `t_max[k]` empty servers of the template standing in domain
+    /// `t_domain[k]`, under `strategy`, `preferred_labels`, the spread constraint (`domain`, `t_domain`, `max_skew`;
+    /// `t_domain` None or 0 = none), the fallback chain (`relax_mask`, at most `ffi::FP_FALLBACK_MAX_HOPS`; empty =
+    /// none) and the quota (`quota` None = none; `quota_used` None = zeros, read only).  No input is changed.
+    /// Returns one row of `ffi::FP_GROW_WORDS` and one of `ffi::FP_GROW_POLICY_WORDS` words per candidate and,
+    /// with `want_assign`, candidate-major per container: the node in the combined table (`nodes.len() + j` = the
+    /// j-th new server, `ffi::FP_NONE` = none), the hop and the reason.
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn grow_sweep_policy(&mut self, c: &Containers, reason: Option<&[u8]>, reason_mask: u32, nodes: &Nodes,
+                             node_count: Option<&[u32]>, t_cpu: &[u32], t_mem: &[u32], t_labels: &[u32],
+                             t_max: Option<&[u32]>, max_new: u32, strategy: u32, preferred_labels: u32,
+                             domain: Option<&[u32]>, t_domain: Option<&[u32]>, max_skew: u32, relax_mask: &[u32],
+                             quota: Option<&[u32; 3]>, quota_used: Option<&[u32; 3]>, want_assign: bool)
+                             -> Result<(Vec<[u32; ffi::FP_GROW_WORDS]>, Vec<[u32; ffi::FP_GROW_POLICY_WORDS]>,
+                                        Option<(Vec<u32>, Vec<u8>, Vec<u8>)>), PlanError> {
+        let (n, nn, k) = (c.cpu_m.len(), nodes.cpu_free.len(), t_cpu.len());
+        if !c.all_len(n) || !nodes.all_len(nn) || t_mem.len() != k || t_labels.len() != k
+            || t_max.map_or(false, |m| m.len() != k) || node_count.map_or(false, |x| x.len() != nn)
+            || domain.map_or(false, |d| d.len() != nn) || t_domain.map_or(false, |d| d.len() != k)
+            || relax_mask.len() > ffi::FP_FALLBACK_MAX_HOPS as usize
+            || (reason_mask != 0 && reason.map_or(true, |r| r.len() != n)) {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        // the sweep reads the node table only: the mutable pointers of fp_nodes are never written through
+        let ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_ptr() as *mut u32,
+                                 mem_free: nodes.mem_free.as_ptr() as *mut u32, labels: nodes.labels.as_ptr(),
+                                 conflict_used: nodes.conflict_used.as_ptr() as *mut u32,
+                                 schedulable: nodes.schedulable.as_ptr() };
+        let mut rows = vec![[0u32; ffi::FP_GROW_WORDS]; k];
+        let mut prows = vec![[0u32; ffi::FP_GROW_POLICY_WORDS]; k];
+        let mut per = if want_assign { Some((vec![ffi::FP_NONE; k * n], vec![0u8; k * n], vec![0u8; k * n])) } else { None };
+        let (pa, ph, pr) = per.as_mut().map_or((std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()),
+                                               |p| (p.0.as_mut_ptr(), p.1.as_mut_ptr(), p.2.as_mut_ptr()));
+        let reason_ptr = if reason_mask != 0 { reason.map_or(std::ptr::null(), |r| r.as_ptr()) } else { std::ptr::null() };
+        check(unsafe {
+            ffi::fp_grow_sweep_policy(self.ctx, &cs, reason_ptr, reason_mask, &ns,
+                                      node_count.map_or(std::ptr::null(), |x| x.as_ptr()), k as u32, t_cpu.as_ptr(),
+                                      t_mem.as_ptr(), t_labels.as_ptr(), t_max.map_or(std::ptr::null(), |m| m.as_ptr()),
+                                      max_new, strategy, preferred_labels, domain.map_or(std::ptr::null(), |d| d.as_ptr()),
+                                      t_domain.map_or(std::ptr::null(), |d| d.as_ptr()), max_skew,
+                                      if relax_mask.is_empty() { std::ptr::null() } else { relax_mask.as_ptr() },
+                                      relax_mask.len() as u32, quota.map_or(std::ptr::null(), |q| q.as_ptr()),
+                                      quota_used.map_or(std::ptr::null(), |q| q.as_ptr()), rows.as_mut_ptr() as *mut u32,
+                                      prows.as_mut_ptr() as *mut u32, pa, ph, pr)
+        })?;
+        Ok((rows, prows, per))
+    }
+
     /// Scored placement (SPEC.md 2.6, fleetplace.h `fp_place_policy`): `strategy` is one of
     /// `ffi::FP_STRATEGY_*`, `preferred_labels` the soft preferred-label mask, `node_count` the
     /// containers already on each node (updated in place; None starts at zero).  `nodes` is

@@ -20,6 +20,24 @@ time comes from the context's event brackets (FP_K_PLACE, FP_K_SORT) in a separa
 timed the two answers are compared: ``same_counts`` says that both placed the same number on the same number of
 servers for every candidate, ``same_plan`` (up to 480 candidates) that every pending container got the same
 server from both.  Writes profiles/grow_timing.json and prints it.
+
+    python tools/grow_timing.py --policy [--steps K] [--warmup W] [--rounds R]
+
+The sweep under the policy (SPEC.md 2.18), written to profiles/grow_policy_timing.json.  For a live table of 1000
+and of 5000 nodes (ten containers a node, eight topology domains) the scenario is placed by
+fp_dev_place_batch_policy_quota under spread, max_skew 1 and a chain over class and region; its NOFIT and SKEW
+containers are the pending.  The same catalogues are timed, each with max_new = 64, 1024 and the most the
+placer's table leaves beside the live nodes, the templates standing in the eight live domains and a ninth:
+
+* ``sweep``: fp_dev_grow_sweep_policy with the policy rows and without the per-container results, and
+* ``route``: the only way to the same answers without it: materialise one combined table per candidate on the
+  device (``build``), call fp_dev_place_batch_policy_quota with S = n_cand (``call``), and reduce its outputs to
+  the counters of the rows (``rows``; FIRST_UNPLACED and the two skew words are left out, so the pass is cheaper
+  than a complete one).
+
+``same_counts`` compares PLACED, OPENED, ON_LIVE, RELAXED, STUCK_SKEW and STUCK_QUOTA of every candidate.
+``sweep_faster`` says that the sweep's median is below the route's median (build + call + rows) by more than the
+two spreads (max - min) together; ``sweep_faster_than_call`` says the same against the call alone.
 """
 import argparse
 import itertools
@@ -69,15 +87,147 @@ def build_replicas(pend_t, tpl, max_new, dev):
     return b
 
 
+RELAX = (0x780, 0x78)  # the generator's class bits, then its region bits
+N_DOM = 8
+
+
+def policy_leg(a):
+    dev = torch.device("cuda", 0)
+    props = torch.cuda.get_device_properties(dev)
+    out = {"steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "device": props.name,
+           "compute_units": props.multi_processor_count, "policy": {"strategy": 1, "max_skew": 1, "relax_mask": list(RELAX),
+                                                                    "domains": N_DOM, "quota": [None, None, 2 ** 30]},
+           "order": "each round: the sweep, then the route", "points": []}
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)  # noqa: E731
+    tens = lambda xs: torch.tensor(xs, dtype=torch.int32, device=dev)  # noqa: E731
+    quota, mask = (None, None, 2 ** 30), (1 << _lib.REASON_NOFIT) | (1 << _lib.REASON_SKEW)
+    with Planner(0) as p:
+        for N in (1000, 5000):
+            C = 10 * N
+            db = DevBatch.allocate(1, C, N, dev)
+            p.dev_gen_batch(SEED4, db, 7)
+            count, domain = i32(N), (torch.arange(N, device=dev) % N_DOM).to(torch.int32)
+            p.dev_place_batch_policy_quota(db, tens([1]), None, None, None, count, domain_t=domain, max_skew_t=tens([1]),
+                                           relax_mask_t=tens(list(RELAX) + [0, 0]), n_hops_t=tens([2]))
+            p.sync()
+            cont_t, nodes_t = (db.cpu, db.mem, db.req, db.conf), (db.cf, db.mf, db.lab, db.cu, db.sched)
+            pend = torch.nonzero((db.reason == _lib.REASON_NOFIT) | (db.reason == _lib.REASON_SKEW)).flatten()
+            pend_t = tuple(t[pend].contiguous() for t in cont_t)
+            P = int(pend.numel())
+            for n_cand, max_new in itertools.product(N_CAND, (64, 1024, _lib.FP_POLICY_MAX_NODES - N)):
+                S, T = n_cand, N + max_new
+                tpl = catalogue(n_cand, dev)
+                t_dom = (torch.arange(n_cand, device=dev) % (N_DOM + 1)).to(torch.int32)
+                rows, prow = i32(S * _lib.GROW_WORDS), i32(S * _lib.GROW_POLICY_WORDS)
+                st, ms, nh = tens([1] * S), tens([1] * S), tens([2] * S)
+                rm, qt = tens((list(RELAX) + [0, 0]) * S), tens([-1, -1, 2 ** 30] * S)
+
+                def sweep():
+                    p.dev_grow_sweep_policy(cont_t, db.reason, nodes_t, tpl, max_new, rows, mask, None, 1, 0, count,
+                                            domain_t=domain, t_domain_t=t_dom, max_skew=1, relax_mask=RELAX, quota=quota,
+                                            quota_used=(0, 0, 0), policy_t=prow)
+
+                def route():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    b = DevBatch.allocate(S, P, T, dev)
+                    for dst, src in zip((b.cpu, b.mem, b.req, b.conf), pend_t):
+                        dst.view(S, P).copy_(src.view(1, P).expand(S, P))
+                    for dst, src, new in zip((b.cf, b.mf, b.lab, b.cu), nodes_t, (*tpl, None)):
+                        dst.view(S, T)[:, :N] = src.view(1, N)
+                        dst.view(S, T)[:, N:] = new.view(S, 1) if new is not None else 0
+                    b.sched.view(S, T)[:, :N] = db.sched.view(1, N)
+                    b.sched.view(S, T)[:, N:] = 1
+                    cnt, dom, used, hops = i32(S * T), i32(S * T), i32(S * 3), torch.zeros(S * P, dtype=torch.uint8, device=dev)
+                    cnt.view(S, T)[:, :N] = count.view(1, N)
+                    dom.view(S, T)[:, :N] = domain.view(1, N)
+                    dom.view(S, T)[:, N:] = t_dom.view(S, 1)
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    p.dev_place_batch_policy_quota(b, st, qt, used, None, cnt, domain_t=dom, max_skew_t=ms, relax_mask_t=rm,
+                                                   n_hops_t=nh, hops_t=hops)
+                    p.sync()
+                    t2 = time.perf_counter()
+                    asg, rs, new_cnt = b.assign.view(S, P), b.reason.view(S, P), cnt.view(S, T)[:, N:]
+                    got = {"placed": (asg != -1).sum(1), "opened": (new_cnt > 0).sum(1),
+                           "on_live": ((asg != -1) & (asg < N)).sum(1), "relaxed": (hops.view(S, P) > 0).sum(1),
+                           "stuck_skew": (rs == _lib.REASON_SKEW).sum(1), "stuck_quota": (rs == _lib.REASON_QUOTA).sum(1),
+                           "left_cpu": (b.cf.view(S, T)[:, N:] * (new_cnt > 0)).sum(1),
+                           "left_mem": (b.mf.view(S, T)[:, N:] * (new_cnt > 0)).sum(1)}
+                    keep = pend_t[2].view(1, P) & ~(RELAX[0] | RELAX[1])
+                    never = ((pend_t[0].view(1, P) > tpl[0].view(S, 1)) | (pend_t[1].view(1, P) > tpl[1].view(S, 1))
+                             | ((tpl[2].view(S, 1) & keep) != keep))
+                    got["unplaceable"] = ((rs == _lib.REASON_NOFIT) & never).sum(1)
+                    torch.cuda.synchronize()
+                    t3 = time.perf_counter()
+                    return (t1 - t0, t2 - t1, t3 - t2), got
+
+                # ---- the same answer first ----
+                sweep()
+                p.sync()
+                _, got = route()
+                sm, pw = rows.view(S, _lib.GROW_WORDS), prow.view(S, _lib.GROW_POLICY_WORDS)
+                pairs = ((got["placed"], sm[:, _lib.GROW_PLACED]), (got["opened"], sm[:, _lib.GROW_OPENED]),
+                         (got["unplaceable"], sm[:, _lib.GROW_UNPLACEABLE]), (got["on_live"], pw[:, _lib.GROW_ON_LIVE]),
+                         (got["relaxed"], pw[:, _lib.GROW_RELAXED]), (got["stuck_skew"], pw[:, _lib.GROW_STUCK_SKEW]),
+                         (got["stuck_quota"], pw[:, _lib.GROW_STUCK_QUOTA]))
+                g = {"live_nodes": N, "containers": C, "pending": P, "n_cand": n_cand, "max_new": max_new,
+                     "placed": int(sm[:, _lib.GROW_PLACED].sum().item()), "opened": int(sm[:, _lib.GROW_OPENED].sum().item()),
+                     "on_live": int(pw[:, _lib.GROW_ON_LIVE].sum().item()),
+                     "stuck_skew": int(pw[:, _lib.GROW_STUCK_SKEW].sum().item()),
+                     "same_counts": all(bool(torch.equal(x.to(torch.int32), y)) for x, y in pairs)}
+                del got
+                for _ in range(a.warmup):
+                    sweep()
+                    route()
+                p.sync()
+                sw, parts = [], [[], [], []]
+                for _ in range(a.rounds):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(a.steps):
+                        sweep()
+                    p.sync()
+                    sw.append(1e3 * (time.perf_counter() - t0) / a.steps)
+                    acc = [0.0, 0.0, 0.0]
+                    for _ in range(a.steps):
+                        dt, _ = route()
+                        acc = [x + y for x, y in zip(acc, dt)]
+                    for xs, x in zip(parts, acc):
+                        xs.append(1e3 * x / a.steps)
+                total = [x + y + z for x, y, z in zip(*parts)]
+                spread = lambda xs: max(xs) - min(xs)  # noqa: E731
+                g["sweep"] = {"ms_per_call": _stats(sw)}
+                g["route"] = {"build_ms": _stats(parts[0]), "call_ms": _stats(parts[1]), "rows_ms": _stats(parts[2]),
+                              "total_ms": _stats(total)}
+                g["route_over_sweep"] = statistics.median(total) / statistics.median(sw)
+                g["call_over_sweep"] = statistics.median(parts[1]) / statistics.median(sw)
+                g["sweep_faster"] = statistics.median(total) - statistics.median(sw) > spread(sw) + spread(total)
+                g["sweep_faster_than_call"] = (statistics.median(parts[1]) - statistics.median(sw)
+                                               > spread(sw) + spread(parts[1]))
+                out["points"].append(g)
+                print(json.dumps(g), flush=True)
+                torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--policy", action="store_true", help="time the sweep under the policy (SPEC.md 2.18)")
     ap.add_argument("--containers", type=int, default=50_000)
     ap.add_argument("--nodes", type=int, default=5_000)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grow_timing.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "grow_policy_timing.json" if a.policy else "grow_timing.json")
+    if a.policy:
+        return policy_leg(a)
     C, N = a.containers, a.nodes
     dev = torch.device("cuda", 0)
     props = torch.cuda.get_device_properties(dev)
