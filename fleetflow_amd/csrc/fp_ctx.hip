@@ -420,13 +420,8 @@ extern "C" int fp_levelize(fp_ctx *c, const fp_graph *g, uint32_t *level_out, ui
 
 // ---- placement: fp_place*, fp_place*_policy* --------------------------------------
 static bool batch_has_tables(const fp_batch *b) {
-    if (b->n_scen && b->n_containers &&
-        (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || !b->assign || !b->reason))
-        return false;
-    if (b->n_scen && b->n_nodes &&
-        (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable))
-        return false;
-    return true;
+    if (b->n_scen && b->n_containers && (!fp_has_cont(b) || !b->assign || !b->reason)) return false;
+    return !(b->n_scen && b->n_nodes) || fp_has_nodes(b);
 }
 
 // one scenario's tables as a batch of one (no cost)
@@ -478,30 +473,31 @@ extern "C" int fp_place(fp_ctx *c, const fp_containers *cs, fp_nodes *ns, const 
     return batch_run(c, &b, nullptr);
 }
 
+// The guarantees of a host scored call (host memory: refused before anything is staged): a pair with one half
+// null is dropped, a domain id out of range in a constrained scenario and an n_hops above FP_FALLBACK_MAX_HOPS
+// are FP_EINVAL, and without quota neither quota_used nor quota_why is touched
+static int policy_guarantees(fp_policy_opts &o, size_t S, size_t N) {
+    if (!o.domain || !o.max_skew) o.domain = o.max_skew = nullptr;
+    for (size_t s = 0; o.max_skew && s < S; ++s)
+        if (o.max_skew[s] != 0u && !fp_domains_ok(o.domain + s * N, N)) return FP_EINVAL;
+    if (!o.relax_mask || !o.n_hops) o.relax_mask = o.n_hops = nullptr;
+    for (size_t s = 0; o.n_hops && s < S; ++s)
+        if (o.n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (!o.quota) o.quota_used = nullptr, o.quota_why = nullptr;
+    return FP_OK;
+}
+
 // Scored placement (SPEC.md 2.6): fp_place_batch's staging with the per-scenario strategy and
 // preferred-label words and the optional node counts.  The strategies are host memory here, so a
-// value that is no fp_strategy is refused before anything is staged.
-// domain / max_skew (SPEC.md 2.7; either null = no constraint) are host memory too: a domain id out of
-// range in a constrained scenario is refused here as well.
-// relax_mask / n_hops (SPEC.md 2.8; either null = no fallback) likewise: an n_hops above
-// FP_FALLBACK_MAX_HOPS is refused here.  hops (nullable) receives the winners' hops.
-// quota (SPEC.md 2.10; null = no quota, and then quota_used and quota_why are not touched) has no
-// illegal value.  quota_used (nullable) goes in and comes back; quota_why (nullable) comes back.
+// value that is no fp_strategy is refused before anything is staged, and so are the guarantees' (SPEC.md 2.7,
+// 2.8, 2.10: policy_guarantees).  hops (nullable) receives the winners' hops; quota_used (nullable) goes in and
+// comes back; quota_why (nullable) comes back.
 static int batch_policy_host(fp_ctx *c, const fp_batch *b, fp_policy_opts o) {
     const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes, SC = S * C;
     if (S && !o.strategy) return FP_EINVAL;
     for (size_t s = 0; s < S; ++s)
         if (o.strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
-    if (!o.domain || !o.max_skew) o.domain = o.max_skew = nullptr;
-    for (size_t s = 0; o.max_skew && s < S; ++s) {
-        if (o.max_skew[s] == 0u) continue;
-        for (size_t n = 0; n < N; ++n)
-            if (o.domain[s * N + n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
-    }
-    if (!o.relax_mask || !o.n_hops) o.relax_mask = o.n_hops = nullptr;
-    for (size_t s = 0; o.n_hops && s < S; ++s)
-        if (o.n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
-    if (!o.quota) o.quota_used = nullptr, o.quota_why = nullptr;
+    if (int rc = policy_guarantees(o, S, N)) return rc;
     if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
     return batch_run(c, b, &o);
 }
@@ -643,19 +639,23 @@ extern "C" int fp_dev_place_batch_policy_quota(fp_ctx *c, const fp_batch *b, con
 
 // ---- re-planning a running stage (SPEC.md 2.13, fp_replan.hip) --------------------
 // A scored batch's staging (batch_run's row list) with prev and the two optional results behind it.  Everything
-// the device entry finds on the device is host memory here and refused before anything is staged.
-static int replan_host(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o, uint8_t *change_out,
-                       uint32_t *summary_out) {
-    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes, SC = S * C;
+// the device entry finds on the device is host memory here and refused before anything is staged: replan_checks
+// is what both host forms test first, replan_run their staging, run and copy back around the impl of each.
+static int replan_checks(const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o) {
+    const size_t S = b->n_scen, N = b->n_nodes, SC = S * b->n_containers;
     if (S && !o.strategy) return FP_EINVAL;
     if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
     for (size_t s = 0; s < S; ++s)
         if (o.strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
     if (!batch_has_tables(b) || (SC && !prev)) return FP_EINVAL;
     if (SC && prev == b->assign) return FP_EINVAL;
-    for (size_t i = 0; i < SC; ++i)
-        if (prev[i] >= N && prev[i] != FP_NONE) return FP_EINVAL;
-    if (S == 0) return FP_OK;
+    return fp_below_or_none(prev, SC, N) ? FP_OK : FP_EINVAL;
+}
+
+typedef int replan_impl(fp_ctx *, const fp_batch *, const uint32_t *, const fp_policy_opts &, uint8_t *, uint32_t *);
+static int replan_run(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o, uint8_t *change_out,
+                      uint32_t *summary_out, replan_impl *impl) {
+    if (b->n_scen == 0) return FP_OK;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
@@ -665,8 +665,14 @@ static int replan_host(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const
     fp_replan_dev dr;
     const int n = fp_replan_rows(b, &o, prev, change_out, summary_out, &d, &dopt, &dr, rows);
     if (int rc = stage_rows(c, rows, n, false)) return rc;
-    if (int rc = fp_dev_replan_batch_impl(c, &d, dr.prev, dopt, dr.change, dr.summary)) return rc;
+    if (int rc = impl(c, &d, dr.prev, dopt, dr.change, dr.summary)) return rc;
     return copy_back_all(c, rows, n);
+}
+
+static int replan_host(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const fp_policy_opts &o, uint8_t *change_out,
+                       uint32_t *summary_out) {
+    if (int rc = replan_checks(b, prev, o)) return rc;
+    return replan_run(c, b, prev, o, change_out, summary_out, fp_dev_replan_batch_impl);
 }
 
 extern "C" int fp_replan_batch(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
@@ -698,37 +704,9 @@ extern "C" int fp_dev_replan_batch(fp_ctx *c, const fp_batch *b, const uint32_t 
 // every policy option (27 rows).
 static int replan_policy_host(fp_ctx *c, const fp_batch *b, const uint32_t *prev, fp_policy_opts o, uint8_t *change_out,
                               uint32_t *summary_out) {
-    const size_t S = b->n_scen, C = b->n_containers, N = b->n_nodes, SC = S * C;
-    if (S && !o.strategy) return FP_EINVAL;
-    if ((uint64_t)b->scen_base + S > 65536ull || N > FP_POLICY_MAX_NODES || SC > 0xFFFFFFFFull) return FP_EOVERFLOW;
-    for (size_t s = 0; s < S; ++s)
-        if (o.strategy[s] > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
-    if (!batch_has_tables(b) || (SC && !prev)) return FP_EINVAL;
-    if (SC && prev == b->assign) return FP_EINVAL;
-    for (size_t i = 0; i < SC; ++i)
-        if (prev[i] >= N && prev[i] != FP_NONE) return FP_EINVAL;
-    if (!o.domain || !o.max_skew) o.domain = o.max_skew = nullptr;
-    for (size_t s = 0; o.max_skew && s < S; ++s) {
-        if (o.max_skew[s] == 0u) continue;
-        for (size_t n = 0; n < N; ++n)
-            if (o.domain[s * N + n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
-    }
-    if (!o.relax_mask || !o.n_hops) o.relax_mask = o.n_hops = nullptr;
-    for (size_t s = 0; o.n_hops && s < S; ++s)
-        if (o.n_hops[s] > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
-    if (!o.quota) o.quota_used = nullptr, o.quota_why = nullptr;
-    if (S == 0) return FP_OK;
-    FP_HIP(hipSetDevice(c->device));
-    fp_host_err_scope es(c);
-    if (es.rc) return es.rc;
-    fp_row rows[FP_MAX_ROWS];
-    fp_batch d;
-    fp_policy_opts dopt;
-    fp_replan_dev dr;
-    const int n = fp_replan_rows(b, &o, prev, change_out, summary_out, &d, &dopt, &dr, rows);
-    if (int rc = stage_rows(c, rows, n, false)) return rc;
-    if (int rc = fp_dev_replan_batch_policy_impl(c, &d, dr.prev, dopt, dr.change, dr.summary)) return rc;
-    return copy_back_all(c, rows, n);
+    if (int rc = replan_checks(b, prev, o)) return rc;
+    if (int rc = policy_guarantees(o, b->n_scen, b->n_nodes)) return rc;
+    return replan_run(c, b, prev, o, change_out, summary_out, fp_dev_replan_batch_policy_impl);
 }
 
 extern "C" int fp_replan_batch_policy(fp_ctx *c, const fp_batch *b, const uint32_t *prev, const uint32_t *strategy,
@@ -778,12 +756,8 @@ extern "C" int fp_feasibility(fp_ctx *c, const fp_containers *cs, const fp_nodes
                               uint32_t *first_out, uint32_t *count_out, uint64_t *bitmap_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
     const size_t C = cs->n, N = ns->n, WC = (C + 63) / 64;
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !first_out ||
-              !count_out))
-        return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used ||
-              !ns->schedulable))
-        return FP_EINVAL;
+    if (C && (!fp_has_cont(cs) || !first_out || !count_out)) return FP_EINVAL;
+    if (N && !fp_has_nodes(ns)) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
@@ -823,9 +797,8 @@ extern "C" int fp_explain(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns
     if (!sel) n_sel = cs->n;
     const size_t M = n_sel;
     if (M == 0) return FP_OK;
-    if (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !rows_out) return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable))
-        return FP_EINVAL;
+    if (!fp_has_cont(cs) || !rows_out) return FP_EINVAL;
+    if (N && !fp_has_nodes(ns)) return FP_EINVAL;
     for (size_t i = 0; sel && i < M; ++i)
         if (sel[i] >= C) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
@@ -852,10 +825,8 @@ extern "C" int fp_explain_batch(fp_ctx *c, const fp_batch *b, uint32_t reason_ma
     if (S == 0) return FP_OK;
     if (S > 65535u) return FP_EOVERFLOW;
     if (!hist_out) return FP_EINVAL;
-    if (C && (!b->cpu_m || !b->mem_mib || !b->req_labels || !b->conflict || (reason_mask && !b->reason)))
-        return FP_EINVAL;
-    if (C && N && (!b->cpu_free || !b->mem_free || !b->labels || !b->conflict_used || !b->schedulable))
-        return FP_EINVAL;
+    if (C && (!fp_has_cont(b) || (reason_mask && !b->reason))) return FP_EINVAL;
+    if (C && N && !fp_has_nodes(b)) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
@@ -877,7 +848,55 @@ extern "C" int fp_explain_batch(fp_ctx *c, const fp_batch *b, uint32_t reason_ma
     return copy_back_all(c, rows);
 }
 
-// drain what-if sweep (SPEC.md 2.11, fp_drain.hip)
+// ---- the what-if sweeps (SPEC.md 2.11, 2.12, 2.15 to 2.18) ----------------------------------------------------
+// A plain sweep is the sweep under the policy with an empty policy: each family has ONE host function, which
+// takes what the policy export's signature adds as an fp_*_policy (fp_internal.h).  The export's arguments fill
+// it (drain_policy, shrink_policy, grow_policy: used by the host and the fp_dev_* export alike), and the host
+// function swaps the staged device pointers in before it calls the same *_impl the device export calls.
+// relax_mask (and the scale-out sweep's quota and quota_used) are host arrays in both entries.
+static fp_drain_policy drain_policy(const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
+                                    uint32_t n_hops, uint8_t *hops_out, uint32_t *policy_out) {
+    fp_drain_policy p;
+    p.domain = domain; p.max_skew = max_skew; p.relax_mask = relax_mask; p.n_hops = n_hops;
+    p.hops_out = hops_out; p.policy_out = policy_out;
+    return p;
+}
+
+// drain what-if sweep (SPEC.md 2.11 and 2.15, fp_drain.hip).  Without a domain and an optional result
+// fp_drain_policy_rows lays out as fp_drain_rows does: the three further rows take nothing
+static int drain_host(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                      const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
+                      const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out, uint32_t *summary_out,
+                      fp_drain_policy pol) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const size_t C = cs->n, N = ns->n;
+    if (N > FP_POLICY_MAX_NODES || n_cand > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
+    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (pol.n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (C && (!fp_has_cont(cs) || !assign || !assign_out || !reason_out)) return FP_EINVAL;
+    if (N && (!fp_has_nodes(ns) || !group)) return FP_EINVAL;
+    if (n_cand && !summary_out) return FP_EINVAL;
+    if (C && assign_out == assign) return FP_EINVAL;
+    if (!fp_below_or_none(group, N, n_cand) || !fp_below_or_none(assign, C, N)) return FP_EINVAL;
+    if (!pol.domain || pol.max_skew == 0u) pol.domain = nullptr;  // otherwise domain is not read
+    if (pol.domain && !fp_domains_ok(pol.domain, N)) return FP_EINVAL;
+    if (C == 0 && n_cand == 0) return FP_OK;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_drain_dev d;
+    fp_drain_policy_dev dp;
+    const int n = fp_drain_policy_rows(cs, ns, assign, group, n_cand, node_count, pol.domain, assign_out, reason_out,
+                                       pol.hops_out, summary_out, pol.policy_out, &d, &dp, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    pol.domain = dp.domain; pol.hops_out = dp.hops_out; pol.policy_out = dp.policy_out;
+    if (int rc = fp_dev_drain_sweep_impl(c, &d.cs, &d.ns, d.assign, d.group, n_cand, strategy, preferred_labels,
+                                         d.node_count, d.assign_out, d.reason_out, d.summary, pol))
+        return rc;
+    return copy_back_all(c, rows, n);
+}
+
 extern "C" int fp_dev_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
                                   const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
                                   const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
@@ -892,35 +911,82 @@ extern "C" int fp_drain_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes
                               const uint32_t *group, uint32_t n_cand, uint32_t strategy, uint32_t preferred_labels,
                               const uint32_t *node_count, uint32_t *assign_out, uint8_t *reason_out,
                               uint32_t *summary_out) {
+    return drain_host(c, cs, ns, assign, group, n_cand, strategy, preferred_labels, node_count, assign_out, reason_out,
+                      summary_out, fp_drain_policy());
+}
+
+extern "C" int fp_dev_drain_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                         const uint32_t *group, uint32_t n_cand, uint32_t strategy,
+                                         uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                                         uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                         uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
+                                         uint32_t *summary_out, uint32_t *policy_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_drain_sweep_impl(c, cs, ns, assign, group, n_cand, strategy, preferred_labels,
+                                                  node_count, assign_out, reason_out, summary_out,
+                                                  drain_policy(domain, max_skew, relax_mask, n_hops, hops_out, policy_out)));
+}
+
+extern "C" int fp_drain_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                     const uint32_t *group, uint32_t n_cand, uint32_t strategy,
+                                     uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
+                                     uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                     uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
+                                     uint32_t *summary_out, uint32_t *policy_out) {
+    return drain_host(c, cs, ns, assign, group, n_cand, strategy, preferred_labels, node_count, assign_out, reason_out,
+                      summary_out, drain_policy(domain, max_skew, relax_mask, n_hops, hops_out, policy_out));
+}
+
+// scale-in sweep (SPEC.md 2.16 and 2.17, fp_shrink.hip)
+static fp_shrink_policy shrink_policy(const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask,
+                                      uint32_t n_hops, uint8_t *hops_out, uint8_t *blocker_reason_out,
+                                      uint32_t *policy_out) {
+    fp_shrink_policy p;
+    p.domain = domain; p.max_skew = max_skew; p.relax_mask = relax_mask; p.n_hops = n_hops;
+    p.hops_out = hops_out; p.blocker_reason_out = blocker_reason_out; p.policy_out = policy_out;
+    return p;
+}
+
+// no variant is nothing to do, whatever the tables are: found before them.  Without a domain and an optional
+// result fp_shrink_policy_rows lays out as fp_shrink_rows does
+static int shrink_host(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                       const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
+                       uint32_t preferred_labels, const uint32_t *node_count, uint32_t *assign_out, uint8_t *state_out,
+                       uint32_t *blocker_out, uint32_t *summary_out, fp_shrink_policy pol) {
     if (!c || !cs || !ns) return FP_EINVAL;
     const size_t C = cs->n, N = ns->n;
-    if (N > FP_POLICY_MAX_NODES || n_cand > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
+    if (N > FP_POLICY_MAX_NODES || n_var > 65535u || C > FP_SHRINK_MAX_CONTAINERS) return FP_EOVERFLOW;
     if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out || !reason_out))
-        return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !group))
-        return FP_EINVAL;
-    if (n_cand && !summary_out) return FP_EINVAL;
+    if (pol.n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (n_var == 0) return FP_OK;
+    if (C && (!fp_has_cont(cs) || !assign || !assign_out)) return FP_EINVAL;
+    if (N && (!fp_has_nodes(ns) || !state_out)) return FP_EINVAL;
+    if ((n_try && !try_order) || !summary_out) return FP_EINVAL;
     if (C && assign_out == assign) return FP_EINVAL;
-    for (size_t n = 0; n < N; ++n)
-        if (group[n] >= n_cand && group[n] != FP_NONE) return FP_EINVAL;
-    for (size_t i = 0; i < C; ++i)
-        if (assign[i] >= N && assign[i] != FP_NONE) return FP_EINVAL;
-    if (C == 0 && n_cand == 0) return FP_OK;
+    if (!fp_below_or_none(assign, C, N) || !fp_below_or_none(try_order, (size_t)n_var * n_try, N)) return FP_EINVAL;
+    if (!pol.domain || pol.max_skew == 0u) pol.domain = nullptr;  // otherwise domain is not read
+    if (pol.domain && !fp_domains_ok(pol.domain, N)) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
     if (es.rc) return es.rc;
     fp_row rows[FP_MAX_ROWS];
-    fp_drain_dev d;
-    const int n = fp_drain_rows(cs, ns, assign, group, n_cand, node_count, assign_out, reason_out, summary_out, &d, rows);
+    fp_shrink_dev d;
+    fp_shrink_policy_dev dp;
+    const int n = fp_shrink_policy_rows(cs, ns, assign, try_order, n_var, n_try, node_count, pol.domain, assign_out,
+                                        state_out, blocker_out, summary_out, pol.hops_out, pol.blocker_reason_out,
+                                        pol.policy_out, &d, &dp, rows);
     if (int rc = stage_rows(c, rows, n, false)) return rc;
-    if (int rc = fp_dev_drain_sweep_impl(c, &d.cs, &d.ns, d.assign, d.group, n_cand, strategy, preferred_labels,
-                                         d.node_count, d.assign_out, d.reason_out, d.summary))
+    pol.domain = dp.domain; pol.hops_out = dp.hops_out; pol.blocker_reason_out = dp.blocker_reason_out;
+    pol.policy_out = dp.policy_out;
+    if (int rc = fp_dev_shrink_sweep_impl(c, &d.cs, &d.ns, d.assign, d.try_order, n_var, n_try, strategy,
+                                          preferred_labels, d.node_count, d.assign_out, d.state_out, d.blocker_out,
+                                          d.summary, pol))
         return rc;
     return copy_back_all(c, rows, n);
 }
 
-// scale-in sweep (SPEC.md 2.16, fp_shrink.hip)
 extern "C" int fp_dev_shrink_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
                                    const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
                                    uint32_t preferred_labels, const uint32_t *node_count, uint32_t *assign_out,
@@ -935,36 +1001,10 @@ extern "C" int fp_shrink_sweep(fp_ctx *c, const fp_containers *cs, const fp_node
                                const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
                                uint32_t preferred_labels, const uint32_t *node_count, uint32_t *assign_out,
                                uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out) {
-    if (!c || !cs || !ns) return FP_EINVAL;
-    const size_t C = cs->n, N = ns->n;
-    if (N > FP_POLICY_MAX_NODES || n_var > 65535u || C > FP_SHRINK_MAX_CONTAINERS) return FP_EOVERFLOW;
-    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
-    if (n_var == 0) return FP_OK;
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out)) return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !state_out))
-        return FP_EINVAL;
-    if ((n_try && !try_order) || !summary_out) return FP_EINVAL;
-    if (C && assign_out == assign) return FP_EINVAL;
-    for (size_t i = 0; i < C; ++i)
-        if (assign[i] >= N && assign[i] != FP_NONE) return FP_EINVAL;
-    for (size_t i = 0; i < (size_t)n_var * n_try; ++i)
-        if (try_order[i] >= N && try_order[i] != FP_NONE) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    fp_host_err_scope es(c);
-    if (es.rc) return es.rc;
-    fp_row rows[FP_MAX_ROWS];
-    fp_shrink_dev d;
-    const int n = fp_shrink_rows(cs, ns, assign, try_order, n_var, n_try, node_count, assign_out, state_out, blocker_out,
-                                 summary_out, &d, rows);
-    if (int rc = stage_rows(c, rows, n, false)) return rc;
-    if (int rc = fp_dev_shrink_sweep_impl(c, &d.cs, &d.ns, d.assign, d.try_order, n_var, n_try, strategy,
-                                          preferred_labels, d.node_count, d.assign_out, d.state_out, d.blocker_out,
-                                          d.summary))
-        return rc;
-    return copy_back_all(c, rows, n);
+    return shrink_host(c, cs, ns, assign, try_order, n_var, n_try, strategy, preferred_labels, node_count, assign_out,
+                       state_out, blocker_out, summary_out, fp_shrink_policy());
 }
 
-// the scale-in sweep under the policy (SPEC.md 2.17, fp_shrink.hip).  relax_mask is a host array in both entries
 extern "C" int fp_dev_shrink_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
                                           const uint32_t *try_order, uint32_t n_var, uint32_t n_try, uint32_t strategy,
                                           uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
@@ -975,11 +1015,10 @@ extern "C" int fp_dev_shrink_sweep_policy(fp_ctx *c, const fp_containers *cs, co
     if (!c || !cs || !ns) return FP_EINVAL;
     if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
-    fp_shrink_policy pol;
-    pol.domain = domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
-    pol.hops_out = hops_out; pol.blocker_reason_out = blocker_reason_out; pol.policy_out = policy_out;
     return fp_dev_done(c, fp_dev_shrink_sweep_impl(c, cs, ns, assign, try_order, n_var, n_try, strategy, preferred_labels,
-                                                   node_count, assign_out, state_out, blocker_out, summary_out, pol));
+                                                   node_count, assign_out, state_out, blocker_out, summary_out,
+                                                   shrink_policy(domain, max_skew, relax_mask, n_hops, hops_out,
+                                                                 blocker_reason_out, policy_out)));
 }
 
 extern "C" int fp_shrink_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
@@ -989,105 +1028,25 @@ extern "C" int fp_shrink_sweep_policy(fp_ctx *c, const fp_containers *cs, const 
                                       uint32_t *assign_out, uint8_t *state_out, uint32_t *blocker_out,
                                       uint32_t *summary_out, uint8_t *hops_out, uint8_t *blocker_reason_out,
                                       uint32_t *policy_out) {
-    if (!c || !cs || !ns) return FP_EINVAL;
-    const size_t C = cs->n, N = ns->n;
-    if (N > FP_POLICY_MAX_NODES || n_var > 65535u || C > FP_SHRINK_MAX_CONTAINERS) return FP_EOVERFLOW;
-    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
-    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
-    if (n_var == 0) return FP_OK;
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out)) return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !state_out))
-        return FP_EINVAL;
-    if ((n_try && !try_order) || !summary_out) return FP_EINVAL;
-    if (C && assign_out == assign) return FP_EINVAL;
-    for (size_t i = 0; i < C; ++i)
-        if (assign[i] >= N && assign[i] != FP_NONE) return FP_EINVAL;
-    for (size_t i = 0; i < (size_t)n_var * n_try; ++i)
-        if (try_order[i] >= N && try_order[i] != FP_NONE) return FP_EINVAL;
-    const bool sp = domain && max_skew != 0u;  // otherwise domain is not read
-    for (size_t n = 0; sp && n < N; ++n)
-        if (domain[n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    fp_host_err_scope es(c);
-    if (es.rc) return es.rc;
-    fp_row rows[FP_MAX_ROWS];
-    fp_shrink_dev d;
-    fp_shrink_policy_dev dp;
-    const int n = fp_shrink_policy_rows(cs, ns, assign, try_order, n_var, n_try, node_count, sp ? domain : nullptr,
-                                        assign_out, state_out, blocker_out, summary_out, hops_out, blocker_reason_out,
-                                        policy_out, &d, &dp, rows);
-    if (int rc = stage_rows(c, rows, n, false)) return rc;
-    fp_shrink_policy pol;
-    pol.domain = dp.domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
-    pol.hops_out = dp.hops_out; pol.blocker_reason_out = dp.blocker_reason_out; pol.policy_out = dp.policy_out;
-    if (int rc = fp_dev_shrink_sweep_impl(c, &d.cs, &d.ns, d.assign, d.try_order, n_var, n_try, strategy,
-                                          preferred_labels, d.node_count, d.assign_out, d.state_out, d.blocker_out,
-                                          d.summary, pol))
-        return rc;
-    return copy_back_all(c, rows, n);
+    return shrink_host(c, cs, ns, assign, try_order, n_var, n_try, strategy, preferred_labels, node_count, assign_out,
+                       state_out, blocker_out, summary_out,
+                       shrink_policy(domain, max_skew, relax_mask, n_hops, hops_out, blocker_reason_out, policy_out));
 }
 
-// the drain sweep under the policy (SPEC.md 2.15, fp_drain.hip).  relax_mask is a host array in both entries
-extern "C" int fp_dev_drain_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
-                                         const uint32_t *group, uint32_t n_cand, uint32_t strategy,
-                                         uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
-                                         uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
-                                         uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
-                                         uint32_t *summary_out, uint32_t *policy_out) {
-    if (!c || !cs || !ns) return FP_EINVAL;
-    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
-    FP_HIP(hipSetDevice(c->device));
-    fp_drain_policy pol;
-    pol.domain = domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
-    pol.hops_out = hops_out; pol.policy_out = policy_out;
-    return fp_dev_done(c, fp_dev_drain_sweep_impl(c, cs, ns, assign, group, n_cand, strategy, preferred_labels,
-                                                  node_count, assign_out, reason_out, summary_out, pol));
+// scale-out sweep (SPEC.md 2.12 and 2.18, fp_grow.hip): the two kernels differ, so each export keeps its impl.
+// What both host exports ask of the pending containers and the templates, after their own FP_EOVERFLOW tests;
+// t_max is host memory here, so a value above max_new is refused before anything is staged
+static int grow_checks(const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask, uint32_t n_cand,
+                       const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels, const uint32_t *t_max,
+                       uint32_t max_new, const uint32_t *summary_out) {
+    if (reason_mask && !reason) return FP_EINVAL;
+    if (cs->n && !fp_has_cont(cs)) return FP_EINVAL;
+    if (n_cand && (!t_cpu || !t_mem || !t_labels || !summary_out)) return FP_EINVAL;
+    for (size_t k = 0; t_max && k < n_cand; ++k)
+        if (t_max[k] > max_new) return FP_EINVAL;
+    return FP_OK;
 }
 
-extern "C" int fp_drain_sweep_policy(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
-                                     const uint32_t *group, uint32_t n_cand, uint32_t strategy,
-                                     uint32_t preferred_labels, const uint32_t *node_count, const uint32_t *domain,
-                                     uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
-                                     uint32_t *assign_out, uint8_t *reason_out, uint8_t *hops_out,
-                                     uint32_t *summary_out, uint32_t *policy_out) {
-    if (!c || !cs || !ns) return FP_EINVAL;
-    const size_t C = cs->n, N = ns->n;
-    if (N > FP_POLICY_MAX_NODES || n_cand > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
-    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
-    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out || !reason_out))
-        return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !group))
-        return FP_EINVAL;
-    if (n_cand && !summary_out) return FP_EINVAL;
-    if (C && assign_out == assign) return FP_EINVAL;
-    for (size_t n = 0; n < N; ++n)
-        if (group[n] >= n_cand && group[n] != FP_NONE) return FP_EINVAL;
-    for (size_t i = 0; i < C; ++i)
-        if (assign[i] >= N && assign[i] != FP_NONE) return FP_EINVAL;
-    const bool sp = domain && max_skew != 0u;  // otherwise domain is not read
-    for (size_t n = 0; sp && n < N; ++n)
-        if (domain[n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
-    if (C == 0 && n_cand == 0) return FP_OK;
-    FP_HIP(hipSetDevice(c->device));
-    fp_host_err_scope es(c);
-    if (es.rc) return es.rc;
-    fp_row rows[FP_MAX_ROWS];
-    fp_drain_dev d;
-    fp_drain_policy_dev dp;
-    const int n = fp_drain_policy_rows(cs, ns, assign, group, n_cand, node_count, sp ? domain : nullptr, assign_out,
-                                       reason_out, hops_out, summary_out, policy_out, &d, &dp, rows);
-    if (int rc = stage_rows(c, rows, n, false)) return rc;
-    fp_drain_policy pol;
-    pol.domain = dp.domain; pol.max_skew = max_skew; pol.relax_mask = relax_mask; pol.n_hops = n_hops;
-    pol.hops_out = dp.hops_out; pol.policy_out = dp.policy_out;
-    if (int rc = fp_dev_drain_sweep_impl(c, &d.cs, &d.ns, d.assign, d.group, n_cand, strategy, preferred_labels,
-                                         d.node_count, d.assign_out, d.reason_out, d.summary, pol))
-        return rc;
-    return copy_back_all(c, rows, n);
-}
-
-// scale-out sweep (SPEC.md 2.12, fp_grow.hip)
 extern "C" int fp_dev_grow_sweep(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
                                  uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                                  const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out) {
@@ -1101,13 +1060,9 @@ extern "C" int fp_grow_sweep(fp_ctx *c, const fp_containers *cs, const uint8_t *
                              uint32_t n_cand, const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                              const uint32_t *t_max, uint32_t max_new, uint32_t *summary_out, uint32_t *assign_out) {
     if (!c || !cs) return FP_EINVAL;
-    const size_t C = cs->n;
     if (n_cand > 65535u || max_new > FP_GROW_MAX_NEW) return FP_EOVERFLOW;
-    if (reason_mask && !reason) return FP_EINVAL;
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict)) return FP_EINVAL;
-    if (n_cand && (!t_cpu || !t_mem || !t_labels || !summary_out)) return FP_EINVAL;
-    for (size_t k = 0; t_max && k < n_cand; ++k)
-        if (t_max[k] > max_new) return FP_EINVAL;
+    if (int rc = grow_checks(cs, reason, reason_mask, n_cand, t_cpu, t_mem, t_labels, t_max, max_new, summary_out))
+        return rc;
     if (n_cand == 0) return FP_OK;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
@@ -1123,8 +1078,19 @@ extern "C" int fp_grow_sweep(fp_ctx *c, const fp_containers *cs, const uint8_t *
     return copy_back_all(c, rows, n);
 }
 
-// the scale-out sweep under the policy (SPEC.md 2.18, fp_grow.hip).  relax_mask, quota and quota_used are host
-// arrays in both entries
+static fp_grow_policy grow_policy(const uint32_t *node_count, uint32_t strategy, uint32_t preferred_labels,
+                                  const uint32_t *domain, const uint32_t *t_domain, uint32_t max_skew,
+                                  const uint32_t *relax_mask, uint32_t n_hops, const uint32_t *quota,
+                                  const uint32_t *quota_used, uint32_t *policy_out, uint8_t *hops_out,
+                                  uint8_t *reason_out) {
+    fp_grow_policy p;
+    p.node_count = node_count; p.strategy = strategy; p.preferred = preferred_labels;
+    p.domain = domain; p.t_domain = t_domain; p.max_skew = max_skew;
+    p.relax_mask = relax_mask; p.n_hops = n_hops; p.quota = quota; p.quota_used = quota_used;
+    p.policy_out = policy_out; p.hops_out = hops_out; p.reason_out = reason_out;
+    return p;
+}
+
 extern "C" int fp_dev_grow_sweep_policy(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,
                                         const fp_nodes *ns, const uint32_t *node_count, uint32_t n_cand,
                                         const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
@@ -1138,11 +1104,8 @@ extern "C" int fp_dev_grow_sweep_policy(fp_ctx *c, const fp_containers *cs, cons
     if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
     if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
     FP_HIP(hipSetDevice(c->device));
-    fp_grow_policy pol;
-    pol.node_count = node_count; pol.strategy = strategy; pol.preferred = preferred_labels;
-    pol.domain = domain; pol.t_domain = t_domain; pol.max_skew = max_skew;
-    pol.relax_mask = relax_mask; pol.n_hops = n_hops; pol.quota = quota; pol.quota_used = quota_used;
-    pol.policy_out = policy_out; pol.hops_out = hops_out; pol.reason_out = reason_out;
+    const fp_grow_policy pol = grow_policy(node_count, strategy, preferred_labels, domain, t_domain, max_skew, relax_mask,
+                                           n_hops, quota, quota_used, policy_out, hops_out, reason_out);
     return fp_dev_done(c, fp_dev_grow_sweep_policy_impl(c, cs, reason, reason_mask, ns, n_cand, t_cpu, t_mem, t_labels,
                                                         t_max, max_new, summary_out, assign_out, pol));
 }
@@ -1156,20 +1119,16 @@ extern "C" int fp_grow_sweep_policy(fp_ctx *c, const fp_containers *cs, const ui
                                     const uint32_t *quota, const uint32_t *quota_used, uint32_t *summary_out,
                                     uint32_t *policy_out, uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out) {
     if (!c || !cs || !ns) return FP_EINVAL;
-    const size_t C = cs->n, N = ns->n;
+    const size_t N = ns->n;
     if (n_cand > 65535u || max_new > FP_GROW_MAX_NEW || N + max_new > FP_POLICY_MAX_NODES) return FP_EOVERFLOW;
     if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
     if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
-    if (reason_mask && !reason) return FP_EINVAL;
-    const bool sp = t_domain && max_skew != 0u;  // otherwise neither domain array is read
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict)) return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable)) return FP_EINVAL;
-    if (N && sp && !domain) return FP_EINVAL;
-    if (n_cand && (!t_cpu || !t_mem || !t_labels || !summary_out)) return FP_EINVAL;
-    for (size_t k = 0; k < n_cand; ++k)
-        if ((t_max && t_max[k] > max_new) || (sp && t_domain[k] >= (uint32_t)FP_SPREAD_MAX_DOMAINS)) return FP_EINVAL;
-    for (size_t n = 0; sp && n < N; ++n)
-        if (domain[n] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return FP_EINVAL;
+    if (int rc = grow_checks(cs, reason, reason_mask, n_cand, t_cpu, t_mem, t_labels, t_max, max_new, summary_out))
+        return rc;
+    if (N && !fp_has_nodes(ns)) return FP_EINVAL;
+    if (!t_domain || max_skew == 0u) domain = t_domain = nullptr;  // otherwise neither domain array is read
+    if (N && t_domain && !domain) return FP_EINVAL;
+    if (t_domain && (!fp_domains_ok(t_domain, n_cand) || !fp_domains_ok(domain, N))) return FP_EINVAL;
     if (n_cand == 0) return FP_OK;
     FP_HIP(hipSetDevice(c->device));
     fp_host_err_scope es(c);
@@ -1178,14 +1137,12 @@ extern "C" int fp_grow_sweep_policy(fp_ctx *c, const fp_containers *cs, const ui
     fp_grow_dev d;
     fp_grow_policy_dev dp;
     const int n = fp_grow_policy_rows(cs, reason, reason_mask, ns, node_count, n_cand, t_cpu, t_mem, t_labels, t_max,
-                                      sp ? domain : nullptr, sp ? t_domain : nullptr, summary_out, policy_out,
-                                      assign_out, hops_out, reason_out, &d, &dp, rows);
+                                      domain, t_domain, summary_out, policy_out, assign_out, hops_out, reason_out, &d,
+                                      &dp, rows);
     if (int rc = stage_rows(c, rows, n, false)) return rc;
-    fp_grow_policy pol;
-    pol.node_count = dp.node_count; pol.strategy = strategy; pol.preferred = preferred_labels;
-    pol.domain = dp.domain; pol.t_domain = dp.t_domain; pol.max_skew = max_skew;
-    pol.relax_mask = relax_mask; pol.n_hops = n_hops; pol.quota = quota; pol.quota_used = quota_used;
-    pol.policy_out = dp.policy_out; pol.hops_out = dp.hops_out; pol.reason_out = dp.reason_out;
+    const fp_grow_policy pol = grow_policy(dp.node_count, strategy, preferred_labels, dp.domain, dp.t_domain, max_skew,
+                                           relax_mask, n_hops, quota, quota_used, dp.policy_out, dp.hops_out,
+                                           dp.reason_out);
     if (int rc = fp_dev_grow_sweep_policy_impl(c, &d.cs, d.reason, reason_mask, &dp.ns, n_cand, d.t_cpu, d.t_mem,
                                                d.t_labels, d.t_max, max_new, d.summary, d.assign_out, pol))
         return rc;

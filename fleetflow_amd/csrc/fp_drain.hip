@@ -482,10 +482,8 @@ int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
     if (pol.n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
     const bool sp = pol.domain && pol.max_skew != 0u;   // SPEC.md 2.15: otherwise domain is not read
     const bool fb = pol.relax_mask && pol.n_hops != 0u;  // relax_mask is a HOST array, read here
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict || !assign || !assign_out || !reason_out))
-        return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable || !group))
-        return FP_EINVAL;
+    if (C && (!fp_has_cont(cs) || !assign || !assign_out || !reason_out)) return FP_EINVAL;
+    if (N && (!fp_has_nodes(ns) || !group)) return FP_EINVAL;
     if (n_cand && !summary_out) return FP_EINVAL;
     if (C && assign_out == assign) return FP_EINVAL;  // every candidate reads the same base assignment
     if (C == 0 && n_cand == 0) return FP_OK;
@@ -554,17 +552,12 @@ int fp_dev_drain_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *
     a.assign_out = assign_out; a.reason_out = reason_out; a.summary = summary_out;
     a.bad = bad;
     a.domain = sp ? pol.domain : nullptr; a.max_skew = sp ? pol.max_skew : 0u;
-    uint32_t cum = 0;  // keep[h] = ~cum[h + 1]; past n_hops the last one repeats (k_policy's keep)
-    for (uint32_t h = 0; h < FP_FALLBACK_MAX_HOPS; ++h) {
-        if (fb && h < pol.n_hops) cum |= pol.relax_mask[h];
-        a.keep[h] = ~cum;
-    }
+    fp_keep_masks(pol.relax_mask, pol.n_hops, fb, a.keep);
     a.hops = pol.hops_out; a.policy = pol.policy_out;
     fp_prof_begin(c, FP_K_PLACE, &ev);
-    if (sp && fb) launch_drain<true, true>(a, n_cand, N, st);
-    else if (sp) launch_drain<true, false>(a, n_cand, N, st);
-    else if (fb) launch_drain<false, true>(a, n_cand, N, st);
-    else launch_drain<false, false>(a, n_cand, N, st);
+    fp_with_flags(sp, fb, [&](auto SP, auto FB) {
+        launch_drain<decltype(SP)::value, decltype(FB)::value>(a, n_cand, N, st);
+    });
     FP_HIP(hipGetLastError());
     fp_prof_end(c, FP_K_PLACE, ev);
     return FP_OK;

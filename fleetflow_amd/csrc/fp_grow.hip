@@ -753,7 +753,7 @@ int fp_dev_grow_sweep_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *re
     c->last_rng = nullptr;  // this call recycles the workspace the last placement's range words live in
     if (n_cand > 65535u || max_new > FP_GROW_MAX_NEW) return FP_EOVERFLOW;
     if (reason_mask && !reason) return FP_EINVAL;
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict)) return FP_EINVAL;
+    if (C && !fp_has_cont(cs)) return FP_EINVAL;
     if (n_cand && (!t_cpu || !t_mem || !t_labels || !summary_out)) return FP_EINVAL;
     if (n_cand == 0) return FP_OK;
     hipStream_t st = c->stream;
@@ -796,8 +796,8 @@ int fp_dev_grow_sweep_policy_impl(fp_ctx *c, const fp_containers *cs, const uint
     if (reason_mask && !reason) return FP_EINVAL;
     const bool sp = pol.t_domain && pol.max_skew != 0u;  // SPEC.md 2.18: otherwise neither domain array is read
     const bool fb = pol.relax_mask && pol.n_hops != 0u;  // relax_mask is a HOST array, read here
-    if (C && (!cs->cpu_m || !cs->mem_mib || !cs->req_labels || !cs->conflict)) return FP_EINVAL;
-    if (N && (!ns->cpu_free || !ns->mem_free || !ns->labels || !ns->conflict_used || !ns->schedulable)) return FP_EINVAL;
+    if (C && !fp_has_cont(cs)) return FP_EINVAL;
+    if (N && !fp_has_nodes(ns)) return FP_EINVAL;
     if (N && sp && !pol.domain) return FP_EINVAL;
     if (n_cand && (!t_cpu || !t_mem || !t_labels || !summary_out)) return FP_EINVAL;
     if (n_cand == 0) return FP_OK;
@@ -820,11 +820,7 @@ int fp_dev_grow_sweep_policy_impl(fp_ctx *c, const fp_containers *cs, const uint
     a.labels = ns->labels; a.schedulable = ns->schedulable; a.node_count = pol.node_count;
     a.t_cpu = t_cpu; a.t_mem = t_mem; a.t_lab = t_labels; a.t_max = t_max;
     a.domain = sp ? pol.domain : nullptr; a.t_dom = sp ? pol.t_domain : nullptr; a.max_skew = sp ? pol.max_skew : 0u;
-    uint32_t cum = 0;  // keep[h] = ~cum[h + 1]; past n_hops the last one repeats (k_policy's keep)
-    for (uint32_t h = 0; h < FP_FALLBACK_MAX_HOPS; ++h) {
-        if (fb && h < pol.n_hops) cum |= pol.relax_mask[h];
-        a.keep[h] = ~cum;
-    }
+    fp_keep_masks(pol.relax_mask, pol.n_hops, fb, a.keep);
     // quota and quota_used are HOST arrays of three words: an absent quota is three caps of UNLIMITED
     for (uint32_t d = 0; d < FP_QUOTA_DIMS; ++d) {
         const uint32_t cap = pol.quota ? pol.quota[d] : FP_QUOTA_UNLIMITED;
@@ -843,10 +839,9 @@ int fp_dev_grow_sweep_policy_impl(fp_ctx *c, const fp_containers *cs, const uint
     }
     hipEvent_t ev;
     fp_prof_begin(c, FP_K_PLACE, &ev);
-    if (sp && fb) launch_grow_policy<true, true>(a, n_cand, st);
-    else if (sp) launch_grow_policy<true, false>(a, n_cand, st);
-    else if (fb) launch_grow_policy<false, true>(a, n_cand, st);
-    else launch_grow_policy<false, false>(a, n_cand, st);
+    fp_with_flags(sp, fb, [&](auto SP, auto FB) {
+        launch_grow_policy<decltype(SP)::value, decltype(FB)::value>(a, n_cand, st);
+    });
     FP_HIP(hipGetLastError());
     fp_prof_end(c, FP_K_PLACE, ev);
     return FP_OK;

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include <vector>
 #include "../../include/fleetplace.h"
 #include "fp_rows.h"
@@ -123,6 +124,43 @@ struct fp_host_err_scope {
     }
     ~fp_host_err_scope() { c->d_err = c->d_err_base; }
 };
+
+// ---- what the entry points and the *_impl functions ask of their arguments (host only) ----
+// t is an fp_containers, an fp_nodes or an fp_batch: its four container arrays / its five node arrays are there
+template <class T>
+static inline bool fp_has_cont(const T *t) { return t->cpu_m && t->mem_mib && t->req_labels && t->conflict; }
+template <class T>
+static inline bool fp_has_nodes(const T *t) {
+    return t->cpu_free && t->mem_free && t->labels && t->conflict_used && t->schedulable;
+}
+// host arrays: every entry is below `bound` or FP_NONE; every domain id is below FP_SPREAD_MAX_DOMAINS
+static inline bool fp_below_or_none(const uint32_t *x, size_t n, size_t bound) {
+    for (size_t i = 0; i < n; ++i)
+        if (x[i] >= bound && x[i] != FP_NONE) return false;
+    return true;
+}
+static inline bool fp_domains_ok(const uint32_t *domain, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (domain[i] >= (uint32_t)FP_SPREAD_MAX_DOMAINS) return false;
+    return true;
+}
+// The sweeps' fallback chain: keep[h] = ~cum[h + 1] over the HOST array relax_mask; past n_hops the last one
+// repeats (k_policy's keep), and without a chain (`fb` false) every keep is ~0
+static inline void fp_keep_masks(const uint32_t *relax_mask, uint32_t n_hops, bool fb, uint32_t *keep) {
+    uint32_t cum = 0;
+    for (uint32_t h = 0; h < FP_FALLBACK_MAX_HOPS; ++h) {
+        if (fb && h < n_hops) cum |= relax_mask[h];
+        keep[h] = ~cum;
+    }
+}
+// f(SP, FB) with the two host flags as std::bool_constant values: the sweeps' kernels are templates over them
+template <class F>
+static inline void fp_with_flags(bool sp, bool fb, F f) {
+    if (sp && fb) f(std::true_type(), std::true_type());
+    else if (sp) f(std::true_type(), std::false_type());
+    else if (fb) f(std::false_type(), std::true_type());
+    else f(std::false_type(), std::false_type());
+}
 
 static inline uint32_t fp_bitwidth(uint64_t v) {
     uint32_t b = 0;

@@ -100,23 +100,34 @@ static inline int fp_replan_rows(const fp_batch *b, const fp_policy_opts *o, con
     return n;
 }
 
-// one scenario's container and node tables as inputs (nine rows, in this order)
-static inline int fp_tables_rows(const fp_containers *cs, const fp_nodes *ns, fp_containers *dc, fp_nodes *dn,
-                                 fp_row *r) {
-    const size_t C = cs->n, N = ns->n;
+// one scenario's container table as inputs (four rows, in this order)
+static inline int fp_cont_rows(const fp_containers *cs, fp_containers *dc, fp_row *r) {
+    const size_t C = cs->n;
     *dc = *cs;
-    *dn = *ns;
     int n = 0;
     r[n++] = fp_row_in(cs->cpu_m, C, &dc->cpu_m);
     r[n++] = fp_row_in(cs->mem_mib, C, &dc->mem_mib);
     r[n++] = fp_row_in(cs->req_labels, C, &dc->req_labels);
     r[n++] = fp_row_in(cs->conflict, C, &dc->conflict);
+    return n;
+}
+// one scenario's node table as inputs (five rows, in this order)
+static inline int fp_node_rows(const fp_nodes *ns, fp_nodes *dn, fp_row *r) {
+    const size_t N = ns->n;
+    *dn = *ns;
+    int n = 0;
     r[n++] = fp_row_in(ns->cpu_free, N, &dn->cpu_free);
     r[n++] = fp_row_in(ns->mem_free, N, &dn->mem_free);
     r[n++] = fp_row_in(ns->labels, N, &dn->labels);
     r[n++] = fp_row_in(ns->conflict_used, N, &dn->conflict_used);
     r[n++] = fp_row_in(ns->schedulable, N, &dn->schedulable);
     return n;
+}
+// both tables: the container rows, then the node rows
+static inline int fp_tables_rows(const fp_containers *cs, const fp_nodes *ns, fp_containers *dc, fp_nodes *dn,
+                                 fp_row *r) {
+    const int n = fp_cont_rows(cs, dc, r);
+    return n + fp_node_rows(ns, dn, r + n);
 }
 
 // fp_drain_sweep: the tables, the live plan, the candidate groups, the counts; then the three results
@@ -215,18 +226,19 @@ struct fp_grow_dev {
     const uint32_t *t_cpu, *t_mem, *t_labels, *t_max;
     uint32_t *summary, *assign_out;
 };
+// the requests and their reasons (absent without a mask): what both grow lists begin with
+static inline int fp_grow_pending(const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask, fp_grow_dev *d,
+                                  fp_row *r) {
+    int n = fp_cont_rows(cs, &d->cs, r);
+    r[n++] = fp_row_in(reason_mask ? reason : nullptr, (size_t)cs->n, &d->reason);
+    return n;
+}
 static inline int fp_grow_rows(const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask, uint32_t n_cand,
                                const uint32_t *t_cpu, const uint32_t *t_mem, const uint32_t *t_labels,
                                const uint32_t *t_max, uint32_t *summary_out, uint32_t *assign_out, fp_grow_dev *d,
                                fp_row *r) {
     const size_t C = cs->n, K = n_cand;
-    d->cs = *cs;
-    int n = 0;
-    r[n++] = fp_row_in(cs->cpu_m, C, &d->cs.cpu_m);
-    r[n++] = fp_row_in(cs->mem_mib, C, &d->cs.mem_mib);
-    r[n++] = fp_row_in(cs->req_labels, C, &d->cs.req_labels);
-    r[n++] = fp_row_in(cs->conflict, C, &d->cs.conflict);
-    r[n++] = fp_row_in(reason_mask ? reason : nullptr, C, &d->reason);
+    int n = fp_grow_pending(cs, reason, reason_mask, d, r);
     r[n++] = fp_row_in(t_cpu, K, &d->t_cpu);
     r[n++] = fp_row_in(t_mem, K, &d->t_mem);
     r[n++] = fp_row_in(t_labels, K, &d->t_labels);
@@ -253,19 +265,8 @@ static inline int fp_grow_policy_rows(const fp_containers *cs, const uint8_t *re
                                       uint8_t *hops_out, uint8_t *reason_out, fp_grow_dev *d, fp_grow_policy_dev *dp,
                                       fp_row *r) {
     const size_t C = cs->n, N = ns->n, K = n_cand;
-    d->cs = *cs;
-    dp->ns = *ns;
-    int n = 0;
-    r[n++] = fp_row_in(cs->cpu_m, C, &d->cs.cpu_m);
-    r[n++] = fp_row_in(cs->mem_mib, C, &d->cs.mem_mib);
-    r[n++] = fp_row_in(cs->req_labels, C, &d->cs.req_labels);
-    r[n++] = fp_row_in(cs->conflict, C, &d->cs.conflict);
-    r[n++] = fp_row_in(reason_mask ? reason : nullptr, C, &d->reason);
-    r[n++] = fp_row_in(ns->cpu_free, N, &dp->ns.cpu_free);
-    r[n++] = fp_row_in(ns->mem_free, N, &dp->ns.mem_free);
-    r[n++] = fp_row_in(ns->labels, N, &dp->ns.labels);
-    r[n++] = fp_row_in(ns->conflict_used, N, &dp->ns.conflict_used);
-    r[n++] = fp_row_in(ns->schedulable, N, &dp->ns.schedulable);
+    int n = fp_grow_pending(cs, reason, reason_mask, d, r);
+    n += fp_node_rows(ns, &dp->ns, r + n);
     r[n++] = fp_row_in(node_count, N, &dp->node_count);
     r[n++] = fp_row_in(domain, N, &dp->domain);
     r[n++] = fp_row_in(t_cpu, K, &d->t_cpu);

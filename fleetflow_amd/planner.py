@@ -182,6 +182,60 @@ def _dev_policy_checks(db, strategy_t, preferred_t, count_t, domain_t, max_skew_
     return domain_t, max_skew_t, relax_mask_t, n_hops_t
 
 
+def _containers(cont):
+    """The container table alone (the scale-out sweep has no node table of its own), as ``_tables`` checks it."""
+    cont = tuple(_u32(x) for x in cont)
+    _need(len(cont) == 4 and all(x.size == cont[0].size for x in cont), "every container array must hold C entries")
+    return cont
+
+
+def _opt_n(a, n, what, size="N"):
+    """An optional u32 array of ``n`` entries (node_count, domain, t_max, ..): None stays None."""
+    if a is None:
+        return None
+    a = _u32(a).reshape(-1)
+    _need(a.size == n, f"{what} must hold {size} entries")
+    return a
+
+
+def _relax(relax_mask):
+    """A sweep's fallback chain: the masks as a list and as the u32 array the export reads (None when empty)."""
+    relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
+    _need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
+    return relax, _u32(relax) if relax else None
+
+
+def _skew_chain(max_skew, relax_mask):
+    """The scalar guarantees of a sweep under the policy, checked: (max_skew, relax_mask array or None, n_hops)."""
+    max_skew = int(max_skew)
+    _need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
+    relax, rm = _relax(relax_mask)
+    return max_skew, rm, len(relax)
+
+
+def _tensor(name, t, n, holds, size=4, optional=False):
+    """A device tensor of ``n`` entries of ``size`` bytes (``optional``: or None); ``holds`` is how the message
+    writes ``n``."""
+    _need((optional and t is None) or (t.numel() == n and t.element_size() == size),
+          f"{name} must hold {holds} " + ("32-bit entries" if size == 4 else "bytes"))
+
+
+def _dev_tables_checks(cont_t, nodes_t=None):
+    """The container and node tensors of a dev_*_sweep call, checked: (C, N, FpContainers, FpNodes); without
+    ``nodes_t`` N and the node struct are None."""
+    C = cont_t[0].numel()
+    N = nodes_t[0].numel() if nodes_t is not None else None
+    _need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
+          "every container tensor must hold C 32-bit entries")
+    cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
+    if nodes_t is None:
+        return C, None, cs, None
+    _need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
+          and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
+          "every node tensor must hold N entries (schedulable N bytes)")
+    return C, N, cs, FpNodes(N, *(t.data_ptr() for t in nodes_t))
+
+
 def strategy_id(strategy) -> int:
     """An fp_strategy value from an int or one of the control plane's policy strings
     (``spread_across_pool``, ``pack_into_dedicated``, ``fill_lowest``).  An int is passed on as it is
@@ -613,6 +667,101 @@ class Planner:
               "fp_explain_batch")
         return hist
 
+    # The sweeps: a plain method and its policy twin share one body.  ``policy`` is what the twin's signature adds
+    # (None for the plain method); the plain call differs only in the export and in the absence of the policy
+    # suffix of arguments and results.
+    def _call(self, export, *args, dev=False):
+        fn = lambda: check(getattr(self._L, export)(self._ctx, *args), export)  # noqa: E731
+        return self._dev(fn) if dev else fn()
+
+    def _drain_host(self, cont, nodes, assign, group, n_cand, strategy, preferred, node_count, policy=None):
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
+        asg, grp = _u32(assign), _u32(group)
+        n_cand, strategy = int(n_cand), strategy_id(strategy)
+        _need(asg.size == C, "assign must hold C entries")
+        _need(grp.size == N, "group must hold N entries")
+        nc = _opt_n(node_count, N, "node_count")
+        dom = _opt_n(policy[0], N, "domain") if policy else None
+        _need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
+        out, reason = np.empty(C, np.uint32), np.empty(C, np.uint8)
+        summary = np.empty((n_cand, _lib.DRAIN_WORDS), np.uint32)
+        cs, ns = _pair(cont, nodes)
+        head = (ct.byref(cs), ct.byref(ns), _arg(asg), _arg(grp), n_cand, strategy, int(preferred) & 0xFFFFFFFF, _arg(nc))
+        if policy is None:
+            self._call("fp_drain_sweep", *head, _arg(out), _arg(reason), _arg(summary))
+            return out, reason, summary
+        max_skew, rm, n_hops = _skew_chain(*policy[1:])
+        hops, rows = np.empty(C, np.uint8), np.empty((n_cand, _lib.DRAIN_POLICY_WORDS), np.uint32)
+        self._call("fp_drain_sweep_policy", *head, _arg(dom), max_skew, _arg(rm), n_hops, _arg(out), _arg(reason),
+                   _arg(hops), _arg(summary), _arg(rows))
+        return out, reason, summary, hops, rows
+
+    def _shrink_host(self, cont, nodes, assign, try_order, strategy, preferred, node_count, policy=None):
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
+        asg, tro = _u32(assign), _u32(try_order)
+        _need(tro.ndim == 2, "try_order must be [n_var, n_try]")
+        n_var, n_try = tro.shape
+        strategy = strategy_id(strategy)
+        _need(asg.size == C, "assign must hold C entries")
+        nc = _opt_n(node_count, N, "node_count")
+        out, state = np.empty((n_var, C), np.uint32), np.empty((n_var, N), np.uint8)
+        blocker, summary = np.empty((n_var, N), np.uint32), np.empty((n_var, _lib.SHRINK_WORDS), np.uint32)
+        cs, ns = _pair(cont, nodes)
+        head = (ct.byref(cs), ct.byref(ns), _arg(asg), _arg(tro), n_var, n_try, strategy, int(preferred) & 0xFFFFFFFF,
+                _arg(nc))
+        outs = (_arg(out), _arg(state), _arg(blocker), _arg(summary))
+        if policy is None:
+            self._call("fp_shrink_sweep", *head, *outs)
+            return out, state, blocker, summary
+        dom = _opt_n(policy[0], N, "domain")
+        max_skew, rm, n_hops = _skew_chain(*policy[1:])
+        hops, why = np.empty((n_var, C), np.uint8), np.empty((n_var, N), np.uint8)
+        rows = np.empty((n_var, _lib.SHRINK_POLICY_WORDS), np.uint32)
+        self._call("fp_shrink_sweep_policy", *head, _arg(dom), max_skew, _arg(rm), n_hops, *outs, _arg(hops), _arg(why),
+                   _arg(rows))
+        return out, state, blocker, summary, hops, why, rows
+
+    def _grow_host(self, cont, reason, templates, max_new, reason_mask, t_max, want_assign, policy=None):
+        cont = _containers(cont)
+        C = cont[0].size
+        if policy is not None:
+            nodes, strategy, preferred, node_count, domain, t_domain, max_skew, relax_mask, quota, quota_used = policy
+            cont, live = _tables(cont, nodes, None, None, False)
+            N = live[0].size
+        tpl = tuple(_u32(x).reshape(-1) for x in templates)
+        _need(len(tpl) == 3, "templates must be (t_cpu, t_mem, t_labels)")
+        n_cand = tpl[0].size
+        _need(all(x.size == n_cand for x in tpl), "every template array must hold n_cand entries")
+        rs = _u8(reason) if reason is not None else None
+        reason_mask, max_new = int(reason_mask), int(max_new)
+        _need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
+        _need(reason_mask == 0 or rs is None or rs.size == C, "reason must hold C entries")
+        _need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
+        tm = _opt_n(t_max, n_cand, "t_max", "n_cand")
+        summary = np.empty((n_cand, _lib.GROW_WORDS), np.uint32)
+        assign = np.empty((n_cand, C), np.uint32) if want_assign else None
+        cs = FpContainers(C, *(_ptr(x) for x in cont))
+        head = (ct.byref(cs), _arg(rs if reason_mask else None), reason_mask)
+        tail = (n_cand, _arg(tpl[0]), _arg(tpl[1]), _arg(tpl[2]), _arg(tm), max_new)
+        if policy is None:
+            self._call("fp_grow_sweep", *head, *tail, _arg(summary), _arg(assign))
+            return summary, assign
+        nc = _opt_n(node_count, N, "node_count")
+        dom, td = _opt_n(domain, N, "domain"), _opt_n(t_domain, n_cand, "t_domain", "n_cand")
+        max_skew, rm, n_hops = _skew_chain(max_skew, relax_mask)
+        qt = _quota_rows(quota, 1) if quota is not None else None
+        qu = _opt_n(quota_used, _lib.QUOTA_DIMS, "quota_used", "3")
+        rows = np.empty((n_cand, _lib.GROW_POLICY_WORDS), np.uint32)
+        hops = np.empty((n_cand, C), np.uint8) if want_assign else None
+        why = np.empty((n_cand, C), np.uint8) if want_assign else None
+        ns = FpNodes(N, *(_ptr(x) for x in live))
+        self._call("fp_grow_sweep_policy", *head, ct.byref(ns), _arg(nc), *tail, strategy_id(strategy),
+                   int(preferred) & 0xFFFFFFFF, _arg(dom), _arg(td), max_skew, _arg(rm), n_hops, _arg(qt), _arg(qu),
+                   _arg(summary), _arg(rows), _arg(assign), _arg(hops), _arg(why))
+        return summary, rows, assign, hops, why
+
     def drain_sweep(self, cont, nodes, assign, group, n_cand, strategy=0, preferred=0, node_count=None):
         """Drain what-if sweep (SPEC.md 2.11, fp_drain_sweep): ``nodes`` is the live table, ``assign`` [C] the
         node each container runs on (NONE = not running), ``group`` [N] the candidate each node belongs to
@@ -620,23 +769,7 @@ class Planner:
         same base state, on the schedulable nodes outside the candidate under ``strategy`` / ``preferred``
         (SPEC.md 2.6) and ``node_count`` ([N] or None = zeros).  Inputs are not mutated.  Returns
         (assign_out [C], reason [C], summary [n_cand, 8]); summary's word indices are _lib.DRAIN_*."""
-        cont, nodes = _tables(cont, nodes, None, None, False)
-        C, N = cont[0].size, nodes[0].size
-        asg, grp = _u32(assign), _u32(group)
-        nc = _u32(node_count) if node_count is not None else None
-        n_cand, strategy = int(n_cand), strategy_id(strategy)
-        self._need(asg.size == C, "assign must hold C entries")
-        self._need(grp.size == N, "group must hold N entries")
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
-        out = np.empty(C, np.uint32)
-        reason = np.empty(C, np.uint8)
-        summary = np.empty((n_cand, _lib.DRAIN_WORDS), np.uint32)
-        cs, ns = _pair(cont, nodes)
-        check(self._L.fp_drain_sweep(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(grp), n_cand,
-                                     strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(out), _arg(reason),
-                                     _arg(summary)), "fp_drain_sweep")
-        return out, reason, summary
+        return self._drain_host(cont, nodes, assign, group, n_cand, strategy, preferred, node_count)
 
     def drain_sweep_policy(self, cont, nodes, assign, group, n_cand, strategy=0, preferred=0, node_count=None, *,
                            domain=None, max_skew=0, relax_mask=()):
@@ -647,32 +780,8 @@ class Planner:
         eligible when it has a target.  There is no quota: a move releases and retakes the same request.
         Returns (assign_out [C], reason [C] with REASON_SKEW beside REASON_NOFIT, summary [n_cand, 8], hops
         [C], policy_rows [n_cand, 4]); the policy rows' word indices are _lib.DRAIN_STRANDED_SKEW, .."""
-        cont, nodes = _tables(cont, nodes, None, None, False)
-        C, N = cont[0].size, nodes[0].size
-        asg, grp = _u32(assign), _u32(group)
-        nc = _u32(node_count) if node_count is not None else None
-        dom = _u32(domain) if domain is not None else None
-        n_cand, strategy, max_skew = int(n_cand), strategy_id(strategy), int(max_skew)
-        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
-        self._need(asg.size == C, "assign must hold C entries")
-        self._need(grp.size == N, "group must hold N entries")
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        self._need(dom is None or dom.size == N, "domain must hold N entries")
-        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
-        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
-        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
-        rm = _u32(relax) if relax else None
-        out = np.empty(C, np.uint32)
-        reason = np.empty(C, np.uint8)
-        hops = np.empty(C, np.uint8)
-        summary = np.empty((n_cand, _lib.DRAIN_WORDS), np.uint32)
-        rows = np.empty((n_cand, _lib.DRAIN_POLICY_WORDS), np.uint32)
-        cs, ns = _pair(cont, nodes)
-        check(self._L.fp_drain_sweep_policy(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(grp), n_cand,
-                                            strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(dom), max_skew,
-                                            _arg(rm), len(relax), _arg(out), _arg(reason), _arg(hops), _arg(summary),
-                                            _arg(rows)), "fp_drain_sweep_policy")
-        return out, reason, summary, hops, rows
+        return self._drain_host(cont, nodes, assign, group, n_cand, strategy, preferred, node_count,
+                                (domain, max_skew, relax_mask))
 
     def drain(self, cont, nodes, assign, drain_mask, strategy=0, preferred=0, node_count=None):
         """Evacuate the nodes of ``drain_mask`` ([N], non-zero = drained) from a live plan: one drain_sweep
@@ -710,25 +819,7 @@ class Planner:
         when all fit the node is released, otherwise the attempt is undone.  Inputs are not mutated.  Returns
         (assign_out [n_var, C], state [n_var, N] of _lib.SHRINK_STATE_*, blocker [n_var, N], summary [n_var, 8]);
         summary's word indices are _lib.SHRINK_*."""
-        cont, nodes = _tables(cont, nodes, None, None, False)
-        C, N = cont[0].size, nodes[0].size
-        asg = _u32(assign)
-        tro = _u32(try_order)
-        self._need(tro.ndim == 2, "try_order must be [n_var, n_try]")
-        n_var, n_try = tro.shape
-        nc = _u32(node_count) if node_count is not None else None
-        strategy = strategy_id(strategy)
-        self._need(asg.size == C, "assign must hold C entries")
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        out = np.empty((n_var, C), np.uint32)
-        state = np.empty((n_var, N), np.uint8)
-        blocker = np.empty((n_var, N), np.uint32)
-        summary = np.empty((n_var, _lib.SHRINK_WORDS), np.uint32)
-        cs, ns = _pair(cont, nodes)
-        check(self._L.fp_shrink_sweep(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(tro), n_var, n_try,
-                                      strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(out), _arg(state),
-                                      _arg(blocker), _arg(summary)), "fp_shrink_sweep")
-        return out, state, blocker, summary
+        return self._shrink_host(cont, nodes, assign, try_order, strategy, preferred, node_count)
 
     def shrink_sweep_policy(self, cont, nodes, assign, try_order, strategy=0, preferred=0, node_count=None, *,
                             domain=None, max_skew=0, relax_mask=()):
@@ -742,35 +833,8 @@ class Planner:
         [n_var, C], state [n_var, N], blocker [n_var, N], summary [n_var, 8], hops [n_var, C], blocker_reason
         [n_var, N] with REASON_SKEW beside REASON_NOFIT, policy_rows [n_var, 4]); the policy rows' word indices
         are _lib.SHRINK_FAILED_SKEW, .."""
-        cont, nodes = _tables(cont, nodes, None, None, False)
-        C, N = cont[0].size, nodes[0].size
-        asg = _u32(assign)
-        tro = _u32(try_order)
-        self._need(tro.ndim == 2, "try_order must be [n_var, n_try]")
-        n_var, n_try = tro.shape
-        nc = _u32(node_count) if node_count is not None else None
-        dom = _u32(domain) if domain is not None else None
-        strategy, max_skew = strategy_id(strategy), int(max_skew)
-        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
-        self._need(asg.size == C, "assign must hold C entries")
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        self._need(dom is None or dom.size == N, "domain must hold N entries")
-        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
-        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
-        rm = _u32(relax) if relax else None
-        out = np.empty((n_var, C), np.uint32)
-        state = np.empty((n_var, N), np.uint8)
-        blocker = np.empty((n_var, N), np.uint32)
-        summary = np.empty((n_var, _lib.SHRINK_WORDS), np.uint32)
-        hops = np.empty((n_var, C), np.uint8)
-        why = np.empty((n_var, N), np.uint8)
-        rows = np.empty((n_var, _lib.SHRINK_POLICY_WORDS), np.uint32)
-        cs, ns = _pair(cont, nodes)
-        check(self._L.fp_shrink_sweep_policy(self._ctx, ct.byref(cs), ct.byref(ns), _arg(asg), _arg(tro), n_var, n_try,
-                                             strategy, int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(dom), max_skew,
-                                             _arg(rm), len(relax), _arg(out), _arg(state), _arg(blocker), _arg(summary),
-                                             _arg(hops), _arg(why), _arg(rows)), "fp_shrink_sweep_policy")
-        return out, state, blocker, summary, hops, why, rows
+        return self._shrink_host(cont, nodes, assign, try_order, strategy, preferred, node_count,
+                                 (domain, max_skew, relax_mask))
 
     def grow_sweep(self, cont, reason, templates, max_new, reason_mask=1 << _lib.REASON_NOFIT, t_max=None,
                    want_assign=False):
@@ -782,27 +846,7 @@ class Planner:
         Returns (summary [n_cand, 8], assign): summary's word indices are _lib.GROW_*, and assign is
         [n_cand, C] with ``want_assign`` (the ordinal of the new server of a placed pending container, NONE
         for every other one), else None."""
-        cont = tuple(_u32(x) for x in cont)
-        C = cont[0].size
-        self._need(len(cont) == 4 and all(x.size == C for x in cont), "every container array must hold C entries")
-        tpl = tuple(_u32(x).reshape(-1) for x in templates)
-        self._need(len(tpl) == 3, "templates must be (t_cpu, t_mem, t_labels)")
-        n_cand = tpl[0].size
-        self._need(all(x.size == n_cand for x in tpl), "every template array must hold n_cand entries")
-        rs = _u8(reason) if reason is not None else None
-        reason_mask, max_new = int(reason_mask), int(max_new)
-        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
-        self._need(reason_mask == 0 or rs is None or rs.size == C, "reason must hold C entries")
-        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
-        tm = _u32(t_max).reshape(-1) if t_max is not None else None
-        self._need(tm is None or tm.size == n_cand, "t_max must hold n_cand entries")
-        summary = np.empty((n_cand, _lib.GROW_WORDS), np.uint32)
-        assign = np.empty((n_cand, C), np.uint32) if want_assign else None
-        cs = FpContainers(C, *(_ptr(x) for x in cont))
-        check(self._L.fp_grow_sweep(self._ctx, ct.byref(cs), _arg(rs if reason_mask else None), reason_mask, n_cand,
-                                    _arg(tpl[0]), _arg(tpl[1]), _arg(tpl[2]), _arg(tm), max_new, _arg(summary),
-                                    _arg(assign)), "fp_grow_sweep")
-        return summary, assign
+        return self._grow_host(cont, reason, templates, max_new, reason_mask, t_max, want_assign)
 
     def grow_sweep_policy(self, cont, reason, nodes, templates, max_new, reason_mask=1 << _lib.REASON_NOFIT,
                           t_max=None, strategy=0, preferred=0, node_count=None, *, domain=None, t_domain=None,
@@ -818,52 +862,104 @@ class Planner:
         policy_rows [n_cand, 8], assign, hops, reason): the policy rows' word indices are _lib.GROW_ON_LIVE, ..;
         the last three are [n_cand, C] with ``want_assign`` (assign = the node in the combined table, N + j the
         j-th new server, NONE for every container that is not pending or not placed), else None."""
-        cont = tuple(_u32(x) for x in cont)
-        C = cont[0].size
-        self._need(len(cont) == 4 and all(x.size == C for x in cont), "every container array must hold C entries")
-        cf, mf, lab, cu = (_u32(x).reshape(-1) for x in nodes[:4])
-        live = (cf, mf, lab, cu, _u8(nodes[4]).reshape(-1))
-        N = cf.size
-        self._need(all(x.size == N for x in live), "every node array must hold N entries")
-        tpl = tuple(_u32(x).reshape(-1) for x in templates)
-        self._need(len(tpl) == 3, "templates must be (t_cpu, t_mem, t_labels)")
-        n_cand = tpl[0].size
-        self._need(all(x.size == n_cand for x in tpl), "every template array must hold n_cand entries")
-        rs = _u8(reason) if reason is not None else None
-        reason_mask, max_new, max_skew, strategy = int(reason_mask), int(max_new), int(max_skew), strategy_id(strategy)
-        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
-        self._need(reason_mask == 0 or rs is None or rs.size == C, "reason must hold C entries")
-        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
-        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
-        tm = _u32(t_max).reshape(-1) if t_max is not None else None
-        self._need(tm is None or tm.size == n_cand, "t_max must hold n_cand entries")
-        nc = _u32(node_count).reshape(-1) if node_count is not None else None
-        self._need(nc is None or nc.size == N, "node_count must hold N entries")
-        dom = _u32(domain).reshape(-1) if domain is not None else None
-        td = _u32(t_domain).reshape(-1) if t_domain is not None else None
-        self._need(dom is None or dom.size == N, "domain must hold N entries")
-        self._need(td is None or td.size == n_cand, "t_domain must hold n_cand entries")
-        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
-        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
-        rm = _u32(relax) if relax else None
-        qt = _quota_rows(quota, 1) if quota is not None else None
-        qu = _u32(quota_used).reshape(-1) if quota_used is not None else None
-        self._need(qu is None or qu.size == _lib.QUOTA_DIMS, "quota_used must hold 3 entries")
-        summary = np.empty((n_cand, _lib.GROW_WORDS), np.uint32)
-        rows = np.empty((n_cand, _lib.GROW_POLICY_WORDS), np.uint32)
-        assign = np.empty((n_cand, C), np.uint32) if want_assign else None
-        hops = np.empty((n_cand, C), np.uint8) if want_assign else None
-        why = np.empty((n_cand, C), np.uint8) if want_assign else None
-        cs = FpContainers(C, *(_ptr(x) for x in cont))
-        ns = FpNodes(N, *(_ptr(x) for x in live))
-        check(self._L.fp_grow_sweep_policy(
-            self._ctx, ct.byref(cs), _arg(rs if reason_mask else None), reason_mask, ct.byref(ns), _arg(nc), n_cand,
-            _arg(tpl[0]), _arg(tpl[1]), _arg(tpl[2]), _arg(tm), max_new, strategy, int(preferred) & 0xFFFFFFFF,
-            _arg(dom), _arg(td), max_skew, _arg(rm), len(relax), _arg(qt), _arg(qu), _arg(summary), _arg(rows),
-            _arg(assign), _arg(hops), _arg(why)), "fp_grow_sweep_policy")
-        return summary, rows, assign, hops, why
+        return self._grow_host(cont, reason, templates, max_new, reason_mask, t_max, want_assign,
+                               (nodes, strategy, preferred, node_count, domain, t_domain, max_skew, relax_mask, quota,
+                                quota_used))
 
     # -- device-pointer API -------------------------------------------------------------
+    def _grow_dev(self, cont_t, reason_t, templates_t, max_new, summary_t, reason_mask, t_max_t, assign_out_t,
+                  policy=None):
+        if policy is None:
+            C, _, cs, _ = _dev_tables_checks(cont_t)
+        else:
+            (nodes_t, strategy, preferred, count_t, domain_t, t_domain_t, max_skew, relax_mask, quota, quota_used,
+             policy_t, hops_t, reason_out_t) = policy
+            C, N, cs, ns = _dev_tables_checks(cont_t, nodes_t)
+        _need(len(templates_t) == 3, "templates_t must be (t_cpu, t_mem, t_labels)")
+        n_cand = templates_t[0].numel()
+        _need(all(t.numel() == n_cand and t.element_size() == 4 for t in templates_t),
+              "every template tensor must hold n_cand 32-bit entries")
+        reason_mask, max_new = int(reason_mask), int(max_new)
+        _need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
+        _need(reason_mask == 0 or reason_t is None or (reason_t.numel() == C and reason_t.element_size() == 1),
+              "reason_t must hold C bytes")
+        _need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
+        _tensor("t_max_t", t_max_t, n_cand, "n_cand", optional=True)
+        _tensor("summary_t", summary_t, n_cand * _lib.GROW_WORDS, "n_cand * 8")
+        _tensor("assign_out_t", assign_out_t, n_cand * C, "n_cand * C", optional=True)
+        head = (ct.byref(cs), _arg(reason_t if reason_mask else None), reason_mask)
+        tail = (n_cand, *(_arg(t) for t in templates_t), _arg(t_max_t), max_new)
+        if policy is None:
+            return self._call("fp_dev_grow_sweep", *head, *tail, _arg(summary_t), _arg(assign_out_t), dev=True)
+        _tensor("count_t", count_t, N, "N", optional=True)
+        _tensor("domain_t", domain_t, N, "N", optional=True)
+        _tensor("t_domain_t", t_domain_t, n_cand, "n_cand", optional=True)
+        max_skew, rm, n_hops = _skew_chain(max_skew, relax_mask)  # the three host arrays are read during the call
+        _tensor("policy_t", policy_t, n_cand * _lib.GROW_POLICY_WORDS, "n_cand * 8", optional=True)
+        _tensor("hops_t", hops_t, n_cand * C, "n_cand * C", 1, True)
+        _tensor("reason_out_t", reason_out_t, n_cand * C, "n_cand * C", 1, True)
+        qt = _quota_rows(quota, 1) if quota is not None else None
+        qu = _opt_n(quota_used, _lib.QUOTA_DIMS, "quota_used", "3")
+        self._call("fp_dev_grow_sweep_policy", *head, ct.byref(ns), _arg(count_t), *tail, strategy_id(strategy),
+                   int(preferred) & 0xFFFFFFFF, _arg(domain_t), _arg(t_domain_t), max_skew, _arg(rm), n_hops, _arg(qt),
+                   _arg(qu), _arg(summary_t), _arg(policy_t), _arg(assign_out_t), _arg(hops_t), _arg(reason_out_t),
+                   dev=True)
+
+    def _drain_dev(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t, strategy,
+                   preferred, count_t, policy=None):
+        n_cand, strategy = int(n_cand), strategy_id(strategy)
+        C, N, cs, ns = _dev_tables_checks(cont_t, nodes_t)
+        _tensor("assign_t", assign_t, C, "C")
+        _tensor("group_t", group_t, N, "N")
+        _tensor("count_t", count_t, N, "N", optional=True)
+        if policy is not None:
+            domain_t, max_skew, relax_mask, hops_t, policy_t = policy
+            _tensor("domain_t", domain_t, N, "N", optional=True)
+        _need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
+        if policy is not None:
+            max_skew, rm, n_hops = _skew_chain(max_skew, relax_mask)  # rm is read during the call
+        _tensor("assign_out_t", assign_out_t, C, "C")
+        _tensor("reason_t", reason_t, C, "C", 1)
+        _tensor("summary_t", summary_t, n_cand * _lib.DRAIN_WORDS, "n_cand * 8")
+        head = (ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(group_t), n_cand, strategy, int(preferred) & 0xFFFFFFFF,
+                _arg(count_t))
+        if policy is None:
+            return self._call("fp_dev_drain_sweep", *head, _arg(assign_out_t), _arg(reason_t), _arg(summary_t), dev=True)
+        _tensor("hops_t", hops_t, C, "C", 1, True)
+        _tensor("policy_t", policy_t, n_cand * _lib.DRAIN_POLICY_WORDS, "n_cand * 4", optional=True)
+        self._call("fp_dev_drain_sweep_policy", *head, _arg(domain_t), max_skew, _arg(rm), n_hops, _arg(assign_out_t),
+                   _arg(reason_t), _arg(hops_t), _arg(summary_t), _arg(policy_t), dev=True)
+
+    def _shrink_dev(self, cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t, strategy,
+                    preferred, count_t, blocker_t, policy=None):
+        n_var, strategy = int(n_var), strategy_id(strategy)
+        C, N, cs, ns = _dev_tables_checks(cont_t, nodes_t)
+        _tensor("assign_t", assign_t, C, "C")
+        _need(0 <= n_var <= 0xFFFFFFFF, "n_var must be a u32")
+        _need(try_order_t.element_size() == 4 and (try_order_t.numel() % n_var == 0 if n_var
+                                                   else try_order_t.numel() == 0),
+              "try_order_t must hold n_var rows of 32-bit entries")
+        n_try = try_order_t.numel() // n_var if n_var else 0
+        _tensor("count_t", count_t, N, "N", optional=True)
+        if policy is not None:
+            domain_t, max_skew, relax_mask, hops_t, blocker_reason_t, policy_t = policy
+            _tensor("domain_t", domain_t, N, "N", optional=True)
+            max_skew, rm, n_hops = _skew_chain(max_skew, relax_mask)  # rm is read during the call
+        _tensor("assign_out_t", assign_out_t, n_var * C, "n_var * C")
+        _tensor("state_t", state_t, n_var * N, "n_var * N", 1)
+        _tensor("blocker_t", blocker_t, n_var * N, "n_var * N", optional=True)
+        _tensor("summary_t", summary_t, n_var * _lib.SHRINK_WORDS, "n_var * 8")
+        head = (ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(try_order_t), n_var, n_try, strategy,
+                int(preferred) & 0xFFFFFFFF, _arg(count_t))
+        outs = (_arg(assign_out_t), _arg(state_t), _arg(blocker_t), _arg(summary_t))
+        if policy is None:
+            return self._call("fp_dev_shrink_sweep", *head, *outs, dev=True)
+        _tensor("hops_t", hops_t, n_var * C, "n_var * C", 1, True)
+        _tensor("blocker_reason_t", blocker_reason_t, n_var * N, "n_var * N", 1, True)
+        _tensor("policy_t", policy_t, n_var * _lib.SHRINK_POLICY_WORDS, "n_var * 4", optional=True)
+        self._call("fp_dev_shrink_sweep_policy", *head, _arg(domain_t), max_skew, _arg(rm), n_hops, *outs, _arg(hops_t),
+                   _arg(blocker_reason_t), _arg(policy_t), dev=True)
+
     def dev_grow_sweep_policy(self, cont_t, reason_t, nodes_t, templates_t, max_new, summary_t,
                               reason_mask=1 << _lib.REASON_NOFIT, t_max_t=None, strategy=0, preferred=0, count_t=None, *,
                               domain_t=None, t_domain_t=None, max_skew=0, relax_mask=(), quota=None, quota_used=None,
@@ -875,53 +971,9 @@ class Planner:
         ``max_new``, ``max_skew``, ``relax_mask``, ``quota`` and ``quota_used`` are host values.  A t_max above
         max_new or a domain value out of range is found on the device: nothing is written and sync() raises
         FP_EINVAL."""
-        C, N = cont_t[0].numel(), nodes_t[0].numel()
-        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
-                   "every container tensor must hold C 32-bit entries")
-        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
-                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
-                   "every node tensor must hold N entries (schedulable N bytes)")
-        self._need(len(templates_t) == 3, "templates_t must be (t_cpu, t_mem, t_labels)")
-        n_cand = templates_t[0].numel()
-        self._need(all(t.numel() == n_cand and t.element_size() == 4 for t in templates_t),
-                   "every template tensor must hold n_cand 32-bit entries")
-        reason_mask, max_new, max_skew, strategy = int(reason_mask), int(max_new), int(max_skew), strategy_id(strategy)
-        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
-        self._need(reason_mask == 0 or reason_t is None or (reason_t.numel() == C and reason_t.element_size() == 1),
-                   "reason_t must hold C bytes")
-        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
-        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
-        self._need(t_max_t is None or (t_max_t.numel() == n_cand and t_max_t.element_size() == 4),
-                   "t_max_t must hold n_cand 32-bit entries")
-        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
-                   "count_t must hold N 32-bit entries")
-        self._need(domain_t is None or (domain_t.numel() == N and domain_t.element_size() == 4),
-                   "domain_t must hold N 32-bit entries")
-        self._need(t_domain_t is None or (t_domain_t.numel() == n_cand and t_domain_t.element_size() == 4),
-                   "t_domain_t must hold n_cand 32-bit entries")
-        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
-        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
-        self._need(summary_t.numel() == n_cand * _lib.GROW_WORDS and summary_t.element_size() == 4,
-                   "summary_t must hold n_cand * 8 32-bit entries")
-        self._need(policy_t is None or (policy_t.numel() == n_cand * _lib.GROW_POLICY_WORDS
-                                        and policy_t.element_size() == 4),
-                   "policy_t must hold n_cand * 8 32-bit entries")
-        self._need(assign_out_t is None or (assign_out_t.numel() == n_cand * C and assign_out_t.element_size() == 4),
-                   "assign_out_t must hold n_cand * C 32-bit entries")
-        for name, x in (("hops_t", hops_t), ("reason_out_t", reason_out_t)):
-            self._need(x is None or (x.numel() == n_cand * C and x.element_size() == 1),
-                       f"{name} must hold n_cand * C bytes")
-        rm = _u32(relax) if relax else None  # the three host arrays are read during the call
-        qt = _quota_rows(quota, 1) if quota is not None else None
-        qu = _u32(quota_used).reshape(-1) if quota_used is not None else None
-        self._need(qu is None or qu.size == _lib.QUOTA_DIMS, "quota_used must hold 3 entries")
-        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
-        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
-        self._dev(lambda: check(self._L.fp_dev_grow_sweep_policy(
-            self._ctx, ct.byref(cs), _arg(reason_t if reason_mask else None), reason_mask, ct.byref(ns), _arg(count_t),
-            n_cand, *(_arg(t) for t in templates_t), _arg(t_max_t), max_new, strategy, int(preferred) & 0xFFFFFFFF,
-            _arg(domain_t), _arg(t_domain_t), max_skew, _arg(rm), len(relax), _arg(qt), _arg(qu), _arg(summary_t),
-            _arg(policy_t), _arg(assign_out_t), _arg(hops_t), _arg(reason_out_t)), "fp_dev_grow_sweep_policy"))
+        self._grow_dev(cont_t, reason_t, templates_t, max_new, summary_t, reason_mask, t_max_t, assign_out_t,
+                       (nodes_t, strategy, preferred, count_t, domain_t, t_domain_t, max_skew, relax_mask, quota,
+                        quota_used, policy_t, hops_t, reason_out_t))
 
     def dev_grow_sweep(self, cont_t, reason_t, templates_t, max_new, summary_t, reason_mask=1 << _lib.REASON_NOFIT,
                        t_max_t=None, assign_out_t=None):
@@ -930,29 +982,7 @@ class Planner:
         t_labels) [n_cand] each, ``t_max_t`` [n_cand] or None; out: ``summary_t`` [n_cand * 8] and
         ``assign_out_t`` [n_cand * C] or None.  ``max_new`` is a host value.  A t_max above max_new is found
         on the device: nothing is written and sync() raises FP_EINVAL."""
-        C = cont_t[0].numel()
-        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
-                   "every container tensor must hold C 32-bit entries")
-        self._need(len(templates_t) == 3, "templates_t must be (t_cpu, t_mem, t_labels)")
-        n_cand = templates_t[0].numel()
-        self._need(all(t.numel() == n_cand and t.element_size() == 4 for t in templates_t),
-                   "every template tensor must hold n_cand 32-bit entries")
-        reason_mask, max_new = int(reason_mask), int(max_new)
-        self._need(0 <= reason_mask <= 0xFFFFFFFF, "reason_mask must be a u32")
-        self._need(reason_mask == 0 or reason_t is None or (reason_t.numel() == C and reason_t.element_size() == 1),
-                   "reason_t must hold C bytes")
-        self._need(0 <= max_new <= 0xFFFFFFFF, "max_new must be a u32")
-        self._need(t_max_t is None or (t_max_t.numel() == n_cand and t_max_t.element_size() == 4),
-                   "t_max_t must hold n_cand 32-bit entries")
-        self._need(summary_t.numel() == n_cand * _lib.GROW_WORDS and summary_t.element_size() == 4,
-                   "summary_t must hold n_cand * 8 32-bit entries")
-        self._need(assign_out_t is None or (assign_out_t.numel() == n_cand * C and assign_out_t.element_size() == 4),
-                   "assign_out_t must hold n_cand * C 32-bit entries")
-        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
-        self._dev(lambda: check(self._L.fp_dev_grow_sweep(
-            self._ctx, ct.byref(cs), _arg(reason_t if reason_mask else None), reason_mask, n_cand,
-            *(_arg(t) for t in templates_t), _arg(t_max_t), max_new, _arg(summary_t), _arg(assign_out_t)),
-            "fp_dev_grow_sweep"))
+        self._grow_dev(cont_t, reason_t, templates_t, max_new, summary_t, reason_mask, t_max_t, assign_out_t)
 
     def dev_drain_sweep(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t, strategy=0,
                         preferred=0, count_t=None):
@@ -961,28 +991,8 @@ class Planner:
         [C], ``group_t`` [N], ``count_t`` [N] or None; out: ``assign_out_t`` [C], ``reason_t`` [C] uint8,
         ``summary_t`` [n_cand * 8].  A group or assign value out of range is found on the device: nothing is
         written and sync() raises FP_EINVAL."""
-        C, N, n_cand, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_cand), strategy_id(strategy)
-        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
-                   "every container tensor must hold C 32-bit entries")
-        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
-                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
-                   "every node tensor must hold N entries (schedulable N bytes)")
-        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
-        self._need(group_t.numel() == N and group_t.element_size() == 4, "group_t must hold N 32-bit entries")
-        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
-                   "count_t must hold N 32-bit entries")
-        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
-        self._need(assign_out_t.numel() == C and assign_out_t.element_size() == 4,
-                   "assign_out_t must hold C 32-bit entries")
-        self._need(reason_t.numel() == C and reason_t.element_size() == 1, "reason_t must hold C bytes")
-        self._need(summary_t.numel() == n_cand * _lib.DRAIN_WORDS and summary_t.element_size() == 4,
-                   "summary_t must hold n_cand * 8 32-bit entries")
-        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
-        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
-        self._dev(lambda: check(self._L.fp_dev_drain_sweep(
-            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(group_t), n_cand, strategy,
-            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(assign_out_t), _arg(reason_t), _arg(summary_t)),
-            "fp_dev_drain_sweep"))
+        self._drain_dev(cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t, strategy,
+                        preferred, count_t)
 
     def dev_shrink_sweep(self, cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t,
                          strategy=0, preferred=0, count_t=None, blocker_t=None):
@@ -990,33 +1000,8 @@ class Planner:
         ``dev_drain_sweep``, ``try_order_t`` [n_var * n_try]; out: ``assign_out_t`` [n_var * C], ``state_t``
         [n_var * N] uint8, ``summary_t`` [n_var * 8] and ``blocker_t`` [n_var * N] or None.  An assign or
         try_order value out of range is found on the device: nothing is written and sync() raises FP_EINVAL."""
-        C, N, n_var, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_var), strategy_id(strategy)
-        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
-                   "every container tensor must hold C 32-bit entries")
-        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
-                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
-                   "every node tensor must hold N entries (schedulable N bytes)")
-        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
-        self._need(0 <= n_var <= 0xFFFFFFFF, "n_var must be a u32")
-        self._need(try_order_t.element_size() == 4 and (try_order_t.numel() % n_var == 0 if n_var
-                                                        else try_order_t.numel() == 0),
-                   "try_order_t must hold n_var rows of 32-bit entries")
-        n_try = try_order_t.numel() // n_var if n_var else 0
-        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
-                   "count_t must hold N 32-bit entries")
-        self._need(assign_out_t.numel() == n_var * C and assign_out_t.element_size() == 4,
-                   "assign_out_t must hold n_var * C 32-bit entries")
-        self._need(state_t.numel() == n_var * N and state_t.element_size() == 1, "state_t must hold n_var * N bytes")
-        self._need(blocker_t is None or (blocker_t.numel() == n_var * N and blocker_t.element_size() == 4),
-                   "blocker_t must hold n_var * N 32-bit entries")
-        self._need(summary_t.numel() == n_var * _lib.SHRINK_WORDS and summary_t.element_size() == 4,
-                   "summary_t must hold n_var * 8 32-bit entries")
-        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
-        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
-        self._dev(lambda: check(self._L.fp_dev_shrink_sweep(
-            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(try_order_t), n_var, n_try, strategy,
-            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(assign_out_t), _arg(state_t), _arg(blocker_t),
-            _arg(summary_t)), "fp_dev_shrink_sweep"))
+        self._shrink_dev(cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t, strategy,
+                         preferred, count_t, blocker_t)
 
     def dev_shrink_sweep_policy(self, cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t,
                                 strategy=0, preferred=0, count_t=None, blocker_t=None, *, domain_t=None, max_skew=0,
@@ -1025,49 +1010,9 @@ class Planner:
         None, ``max_skew``, ``relax_mask`` (host values, at most 4) and the optional results ``hops_t`` [n_var * C]
         uint8, ``blocker_reason_t`` [n_var * N] uint8 and ``policy_t`` [n_var * 4].  An assign, try_order or
         domain value out of range is found on the device: nothing is written and sync() raises FP_EINVAL."""
-        C, N, n_var, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_var), strategy_id(strategy)
-        max_skew = int(max_skew)
-        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
-        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
-                   "every container tensor must hold C 32-bit entries")
-        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
-                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
-                   "every node tensor must hold N entries (schedulable N bytes)")
-        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
-        self._need(0 <= n_var <= 0xFFFFFFFF, "n_var must be a u32")
-        self._need(try_order_t.element_size() == 4 and (try_order_t.numel() % n_var == 0 if n_var
-                                                        else try_order_t.numel() == 0),
-                   "try_order_t must hold n_var rows of 32-bit entries")
-        n_try = try_order_t.numel() // n_var if n_var else 0
-        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
-                   "count_t must hold N 32-bit entries")
-        self._need(domain_t is None or (domain_t.numel() == N and domain_t.element_size() == 4),
-                   "domain_t must hold N 32-bit entries")
-        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
-        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
-        self._need(assign_out_t.numel() == n_var * C and assign_out_t.element_size() == 4,
-                   "assign_out_t must hold n_var * C 32-bit entries")
-        self._need(state_t.numel() == n_var * N and state_t.element_size() == 1, "state_t must hold n_var * N bytes")
-        self._need(blocker_t is None or (blocker_t.numel() == n_var * N and blocker_t.element_size() == 4),
-                   "blocker_t must hold n_var * N 32-bit entries")
-        self._need(summary_t.numel() == n_var * _lib.SHRINK_WORDS and summary_t.element_size() == 4,
-                   "summary_t must hold n_var * 8 32-bit entries")
-        self._need(hops_t is None or (hops_t.numel() == n_var * C and hops_t.element_size() == 1),
-                   "hops_t must hold n_var * C bytes")
-        self._need(blocker_reason_t is None or (blocker_reason_t.numel() == n_var * N
-                                                and blocker_reason_t.element_size() == 1),
-                   "blocker_reason_t must hold n_var * N bytes")
-        self._need(policy_t is None or (policy_t.numel() == n_var * _lib.SHRINK_POLICY_WORDS
-                                        and policy_t.element_size() == 4),
-                   "policy_t must hold n_var * 4 32-bit entries")
-        rm = _u32(relax) if relax else None  # read during the call
-        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
-        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
-        self._dev(lambda: check(self._L.fp_dev_shrink_sweep_policy(
-            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(try_order_t), n_var, n_try, strategy,
-            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(domain_t), max_skew, _arg(rm), len(relax),
-            _arg(assign_out_t), _arg(state_t), _arg(blocker_t), _arg(summary_t), _arg(hops_t), _arg(blocker_reason_t),
-            _arg(policy_t)), "fp_dev_shrink_sweep_policy"))
+        self._shrink_dev(cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t, strategy,
+                         preferred, count_t, blocker_t, (domain_t, max_skew, relax_mask, hops_t, blocker_reason_t,
+                                                         policy_t))
 
     def dev_drain_sweep_policy(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t,
                                strategy=0, preferred=0, count_t=None, *, domain_t=None, max_skew=0, relax_mask=(),
@@ -1076,40 +1021,8 @@ class Planner:
         None, ``max_skew``, ``relax_mask`` (host values, at most 4: the one array of a dev_* call that is not a
         tensor) and the optional results ``hops_t`` [C] uint8 and ``policy_t`` [n_cand * 4].  A group, assign or
         domain value out of range is found on the device: nothing is written and sync() raises FP_EINVAL."""
-        C, N, n_cand, strategy = cont_t[0].numel(), nodes_t[0].numel(), int(n_cand), strategy_id(strategy)
-        max_skew = int(max_skew)
-        relax = [int(m) & 0xFFFFFFFF for m in relax_mask]
-        self._need(len(cont_t) == 4 and all(t.numel() == C and t.element_size() == 4 for t in cont_t),
-                   "every container tensor must hold C 32-bit entries")
-        self._need(len(nodes_t) == 5 and all(t.numel() == N and t.element_size() == 4 for t in nodes_t[:4])
-                   and nodes_t[4].numel() == N and nodes_t[4].element_size() == 1,
-                   "every node tensor must hold N entries (schedulable N bytes)")
-        self._need(assign_t.numel() == C and assign_t.element_size() == 4, "assign_t must hold C 32-bit entries")
-        self._need(group_t.numel() == N and group_t.element_size() == 4, "group_t must hold N 32-bit entries")
-        self._need(count_t is None or (count_t.numel() == N and count_t.element_size() == 4),
-                   "count_t must hold N 32-bit entries")
-        self._need(domain_t is None or (domain_t.numel() == N and domain_t.element_size() == 4),
-                   "domain_t must hold N 32-bit entries")
-        self._need(0 <= n_cand <= 0xFFFFFFFF, "n_cand must be a u32")
-        self._need(0 <= max_skew <= 0xFFFFFFFF, "max_skew must be a u32")
-        self._need(len(relax) <= _lib.FP_FALLBACK_MAX_HOPS, f"relax_mask holds at most {_lib.FP_FALLBACK_MAX_HOPS} hops")
-        self._need(assign_out_t.numel() == C and assign_out_t.element_size() == 4,
-                   "assign_out_t must hold C 32-bit entries")
-        self._need(reason_t.numel() == C and reason_t.element_size() == 1, "reason_t must hold C bytes")
-        self._need(summary_t.numel() == n_cand * _lib.DRAIN_WORDS and summary_t.element_size() == 4,
-                   "summary_t must hold n_cand * 8 32-bit entries")
-        self._need(hops_t is None or (hops_t.numel() == C and hops_t.element_size() == 1), "hops_t must hold C bytes")
-        self._need(policy_t is None or (policy_t.numel() == n_cand * _lib.DRAIN_POLICY_WORDS
-                                        and policy_t.element_size() == 4),
-                   "policy_t must hold n_cand * 4 32-bit entries")
-        rm = _u32(relax) if relax else None  # read during the call
-        cs = FpContainers(C, *(t.data_ptr() for t in cont_t))
-        ns = FpNodes(N, *(t.data_ptr() for t in nodes_t))
-        self._dev(lambda: check(self._L.fp_dev_drain_sweep_policy(
-            self._ctx, ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(group_t), n_cand, strategy,
-            int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(domain_t), max_skew, _arg(rm), len(relax),
-            _arg(assign_out_t), _arg(reason_t), _arg(hops_t), _arg(summary_t), _arg(policy_t)),
-            "fp_dev_drain_sweep_policy"))
+        self._drain_dev(cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t, strategy,
+                        preferred, count_t, (domain_t, max_skew, relax_mask, hops_t, policy_t))
 
     def dev_explain(self, db: "DevBatch", rows_t, sel_t=None, ignore_labels=0, scenario=0):
         """fp_dev_explain on one scenario of ``db`` (offset pointers, as dev_feasibility): ``rows_t``

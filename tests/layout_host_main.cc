@@ -90,6 +90,155 @@ static size_t old_drain_formula(size_t C, size_t N, size_t n_cand) {
     return C * 25 + N * 25 + R * 4 + 20 * 256;
 }
 
+// ---- the sweep lists and the re-plan list ----------------------------------------------------------------------
+// where every row of a list starts, in units of 256 bytes (-1: the row takes nothing); returns the total
+static size_t row_offsets(const fp_row *r, int n, long *at) {
+    size_t off[FP_MAX_ROWS];
+    const size_t total = fp_rows_layout(r, n, 0, off);
+    for (int i = 0; i < n; ++i) at[i] = fp_row_taken(r[i]) ? (long)(off[i] / 256) : -1;
+    return total;
+}
+
+// The order of the rows is the arena layout: the offsets of every list at S = 2, C = 70, N = 9 (2 variants of 9
+// tries, 3 templates, every option given), recorded from the lists as they were when each entry point had its own.
+struct pinned_list {
+    const char *name;
+    int n;
+    long at[FP_MAX_ROWS];
+};
+static const pinned_list PINNED[] = {
+    {"drain", 15, {0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 15, 16, 17, 19, 20}},
+    {"drain_policy", 18, {0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 15, 16, 17, 19, 20, 22, 23, 24}},
+    {"shrink", 16, {0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 15, 16, 17, 20, 21, 22}},
+    {"shrink_policy", 20, {0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 15, 16, 17, 20, 21, 22, 23, 24, 25, 26}},
+    {"grow", 11, {0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 14}},
+    {"grow_policy", 22, {0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 27, 28}},
+    {"replan", 27, {0,  3,  6,  9,  12, 15, 16, 17, 18, 19, 20, 21, 22, 23,
+                    24, 25, 26, 27, 28, 29, 32, 33, 34, 35, 36, 39, 40}},
+};
+
+static void check_pinned(const char *name, const fp_row *r, int n, bool pinned) {
+    long at[FP_MAX_ROWS];
+    row_offsets(r, n, at);
+    if (!pinned) return;
+    printf("order %s:", name);
+    for (int i = 0; i < n; ++i) printf(" %ld", at[i]);
+    printf("\n");
+    for (const pinned_list &p : PINNED) {
+        if (strcmp(p.name, name)) continue;
+        CHECK(p.n == n);
+        for (int i = 0; i < n && i < p.n; ++i) CHECK(p.at[i] == at[i]);
+        return;
+    }
+    CHECK(!"a list without a pinned order");
+}
+
+static void test_sweep_lists(uint32_t S, uint32_t C, uint32_t N, fp_batch *b, const fp_policy_opts *o,
+                             const fp_containers *cs, const fp_nodes *ns) {
+    const bool pin = S == 2 && C == 70 && N == 9;
+    const uint32_t V = 2, K = 3, n_try = N;
+    const size_t SC = (size_t)S * C;
+    std::vector<uint32_t> in((SC > 2 * (size_t)N ? SC : 2 * (size_t)N) + 64, 1u);  // every u32 input reads from this
+    std::vector<uint8_t> in8(C + 1, 1u);
+    uint32_t o32[1];  // results are never written through their host pointer here: non-null is all they need
+    uint8_t o8[1];
+    fp_row rows[FP_MAX_ROWS], plain[FP_MAX_ROWS];
+    long at[FP_MAX_ROWS], at_plain[FP_MAX_ROWS];
+
+    // drain: every option, then the policy list without a guarantee against the plain list
+    fp_drain_dev dd, dd0;
+    fp_drain_policy_dev dp;
+    int n = fp_drain_policy_rows(cs, ns, in.data(), in.data(), N, in.data(), in.data(), o32, o8, o8, o32, o32, &dd, &dp,
+                                 rows);
+    CHECK(n == 18);
+    stage_and_check(rows, n);
+    CHECK(dd.cs.conflict && dd.ns.cpu_free && dd.assign && dd.group && dd.node_count && dd.assign_out && dd.reason_out &&
+          dd.summary && dp.domain && dp.hops_out && dp.policy_out);
+    check_pinned("drain_policy", rows, n, pin);
+    n = fp_drain_policy_rows(cs, ns, in.data(), in.data(), N, in.data(), nullptr, o32, o8, nullptr, o32, nullptr, &dd, &dp,
+                             rows);
+    int n0 = fp_drain_rows(cs, ns, in.data(), in.data(), N, in.data(), o32, o8, o32, &dd0, plain);
+    CHECK(n == 18 && n0 == 15);
+    CHECK(row_offsets(rows, n, at) == row_offsets(plain, n0, at_plain));
+    for (int i = 0; i < n0; ++i) CHECK(at[i] == at_plain[i] && rows[i].bytes == plain[i].bytes && at[i] >= 0);
+    for (int i = n0; i < n; ++i) CHECK(at[i] == -1);
+    stage_and_check(rows, n);
+    CHECK(!dp.domain && !dp.hops_out && !dp.policy_out && dd.summary);
+    check_pinned("drain", plain, n0, pin);
+
+    // shrink
+    fp_shrink_dev sd, sd0;
+    fp_shrink_policy_dev sp;
+    n = fp_shrink_rows(cs, ns, in.data(), in.data(), V, n_try, in.data(), o32, o8, o32, o32, &sd, rows);
+    CHECK(n == 16);
+    stage_and_check(rows, n);
+    CHECK(sd.cs.cpu_m && sd.ns.schedulable && sd.assign && sd.try_order && sd.node_count && sd.assign_out &&
+          sd.state_out && sd.blocker_out && sd.summary);
+    check_pinned("shrink", rows, n, pin);
+    n = fp_shrink_policy_rows(cs, ns, in.data(), in.data(), V, n_try, in.data(), in.data(), o32, o8, o32, o32, o8, o8, o32,
+                              &sd, &sp, rows);
+    CHECK(n == 20);
+    stage_and_check(rows, n);
+    CHECK(sd.cs.cpu_m && sd.ns.schedulable && sd.assign && sd.try_order && sd.node_count && sd.assign_out &&
+          sd.state_out && sd.blocker_out && sd.summary && sp.domain && sp.hops_out && sp.blocker_reason_out &&
+          sp.policy_out);
+    check_pinned("shrink_policy", rows, n, pin);
+    n = fp_shrink_policy_rows(cs, ns, in.data(), in.data(), V, n_try, in.data(), nullptr, o32, o8, o32, o32, nullptr,
+                              nullptr, nullptr, &sd, &sp, rows);
+    n0 = fp_shrink_rows(cs, ns, in.data(), in.data(), V, n_try, in.data(), o32, o8, o32, o32, &sd0, plain);
+    CHECK(n == 20 && n0 == 16);
+    CHECK(row_offsets(rows, n, at) == row_offsets(plain, n0, at_plain));
+    for (int i = 0; i < n0; ++i) CHECK(at[i] == at_plain[i] && rows[i].bytes == plain[i].bytes && at[i] >= 0);
+    for (int i = n0; i < n; ++i) CHECK(at[i] == -1);
+    stage_and_check(rows, n);
+    CHECK(!sp.domain && !sp.hops_out && !sp.blocker_reason_out && !sp.policy_out && sd.summary);
+
+    // grow
+    fp_grow_dev gd, gd0;
+    fp_grow_policy_dev gp;
+    n = fp_grow_rows(cs, in8.data(), 2u, K, in.data(), in.data(), in.data(), in.data(), o32, o32, &gd, rows);
+    CHECK(n == 11);
+    stage_and_check(rows, n);
+    CHECK(gd.cs.cpu_m && gd.cs.conflict && gd.reason && gd.t_cpu && gd.t_mem && gd.t_labels && gd.t_max && gd.summary &&
+          gd.assign_out);
+    check_pinned("grow", rows, n, pin);
+    n = fp_grow_policy_rows(cs, in8.data(), 2u, ns, in.data(), K, in.data(), in.data(), in.data(), in.data(), in.data(),
+                            in.data(), o32, o32, o32, o8, o8, &gd, &gp, rows);
+    CHECK(n == 22);
+    stage_and_check(rows, n);
+    CHECK(gd.cs.cpu_m && gd.reason && gp.ns.cpu_free && gp.ns.schedulable && gp.node_count && gp.domain && gd.t_cpu &&
+          gd.t_max && gp.t_domain && gd.summary && gp.policy_out && gd.assign_out && gp.hops_out && gp.reason_out);
+    check_pinned("grow_policy", rows, n, pin);
+    // no live table and no policy option: the container, reason, template and result rows lie where fp_grow_rows
+    // puts them
+    fp_nodes none = {};
+    n = fp_grow_policy_rows(cs, in8.data(), 2u, &none, nullptr, K, in.data(), in.data(), in.data(), in.data(), nullptr,
+                            nullptr, o32, nullptr, o32, nullptr, nullptr, &gd, &gp, rows);
+    n0 = fp_grow_rows(cs, in8.data(), 2u, K, in.data(), in.data(), in.data(), in.data(), o32, o32, &gd0, plain);
+    CHECK(n == 22 && n0 == 11);
+    CHECK(row_offsets(rows, n, at) == row_offsets(plain, n0, at_plain));
+    const int same[11] = {0, 1, 2, 3, 4, 12, 13, 14, 15, 17, 19};  // where the eleven rows stand among the 22
+    for (int i = 0; i < n0; ++i) CHECK(at[same[i]] == at_plain[i] && rows[same[i]].bytes == plain[i].bytes && at_plain[i] >= 0);
+    int taken = 0;
+    for (int i = 0; i < n; ++i) taken += at[i] >= 0;
+    CHECK(taken == n0);
+    stage_and_check(rows, n);
+    CHECK(gd.cs.cpu_m && gd.t_max && gd.summary && gd.assign_out && !gp.ns.cpu_free && !gp.node_count && !gp.policy_out);
+
+    // re-plan with every policy option
+    b->level = in.data();
+    fp_batch d;
+    fp_policy_opts dopt;
+    fp_replan_dev dr;
+    n = fp_replan_rows(b, o, in.data(), o8, o32, &d, &dopt, &dr, rows);
+    CHECK(n == 27);
+    stage_and_check(rows, n);
+    CHECK(d.cpu_m && d.level && d.schedulable && d.assign && d.reason && d.cost && dopt.strategy && dopt.preferred &&
+          dopt.node_count && dopt.domain && dopt.max_skew && dopt.relax_mask && dopt.n_hops && dopt.quota &&
+          dopt.quota_used && dopt.hops && dopt.quota_why && dr.prev && dr.change && dr.summary);
+    check_pinned("replan", rows, n, pin);
+}
+
 static void test_entry_points(uint32_t S, uint32_t C, uint32_t N) {
     const size_t SC = (size_t)S * C, SN = (size_t)S * N;
     const size_t big = (SC > SN ? SC : SN) + (size_t)S * 8 + 64;
@@ -138,6 +287,7 @@ static void test_entry_points(uint32_t S, uint32_t C, uint32_t N) {
     CHECK(total <= old_drain_formula(C, N, N));
     CHECK(dd.cs.cpu_m && dd.ns.schedulable && dd.assign && dd.group && dd.node_count && dd.assign_out && dd.reason_out &&
           dd.summary);
+    test_sweep_lists(S, C, N, &b, &o, &cs, &ns);
 }
 
 int main() {

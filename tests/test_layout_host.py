@@ -38,3 +38,4 @@ def test_layout_under_sanitizers(tmp_path):
     assert r.returncode == 0, r.stdout
     assert r.stdout.rstrip().endswith("layout ok")
     assert "policy S=3 C=3000 N=700" in r.stdout and "drain C=3000 N=700" in r.stdout
+    assert "order grow_policy: 0 2 4 " in r.stdout and "order replan: 0 3 6 " in r.stdout
