@@ -54,6 +54,10 @@ SHRINK_STATE_NEVER, SHRINK_STATE_RELEASED, SHRINK_STATE_FAILED = 0, 1, 2
 # the scale-in sweep under the policy (SPEC.md 2.17): the word indices of a variant's policy row, and their names
 SHRINK_FAILED_SKEW, SHRINK_RELAXED, SHRINK_SKEW_BEFORE, SHRINK_SKEW_AFTER, SHRINK_POLICY_WORDS = 0, 1, 2, 3, 4
 SHRINK_POLICY_FIELDS = ("failed_skew", "relaxed", "skew_before", "skew_after")
+# rebalance sweep (SPEC.md 2.19): the word indices of a variant's summary row, and their names in order
+REBAL_MOVES, REBAL_STUCK, REBAL_STUCK_SKEW, REBAL_RELAXED, REBAL_MOVED_CPU = 0, 1, 2, 3, 4
+REBAL_MOVED_MEM, REBAL_SKEW_BEFORE, REBAL_SKEW_AFTER, REBAL_WORDS = 5, 6, 7, 8
+REBAL_FIELDS = ("moves", "stuck", "stuck_skew", "relaxed", "moved_cpu", "moved_mem", "skew_before", "skew_after")
 # scale-out sweep (SPEC.md 2.12): the word indices of a candidate's summary row, their names in order, and the
 # most new servers a candidate may open
 GROW_PENDING, GROW_PLACED, GROW_OPENED, GROW_UNPLACEABLE, GROW_CAPPED = 0, 1, 2, 3, 4
@@ -192,6 +196,13 @@ SIGNATURES = {
     "fp_dev_shrink_sweep_policy": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, vp, ct.c_uint32,
                                               ct.c_uint32, ct.c_uint32, ct.c_uint32, vp, vp, ct.c_uint32, u32p,
                                               ct.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+    "fp_rebalance_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), u32p, u32p, ct.c_uint32,
+                                      ct.c_uint32, u32p, ct.c_uint32, ct.c_uint32, u32p, u32p, ct.c_uint32, u32p,
+                                      ct.c_uint32, u32p, u8p, u8p, u32p]),
+    # relax_mask (u32p) is a host array in the device entry too
+    "fp_dev_rebalance_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), ct.POINTER(FpNodes), vp, vp, ct.c_uint32,
+                                          ct.c_uint32, vp, ct.c_uint32, ct.c_uint32, vp, vp, ct.c_uint32, u32p,
+                                          ct.c_uint32, vp, vp, vp, vp]),
     "fp_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), u8p, ct.c_uint32, ct.c_uint32, u32p, u32p, u32p, u32p,
                                  ct.c_uint32, u32p, u32p]),
     "fp_dev_grow_sweep": (ct.c_int, [vp, ct.POINTER(FpContainers), vp, ct.c_uint32, ct.c_uint32, vp, vp, vp, vp,

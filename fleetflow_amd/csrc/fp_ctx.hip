@@ -1033,6 +1033,63 @@ extern "C" int fp_shrink_sweep_policy(fp_ctx *c, const fp_containers *cs, const 
                        shrink_policy(domain, max_skew, relax_mask, n_hops, hops_out, blocker_reason_out, policy_out));
 }
 
+// rebalance sweep (SPEC.md 2.19, fp_rebalance.hip)
+static fp_rebalance_opts rebalance_opts(const uint32_t *node_count, const uint32_t *domain, uint32_t max_skew,
+                                        const uint32_t *relax_mask, uint32_t n_hops) {
+    fp_rebalance_opts o;
+    o.node_count = node_count; o.domain = domain; o.max_skew = max_skew; o.relax_mask = relax_mask; o.n_hops = n_hops;
+    return o;
+}
+
+extern "C" int fp_dev_rebalance_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                      const uint32_t *victim_order, uint32_t n_var, uint32_t n_try,
+                                      const uint32_t *max_moves, uint32_t strategy, uint32_t preferred_labels,
+                                      const uint32_t *node_count, const uint32_t *domain, uint32_t max_skew,
+                                      const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
+                                      uint8_t *hops_out, uint8_t *reason_out, uint32_t *summary_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    return fp_dev_done(c, fp_dev_rebalance_sweep_impl(c, cs, ns, assign, victim_order, n_var, n_try, max_moves, strategy,
+                                                      preferred_labels,
+                                                      rebalance_opts(node_count, domain, max_skew, relax_mask, n_hops),
+                                                      assign_out, hops_out, reason_out, summary_out));
+}
+
+// no variant is nothing to do, whatever the tables are: found before them, as in shrink_host
+extern "C" int fp_rebalance_sweep(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                  const uint32_t *victim_order, uint32_t n_var, uint32_t n_try, const uint32_t *max_moves,
+                                  uint32_t strategy, uint32_t preferred_labels, const uint32_t *node_count,
+                                  const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                                  uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out, uint32_t *summary_out) {
+    if (!c || !cs || !ns) return FP_EINVAL;
+    const size_t C = cs->n, N = ns->n;
+    if (N > FP_POLICY_MAX_NODES || n_var > 65535u || C > FP_SHRINK_MAX_CONTAINERS) return FP_EOVERFLOW;
+    if (strategy > (uint32_t)FP_STRATEGY_FILL_LOWEST) return FP_EINVAL;
+    if (n_hops > (uint32_t)FP_FALLBACK_MAX_HOPS) return FP_EINVAL;
+    if (n_var == 0) return FP_OK;
+    if (C && (!fp_has_cont(cs) || !assign || !assign_out)) return FP_EINVAL;
+    if (N && !fp_has_nodes(ns)) return FP_EINVAL;
+    if ((n_try && !victim_order) || !summary_out) return FP_EINVAL;
+    if (C && assign_out == assign) return FP_EINVAL;
+    if (!fp_below_or_none(assign, C, N) || !fp_below_or_none(victim_order, (size_t)n_var * n_try, C)) return FP_EINVAL;
+    if (!domain || max_skew == 0u) domain = nullptr;  // otherwise domain is not read
+    if (domain && !fp_domains_ok(domain, N)) return FP_EINVAL;
+    FP_HIP(hipSetDevice(c->device));
+    fp_host_err_scope es(c);
+    if (es.rc) return es.rc;
+    fp_row rows[FP_MAX_ROWS];
+    fp_rebalance_dev d;
+    const int n = fp_rebalance_rows(cs, ns, assign, victim_order, n_var, n_try, max_moves, node_count, domain, assign_out,
+                                    hops_out, reason_out, summary_out, &d, rows);
+    if (int rc = stage_rows(c, rows, n, false)) return rc;
+    if (int rc = fp_dev_rebalance_sweep_impl(c, &d.cs, &d.ns, d.assign, d.victim_order, n_var, n_try, d.max_moves,
+                                             strategy, preferred_labels,
+                                             rebalance_opts(d.node_count, d.domain, max_skew, relax_mask, n_hops),
+                                             d.assign_out, d.hops_out, d.reason_out, d.summary))
+        return rc;
+    return copy_back_all(c, rows, n);
+}
+
 // scale-out sweep (SPEC.md 2.12 and 2.18, fp_grow.hip): the two kernels differ, so each export keeps its impl.
 // What both host exports ask of the pending containers and the templates, after their own FP_EOVERFLOW tests;
 // t_max is host memory here, so a value above max_new is refused before anything is staged

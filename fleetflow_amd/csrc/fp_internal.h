@@ -252,6 +252,23 @@ int fp_dev_shrink_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes 
                              uint32_t preferred, const uint32_t *node_count, uint32_t *assign_out, uint8_t *state_out,
                              uint32_t *blocker_out, uint32_t *summary_out, const fp_shrink_policy &pol = fp_shrink_policy());
 
+// what a rebalance sweep is held to (SPEC.md 2.19).  Not ABI: the exports of fp_ctx.hip fill it in.  node_count
+// and domain are device memory, relax_mask a HOST array
+struct fp_rebalance_opts {
+    const uint32_t *node_count = nullptr;  // [N]; null: derived from assign
+    const uint32_t *domain = nullptr;      // [N]; null or max_skew == 0: nothing is heavy
+    uint32_t max_skew = 0;
+    const uint32_t *relax_mask = nullptr;  // [n_hops]; null or n_hops == 0: no chain
+    uint32_t n_hops = 0;
+};
+// rebalance sweep (fp_rebalance.hip, SPEC.md 2.19); every pointer but o.relax_mask is device memory.  assign,
+// victim_order and domain values out of range are found on the device (FP_EINVAL in the context's error word,
+// nothing written).  hops_out and reason_out are nullable
+int fp_dev_rebalance_sweep_impl(fp_ctx *c, const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                const uint32_t *victim_order, uint32_t n_var, uint32_t n_try, const uint32_t *max_moves,
+                                uint32_t strategy, uint32_t preferred, const fp_rebalance_opts &o, uint32_t *assign_out,
+                                uint8_t *hops_out, uint8_t *reason_out, uint32_t *summary_out);
+
 // scale-out sweep (fp_grow.hip, SPEC.md 2.12); every pointer is device memory, max_new a host value.  A t_max
 // value above max_new is found on the device (FP_EINVAL in the context's error word, nothing written)
 int fp_dev_grow_sweep_impl(fp_ctx *c, const fp_containers *cs, const uint8_t *reason, uint32_t reason_mask,

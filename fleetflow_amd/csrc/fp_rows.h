@@ -219,6 +219,34 @@ static inline int fp_shrink_policy_rows(const fp_containers *cs, const fp_nodes 
     return n;
 }
 
+// fp_rebalance_sweep (SPEC.md 2.19): the tables, the live plan, the victim orders with their budgets, the counts
+// and the domains (each absent when the caller gives none); then the four results.  relax_mask stays on the host
+struct fp_rebalance_dev {
+    fp_containers cs;
+    fp_nodes ns;
+    const uint32_t *assign, *victim_order, *max_moves, *node_count, *domain;
+    uint32_t *assign_out, *summary;
+    uint8_t *hops_out, *reason_out;
+};
+static inline int fp_rebalance_rows(const fp_containers *cs, const fp_nodes *ns, const uint32_t *assign,
+                                    const uint32_t *victim_order, uint32_t n_var, uint32_t n_try,
+                                    const uint32_t *max_moves, const uint32_t *node_count, const uint32_t *domain,
+                                    uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out, uint32_t *summary_out,
+                                    fp_rebalance_dev *d, fp_row *r) {
+    const size_t C = cs->n, N = ns->n, V = n_var;
+    int n = fp_tables_rows(cs, ns, &d->cs, &d->ns, r);
+    r[n++] = fp_row_in(assign, C, &d->assign);
+    r[n++] = fp_row_in(victim_order, V * n_try, &d->victim_order);
+    r[n++] = fp_row_in(max_moves, V, &d->max_moves);
+    r[n++] = fp_row_in(node_count, N, &d->node_count);
+    r[n++] = fp_row_in(domain, N, &d->domain);
+    r[n++] = fp_row_out(assign_out, V * C, &d->assign_out);
+    r[n++] = fp_row_opt(hops_out, V * C, &d->hops_out);
+    r[n++] = fp_row_opt(reason_out, V * C, &d->reason_out);
+    r[n++] = fp_row_out(summary_out, V * FP_REBAL_WORDS, &d->summary);
+    return n;
+}
+
 // fp_grow_sweep: the requests, the reasons (absent without a mask), the templates; then the two results
 struct fp_grow_dev {
     fp_containers cs;

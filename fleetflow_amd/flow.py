@@ -929,6 +929,172 @@ def shrink_stage(flow: Flow, stage_name: str, plan: Plan, orders=None, keep=None
 
 
 @dataclass
+class RebalanceVariant:
+    """One victim order of a rebalance sweep (SPEC.md 2.19): the seats it gives up to bring the spread constraint
+    back within ``max_skew``, where they go, and the services it tried and could not move."""
+    name: str                              # the rule's name, or "order<i>" for an explicit list
+    order: list[str]                       # the services in the order they were visited
+    moves: list[tuple[str, str, str]]      # (service, from, to), in victim order
+    stuck: dict[str, str] = field(default_factory=dict)          # service whose last attempt failed -> "NOFIT" / "SKEW"
+    relaxed: dict[str, list[str]] = field(default_factory=dict)  # moved service -> label keys given up (Plan.relaxed)
+    n_stuck: int = 0                       # rejected attempts; a service tried twice counts twice
+    max_moves: int | None = None           # the move budget; None = unlimited
+    moved_cpu_m: int = 0                   # what the moved services ask for in sum
+    moved_mem_mib: int = 0
+    skew_before: int = 0                   # max - min of the services per eligible domain on the live state
+    skew_after: int = 0                    # the same on the state the variant leaves
+    lightest: str | None = None            # where skew_after is out of bound: the eligible "key=value" with the fewest
+
+
+@dataclass
+class RebalanceReport:
+    """``rebalance_stage``'s answer: one RebalanceVariant per victim order, every one computed independently from
+    the same live state under the strategy, preferred labels, spread constraint and fallback chain named here.
+    ``best`` indexes the variant that ends within ``max_skew`` if one does, then the one with the smallest
+    ``skew_after``, the fewest moves, the least moved CPU and the lowest index (None without variants); ``plan`` is
+    the plan that variant leaves.  ``note`` says why a report has no variants."""
+    stage: str
+    strategy: str | None = None
+    preferred: list[str] = field(default_factory=list)
+    pin: list[str] = field(default_factory=list)
+    variants: list[RebalanceVariant] = field(default_factory=list)
+    best: int | None = None
+    plan: Plan | None = None
+    spread_topology_key: str | None = None
+    spread_max_skew: int | None = None
+    fallback_relax_order: list[str] = field(default_factory=list)
+    fallback_max_hops: int | None = None
+    note: str | None = None
+
+
+REBALANCE_RULES = ("smallest", "largest", "newest")
+
+
+def rebalance_order(rule: str, names: list[str], cont, assign, pin=()) -> list[int]:
+    """The service indices a rule visits, in order: ``"smallest"`` by (cpu asc, mem asc, stage order), ``"largest"``
+    in the order of SPEC.md 2.3 (cpu desc, mem desc, stage order), ``"newest"`` by stage order descending.  Only
+    services that run are listed; ``pin`` (names) are left out."""
+    if rule not in REBALANCE_RULES:
+        raise ValueError(f"rebalance: unknown order rule '{rule}' (one of {', '.join(REBALANCE_RULES)})")
+    held = set(pin)
+    idx = [v for v, n in enumerate(names) if n not in held and assign[v] != NONE]
+    if rule == "smallest":
+        key = lambda v: (cont[0][v], cont[1][v], v)  # noqa: E731
+    elif rule == "largest":
+        key = lambda v: (-cont[0][v], -cont[1][v], v)  # noqa: E731
+    else:
+        key = lambda v: -v  # noqa: E731
+    return sorted(idx, key=key)
+
+
+def rebalance_stage(flow: Flow, stage_name: str, plan: Plan, orders=None, pin=None, max_moves=None,
+                    policy: PlacementPolicy | None = None, planner: Planner | None = None) -> RebalanceReport:
+    """"Which services have to move so that the spread holds again?" for a stage that runs as ``plan`` says (SPEC.md
+    2.19; the descheduler to ``replan_stage``'s scheduler): one ``Planner.rebalance_sweep`` over the live tables of
+    ``live_tables``, one variant per entry of ``orders``.  An entry is a rule name (``rebalance_order``: "smallest",
+    "largest", "newest") or an explicit list of service names; the default is all three rules.  ``pin`` (names) are
+    never victims, in a rule or in an explicit list; an unknown name anywhere is a ValueError.  ``max_moves`` is the
+    move budget of every variant, or one per variant (None = unlimited).
+
+    A variant visits its services in order.  One that runs in a heavy domain (a value of the topology key that holds
+    more than ``max_skew`` services above the lightest eligible one) is lifted off its server and placed again under
+    the strategy, preferred labels, spread constraint and fallback chain of ``policy`` or, without one, of the
+    policy the plan was made under; if no server takes it, it stays where it was.  Servers without the topology key
+    take no move, but what runs on them counts (``replan_domains``).  A rule visits its order twice, so that a
+    service that was refused is tried again on the state the others left.  A quota has nothing to test: a move
+    releases and retakes the same request.
+
+    A stage without a spread constraint has nothing to restore: the report has no variants and ``note`` says so."""
+    import dataclasses
+    from ._lib import (REASON_SKEW, REBAL_MOVED_CPU, REBAL_MOVED_MEM, REBAL_SKEW_AFTER, REBAL_SKEW_BEFORE, REBAL_STUCK)
+    pol = policy if policy is not None else _plan_policy(plan)
+    names, nodes, cont, live, assign, count, strategy, pmask = live_tables(flow, stage_name, plan, policy)
+    pin = list(pin or [])
+    report = RebalanceReport(stage_name, strategy, list(pol.preferred), pin)
+    if pol.fallback:
+        report.fallback_relax_order, report.fallback_max_hops = list(pol.fallback_relax_order), pol.fallback_max_hops
+    index = {n: v for v, n in enumerate(names)}
+    unknown = [s for s in pin if s not in index]
+    if unknown:
+        raise ValueError(f"rebalance: {unknown} are no services of stage '{stage_name}'")
+    rows, labels = [], []
+    for i, entry in enumerate(REBALANCE_RULES if orders is None else orders):
+        if isinstance(entry, str):
+            rows.append(rebalance_order(entry, names, cont, assign, pin) * 2)
+            labels.append(entry)
+        else:
+            unknown = [s for s in entry if s not in index]
+            if unknown:
+                raise ValueError(f"rebalance: {unknown} are no services of stage '{stage_name}'")
+            rows.append([index[s] for s in entry if s not in pin])
+            labels.append(f"order{i}")
+    if pol.spread is None or not pol.spread[1]:
+        report.note = "no spread constraint: nothing to restore"
+        return report
+    report.spread_topology_key, report.spread_max_skew = pol.spread
+    if not rows or not nodes:
+        report.note = "no victim orders" if not rows else "no servers"
+        return report
+    budgets = None
+    if max_moves is not None:
+        per = list(max_moves) if isinstance(max_moves, (list, tuple)) else [max_moves] * len(rows)
+        if len(per) != len(rows):
+            raise ValueError("rebalance: max_moves must hold one budget per order")
+        budgets = [NONE if b is None else int(b) for b in per]
+    key, max_skew = pol.spread
+    domain, has_key = replan_domains(nodes, key)
+    live = (*live[:4], [s if k else 0 for s, k in zip(live[4], has_key)])
+    relax = [_stage_labels(names, flow, nodes, list(pol.preferred)).key_mask(k) for k in pol.fallback]
+    n_try = max(len(r) for r in rows)
+    victim_order = np.full((len(rows), n_try), NONE, np.uint32)
+    for i, r in enumerate(rows):
+        victim_order[i, :len(r)] = r
+    p = planner or default_planner()
+    out, hops, why, summary = p.rebalance_sweep(cont, live, assign, victim_order, strategy if strategy is not None else 0,
+                                                pmask, count, domain=domain, max_skew=max_skew, relax_mask=relax,
+                                                max_moves=budgets)
+    slugs = [nd.slug for nd in nodes]
+    prefix = key + "="
+    value = {}
+    for nd, d, k in zip(nodes, domain, has_key):
+        if k:
+            value.setdefault(d, next(lab for lab in nd.labels if lab.startswith(prefix)))
+    eligible = sorted({d for d, s in zip(domain, live[4]) if s})
+    for i, r in enumerate(rows):
+        row = [int(x) for x in summary[i]]
+        seen = list(dict.fromkeys(r))
+        moves = [(names[v], slugs[assign[v]], slugs[int(out[i][v])]) for v in seen if int(out[i][v]) != assign[v]]
+        var = RebalanceVariant(labels[i], [names[v] for v in r], moves, n_stuck=row[REBAL_STUCK],
+                               max_moves=None if budgets is None or budgets[i] == NONE else budgets[i],
+                               moved_cpu_m=row[REBAL_MOVED_CPU], moved_mem_mib=row[REBAL_MOVED_MEM],
+                               skew_before=row[REBAL_SKEW_BEFORE], skew_after=row[REBAL_SKEW_AFTER])
+        for v in seen:
+            if int(why[i][v]):
+                var.stuck[names[v]] = "SKEW" if int(why[i][v]) == REASON_SKEW else "NOFIT"
+            if int(out[i][v]) != assign[v] and int(hops[i][v]):
+                required = {lab.split("=", 1)[0] for lab in flow.services.get(names[v], Service()).labels}
+                var.relaxed[names[v]] = [k for k in pol.fallback[:int(hops[i][v])] if k in required]
+        if var.skew_after > max_skew and eligible:
+            per = dict.fromkeys(eligible, 0)
+            for v, n in enumerate(out[i]):
+                if int(n) != NONE and domain[int(n)] in per:
+                    per[domain[int(n)]] += 1
+            var.lightest = value[min(eligible, key=lambda d: (per[d], d))]
+        report.variants.append(var)
+    vs = report.variants
+    report.best = min(range(len(vs)), key=lambda i: (vs[i].skew_after > max_skew, vs[i].skew_after, len(vs[i].moves),
+                                                     vs[i].moved_cpu_m, i))
+    best = vs[report.best]
+    assignment = dict(plan.assignment)
+    for svc, _, dst in best.moves:
+        assignment[svc] = dst
+    relaxed = {svc: keys for svc, keys in plan.relaxed.items() if svc not in {m[0] for m in best.moves}}
+    relaxed.update(best.relaxed)  # a moved service carries the keys its move gave up, and no others
+    report.plan = dataclasses.replace(plan, assignment=assignment, relaxed=relaxed)
+    return report
+
+
+@dataclass
 class GrowCandidate:
     """One candidate of a scale-out sweep (SPEC.md 2.12): a server template and what adding servers of it does
     for the plan's unplaced services."""

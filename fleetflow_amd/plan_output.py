@@ -48,8 +48,8 @@ import json
 from dataclasses import asdict
 
 from ._lib import QUOTA_NAMES
-from .flow import (U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, GrowCandidate, GrowReport, Plan, Replan,
-                   ShrinkReport, ShrinkVariant, Why)
+from .flow import (U32_MAX, WHY_NAMES, DrainCandidate, DrainReport, Flow, GrowCandidate, GrowReport, Plan,
+                   RebalanceReport, RebalanceVariant, Replan, ShrinkReport, ShrinkVariant, Why)
 from .parser import FlowError
 
 
@@ -225,6 +225,60 @@ def shrink_report_from_json(text: str) -> ShrinkReport:
                         (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"),
                         list((pol.get("fallback") or {}).get("relax_order") or []),
                         (pol.get("fallback") or {}).get("max_hops"))
+
+
+def format_rebalance_report(report: RebalanceReport) -> str:
+    """One line per victim order, ``rebalance <name>: <m> services move (<cpu>m cpu, <mem> MiB), skew over <key>
+    <before> -> <after> (max_skew <k>), <s> attempts refused``, marked ``(best)`` where it is and with ``budget
+    <b>`` where the variant had one, with the moves (``service: from -> to``, ``(relaxed: class)`` behind a relaxed
+    one) and the services that stay (``service: stays (SKEW)``) indented under it.  A variant that ends out of bound
+    says which eligible domain is the lightest and what would give it room.  A report without variants is its note."""
+    if not report.variants:
+        return f"rebalance {report.stage}: {report.note or 'no variants'}"
+    lines = []
+    for i, v in enumerate(report.variants):
+        lines.append(f"rebalance {v.name}: {len(v.moves)} services move ({v.moved_cpu_m}m cpu, {v.moved_mem_mib} MiB), "
+                     f"skew over {report.spread_topology_key} {v.skew_before} -> {v.skew_after} "
+                     f"(max_skew {report.spread_max_skew}), {v.n_stuck} attempts refused"
+                     + (f", budget {v.max_moves}" if v.max_moves is not None else "")
+                     + (" (best)" if i == report.best else ""))
+        lines += [f"  {svc}: {src} -> {dst}" + (f" (relaxed: {', '.join(v.relaxed[svc])})" if v.relaxed.get(svc) else "")
+                  for svc, src, dst in v.moves]
+        lines += [f"  {svc}: stays ({why})" for svc, why in v.stuck.items()]
+        if v.skew_after > (report.spread_max_skew or 0):
+            lines.append(f"  still out of bound: {v.lightest} is the lightest eligible domain and takes no more of these "
+                         "services; grow_stage(under_policy=True) says which servers would give it room")
+    return "\n".join(lines)
+
+
+def rebalance_report_to_dict(report: RebalanceReport) -> dict:
+    d = {"stage": report.stage, "placement": {"strategy": report.strategy, "preferred": report.preferred},
+         "pin": report.pin, "best": report.best,
+         "plan": None if report.plan is None else json.loads(plan_to_json(report.plan)),
+         "variants": [asdict(v) for v in report.variants]}
+    if report.spread_topology_key is not None:
+        d["placement"]["spread"] = {"topology_key": report.spread_topology_key, "max_skew": report.spread_max_skew}
+    if report.fallback_relax_order:
+        d["placement"]["fallback"] = {"relax_order": report.fallback_relax_order, "max_hops": report.fallback_max_hops}
+    if report.note is not None:
+        d["note"] = report.note
+    return d
+
+
+def rebalance_report_from_dict(d: dict) -> RebalanceReport:
+    pol = d.get("placement") or {}
+    variants = [RebalanceVariant(v["name"], list(v["order"]), [tuple(m) for m in v["moves"]], dict(v.get("stuck") or {}),
+                                 {k: list(x) for k, x in (v.get("relaxed") or {}).items()}, v.get("n_stuck", 0),
+                                 v.get("max_moves"), v.get("moved_cpu_m", 0), v.get("moved_mem_mib", 0),
+                                 v.get("skew_before", 0), v.get("skew_after", 0), v.get("lightest"))
+                for v in d.get("variants") or []]
+    plan = d.get("plan")
+    return RebalanceReport(d["stage"], pol.get("strategy"), list(pol.get("preferred") or []), list(d.get("pin") or []),
+                           variants, d.get("best"),
+                           None if plan is None else plan_from_json(json.dumps(plan, ensure_ascii=False)),
+                           (pol.get("spread") or {}).get("topology_key"), (pol.get("spread") or {}).get("max_skew"),
+                           list((pol.get("fallback") or {}).get("relax_order") or []),
+                           (pol.get("fallback") or {}).get("max_hops"), d.get("note"))
 
 
 def format_replan_report(report: Replan) -> str:

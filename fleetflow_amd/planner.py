@@ -836,6 +836,39 @@ class Planner:
         return self._shrink_host(cont, nodes, assign, try_order, strategy, preferred, node_count,
                                  (domain, max_skew, relax_mask))
 
+    def rebalance_sweep(self, cont, nodes, assign, victim_order, strategy=0, preferred=0, node_count=None, *,
+                        domain=None, max_skew=0, relax_mask=(), max_moves=None, want_hops=True, want_reason=True):
+        """Rebalance sweep (SPEC.md 2.19, fp_rebalance_sweep): ``nodes`` is the live table, ``assign`` [C] the node
+        each container runs on (NONE = not running), ``victim_order`` [n_var, n_try] one victim order per row
+        (container indices; NONE entries are skipped, so rows may be ragged), ``max_moves`` [n_var] the move budget
+        of each (NONE = unlimited; None = unlimited everywhere).  ``node_count`` None means derived from ``assign``,
+        not zeros.  Every variant starts from the base state and visits its entries in order: a container whose
+        node lies in a heavy domain (eligible, count - min > ``max_skew``) is lifted off its node and placed as the
+        only container of a place_policy_fallback call under ``strategy`` / ``preferred``, the spread constraint
+        (``domain`` [N] ids below 64 and ``max_skew``; None or 0 = nothing is heavy, ``domain`` is then not read)
+        and the fallback chain (``relax_mask``, at most 4 hops; empty = none); a rejected attempt leaves the state
+        exactly as it was.  Inputs are not mutated.  Returns (assign_out [n_var, C], hops [n_var, C], reason [n_var,
+        C] with REASON_NOFIT / REASON_SKEW where the container's last attempt was rejected, summary [n_var, 8]);
+        hops and reason are None when not wanted; summary's word indices are _lib.REBAL_*."""
+        cont, nodes = _tables(cont, nodes, None, None, False)
+        C, N = cont[0].size, nodes[0].size
+        asg, vo = _u32(assign), _u32(victim_order)
+        _need(vo.ndim == 2, "victim_order must be [n_var, n_try]")
+        n_var, n_try = vo.shape
+        strategy = strategy_id(strategy)
+        _need(asg.size == C, "assign must hold C entries")
+        mm = _opt_n(max_moves, n_var, "max_moves", "n_var")
+        nc, dom = _opt_n(node_count, N, "node_count"), _opt_n(domain, N, "domain")
+        max_skew, rm, n_hops = _skew_chain(max_skew, relax_mask)
+        out, summary = np.empty((n_var, C), np.uint32), np.empty((n_var, _lib.REBAL_WORDS), np.uint32)
+        hops = np.empty((n_var, C), np.uint8) if want_hops else None
+        why = np.empty((n_var, C), np.uint8) if want_reason else None
+        cs, ns = _pair(cont, nodes)
+        self._call("fp_rebalance_sweep", ct.byref(cs), ct.byref(ns), _arg(asg), _arg(vo), n_var, n_try, _arg(mm), strategy,
+                   int(preferred) & 0xFFFFFFFF, _arg(nc), _arg(dom), max_skew, _arg(rm), n_hops, _arg(out), _arg(hops),
+                   _arg(why), _arg(summary))
+        return out, hops, why, summary
+
     def grow_sweep(self, cont, reason, templates, max_new, reason_mask=1 << _lib.REASON_NOFIT, t_max=None,
                    want_assign=False):
         """Scale-out sweep (SPEC.md 2.12, fp_grow_sweep): the pending containers are those of ``cont`` whose
@@ -1013,6 +1046,36 @@ class Planner:
         self._shrink_dev(cont_t, nodes_t, assign_t, try_order_t, n_var, assign_out_t, state_t, summary_t, strategy,
                          preferred, count_t, blocker_t, (domain_t, max_skew, relax_mask, hops_t, blocker_reason_t,
                                                          policy_t))
+
+    def dev_rebalance_sweep(self, cont_t, nodes_t, assign_t, victim_order_t, n_var, assign_out_t, summary_t, strategy=0,
+                            preferred=0, count_t=None, *, domain_t=None, max_skew=0, relax_mask=(), max_moves_t=None,
+                            hops_t=None, reason_t=None):
+        """fp_dev_rebalance_sweep on device tensors: ``cont_t``, ``nodes_t``, ``assign_t`` and ``count_t`` (None =
+        derived from ``assign_t``) as in ``dev_drain_sweep``, ``victim_order_t`` [n_var * n_try], ``max_moves_t``
+        [n_var] or None, ``domain_t`` [N] or None, ``max_skew`` and ``relax_mask`` (host values, at most 4); out:
+        ``assign_out_t`` [n_var * C], ``summary_t`` [n_var * 8] and the optional ``hops_t`` and ``reason_t``
+        [n_var * C] uint8.  An assign, victim_order or domain value out of range is found on the device: nothing is
+        written and sync() raises FP_EINVAL."""
+        n_var, strategy = int(n_var), strategy_id(strategy)
+        C, N, cs, ns = _dev_tables_checks(cont_t, nodes_t)
+        _tensor("assign_t", assign_t, C, "C")
+        _need(0 <= n_var <= 0xFFFFFFFF, "n_var must be a u32")
+        _need(victim_order_t.element_size() == 4 and (victim_order_t.numel() % n_var == 0 if n_var
+                                                      else victim_order_t.numel() == 0),
+              "victim_order_t must hold n_var rows of 32-bit entries")
+        n_try = victim_order_t.numel() // n_var if n_var else 0
+        _tensor("max_moves_t", max_moves_t, n_var, "n_var", optional=True)
+        _tensor("count_t", count_t, N, "N", optional=True)
+        _tensor("domain_t", domain_t, N, "N", optional=True)
+        max_skew, rm, n_hops = _skew_chain(max_skew, relax_mask)  # rm is read during the call
+        _tensor("assign_out_t", assign_out_t, n_var * C, "n_var * C")
+        _tensor("hops_t", hops_t, n_var * C, "n_var * C", 1, True)
+        _tensor("reason_t", reason_t, n_var * C, "n_var * C", 1, True)
+        _tensor("summary_t", summary_t, n_var * _lib.REBAL_WORDS, "n_var * 8")
+        self._call("fp_dev_rebalance_sweep", ct.byref(cs), ct.byref(ns), _arg(assign_t), _arg(victim_order_t), n_var,
+                   n_try, _arg(max_moves_t), strategy, int(preferred) & 0xFFFFFFFF, _arg(count_t), _arg(domain_t),
+                   max_skew, _arg(rm), n_hops, _arg(assign_out_t), _arg(hops_t), _arg(reason_t), _arg(summary_t),
+                   dev=True)
 
     def dev_drain_sweep_policy(self, cont_t, nodes_t, assign_t, group_t, n_cand, assign_out_t, reason_t, summary_t,
                                strategy=0, preferred=0, count_t=None, *, domain_t=None, max_skew=0, relax_mask=(),

@@ -39,6 +39,11 @@
  *   fp_shrink_sweep_policy <- new: the same sweep with every move held to the policy's SpreadConstraint and
  *                        FallbackPolicy (model.rs:47-63) and every release to the bound rule: a server is given
  *                        back only if that leaves the skew within max_skew or no larger than it was
+ *   fp_rebalance_sweep <- new: the seats a live plan gives up, one after the other in a given victim order, to
+ *                        bring the policy's SpreadConstraint back within max_skew (the descheduler to the
+ *                        scheduler's PodTopologySpread), for many orders at once; each seat is re-placed under
+ *                        the constraint and the FallbackPolicy
+ *                        crates/fleetflow-controlplane/src/model.rs:56-63 and :435-442
  *   fp_grow_sweep     <- new: the new servers of each template (a plan string's size,
  *                        crates/fleetflow-cloud-sakura/src/provider.rs:15-30, with the ServerLabels /
  *                        ServerCapacity a new server would carry, crates/fleetflow-controlplane/src/model.rs:399-419)
@@ -484,6 +489,45 @@ int fp_shrink_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nodes *
                            uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
                            uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out, uint8_t *hops_out,
                            uint8_t *blocker_reason_out, uint32_t *policy_out);
+/* Rebalance sweep (SPEC.md 2.19; the SpreadConstraint of model.rs:56-63 on the live placements of model.rs:435-442):
+ * "which seats do I have to give up so that the spread holds again, and where do they go?", asked of every victim
+ * order at once.  containers, nodes (the LIVE table), assign, strategy and preferred_labels are fp_drain_sweep's;
+ * domain / max_skew are fp_place_policy_spread's and relax_mask / n_hops fp_place_policy_fallback's.  node_count is
+ * nullable and ABSENT MEANS DERIVED, not zero: node_count[n] = the number of c with assign[c] == n.  Variant v is a
+ * victim order victim_order[v][0 .. n_try): container indices, FP_NONE entries are skipped (ragged rows), with the
+ * move budget max_moves[v] (FP_NONE, or max_moves == NULL: unlimited).  Every variant starts from the base state and
+ * is independent of the others.  With dom_count[d] the u32 sum of the running node_count over all nodes of domain d,
+ * a domain eligible when it has a schedulable node, and min the least dom_count over the eligible domains, a domain
+ * is HEAVY when it is eligible and dom_count[d] - min > max_skew.  The entries are visited in order; the variant
+ * ends when its committed moves reach the budget (tested before every entry); an entry is skipped when it is
+ * FP_NONE, its container does not run, or the domain of the node it runs on is not heavy.  Every other entry is an
+ * ATTEMPT: the container is lifted off its node s (cpu_free, mem_free += its request, conflict_used &= ~conflict,
+ * node_count -= 1) and placed exactly as the only container of an fp_place_policy_fallback call on that state.  If
+ * a node takes it, that is a MOVE; otherwise the state is exactly what it was before the lift (the conflict word is
+ * put back as it was) and the attempt is STUCK with that call's reason.  A repeated entry is a fresh attempt.
+ *   assign_out  [n_var][c->n]  the variant's final assignment
+ *   hops_out    [n_var][c->n]  nullable: the hop of the container's move, 0 if it never moved
+ *   reason_out  [n_var][c->n]  nullable: FP_REASON_NOFIT / FP_REASON_SKEW if the container's last attempt was
+ *                              rejected, else 0
+ *   summary_out [n_var][FP_REBAL_WORDS]:
+ *     MOVES  committed moves      STUCK  rejected attempts      STUCK_SKEW  those whose reason is SKEW
+ *     RELAXED  moves at a hop >= 1      MOVED_CPU, MOVED_MEM  the sums of the moved containers' requests (u32, wrap)
+ *     SKEW_BEFORE, SKEW_AFTER  max - min of dom_count over the eligible domains (0 without one), base and final state
+ * domain == NULL or max_skew == 0: nothing is heavy, every assign_out row is assign, every other result is 0 and
+ * domain is not read.  There is no quota input: a move releases and retakes the same request.  nodes->n above
+ * FP_POLICY_MAX_NODES, n_var above 65535 or c->n above 0x7FFF0000 is FP_EOVERFLOW; a strategy above
+ * FP_STRATEGY_FILL_LOWEST, n_hops above FP_FALLBACK_MAX_HOPS, assign_out == assign, a required pointer that is NULL,
+ * an assign[c] that is neither < nodes->n nor FP_NONE, a victim_order entry that is neither < c->n nor FP_NONE and
+ * (with max_skew != 0) a domain[n] >= FP_SPREAD_MAX_DOMAINS are FP_EINVAL; on any error nothing is written.
+ * n_var == 0 is FP_OK.  Evicting for the quota, balancing utilisation without a spread constraint, the choice of
+ * the victim order and the final node table are not part of this call. */
+enum { FP_REBAL_MOVES = 0, FP_REBAL_STUCK = 1, FP_REBAL_STUCK_SKEW = 2, FP_REBAL_RELAXED = 3, FP_REBAL_MOVED_CPU = 4,
+       FP_REBAL_MOVED_MEM = 5, FP_REBAL_SKEW_BEFORE = 6, FP_REBAL_SKEW_AFTER = 7, FP_REBAL_WORDS = 8 };
+int fp_rebalance_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                       const uint32_t *victim_order, uint32_t n_var, uint32_t n_try, const uint32_t *max_moves,
+                       uint32_t strategy, uint32_t preferred_labels, const uint32_t *node_count,
+                       const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                       uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out, uint32_t *summary_out);
 /* Scale-out sweep (SPEC.md 2.12): "what do I have to add?", asked of every server template at once.  The pending
  * containers are those whose reason's bit is set in reason_mask (fp_explain_batch's convention; reason_mask == 0
  * selects every container and reason is not read and may be NULL).  Candidate k is a template: a new server has
@@ -719,6 +763,17 @@ int fp_dev_shrink_sweep_policy(fp_ctx *ctx, const fp_containers *c, const fp_nod
                                uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops, uint32_t *assign_out,
                                uint8_t *state_out, uint32_t *blocker_out, uint32_t *summary_out, uint8_t *hops_out,
                                uint8_t *blocker_reason_out, uint32_t *policy_out);
+/* As fp_rebalance_sweep on device pointers (every output included; relax_mask stays a HOST array of n_hops words:
+ * the masks go to the kernel by value; model.rs:56-63 and :435-442 as there).  A strategy above
+ * FP_STRATEGY_FILL_LOWEST and n_hops above FP_FALLBACK_MAX_HOPS are returned directly.  An assign, victim_order or
+ * domain value out of range is found on the device before any store: nothing is written and fp_ctx_sync() reports
+ * FP_EINVAL.  The call takes 256 bytes, and 4 bytes per node where node_count is NULL, from the context's
+ * workspace; the variants' running rows are the assign_out rows. */
+int fp_dev_rebalance_sweep(fp_ctx *ctx, const fp_containers *c, const fp_nodes *nodes, const uint32_t *assign,
+                           const uint32_t *victim_order, uint32_t n_var, uint32_t n_try, const uint32_t *max_moves,
+                           uint32_t strategy, uint32_t preferred_labels, const uint32_t *node_count,
+                           const uint32_t *domain, uint32_t max_skew, const uint32_t *relax_mask, uint32_t n_hops,
+                           uint32_t *assign_out, uint8_t *hops_out, uint8_t *reason_out, uint32_t *summary_out);
 /* As fp_grow_sweep on device pointers (max_new stays a host value: the kernel's geometry follows it, nothing is
  * read back).  A t_max[k] > max_new is found on the device before any store: nothing is written and fp_ctx_sync()
  * reports FP_EINVAL.  The call takes 28 bytes per container plus the sort's scratch from the context's workspace. */

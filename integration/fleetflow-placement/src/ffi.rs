@@ -66,6 +66,15 @@ pub const FP_SHRINK_MOVED_CPU: usize = 5;
 pub const FP_SHRINK_MOVED_MEM: usize = 6;
 pub const FP_SHRINK_FIRST_FAILED: usize = 7;
 pub const FP_SHRINK_WORDS: usize = 8;
+pub const FP_REBAL_MOVES: usize = 0;
+pub const FP_REBAL_STUCK: usize = 1;
+pub const FP_REBAL_STUCK_SKEW: usize = 2;
+pub const FP_REBAL_RELAXED: usize = 3;
+pub const FP_REBAL_MOVED_CPU: usize = 4;
+pub const FP_REBAL_MOVED_MEM: usize = 5;
+pub const FP_REBAL_SKEW_BEFORE: usize = 6;
+pub const FP_REBAL_SKEW_AFTER: usize = 7;
+pub const FP_REBAL_WORDS: usize = 8;
 pub const FP_SHRINK_STATE_NEVER: u8 = 0;
 pub const FP_SHRINK_STATE_RELEASED: u8 = 1;
 pub const FP_SHRINK_STATE_FAILED: u8 = 2;
@@ -292,6 +301,12 @@ unsafe extern "C" {
                                   relax_mask: *const u32, n_hops: u32, assign_out: *mut u32, state_out: *mut u8,
                                   blocker_out: *mut u32, summary_out: *mut u32, hops_out: *mut u8,
                                   blocker_reason_out: *mut u8, policy_out: *mut u32) -> c_int;
+    pub fn fp_rebalance_sweep(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes,
+                              assign: *const u32, victim_order: *const u32, n_var: u32, n_try: u32,
+                              max_moves: *const u32, strategy: u32, preferred_labels: u32, node_count: *const u32,
+                              domain: *const u32, max_skew: u32, relax_mask: *const u32, n_hops: u32,
+                              assign_out: *mut u32, hops_out: *mut u8, reason_out: *mut u8,
+                              summary_out: *mut u32) -> c_int;
     pub fn fp_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32, n_cand: u32,
                          t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32, t_max: *const u32,
                          max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;
@@ -374,6 +389,12 @@ unsafe extern "C" {
                                       assign_out: *mut u32, state_out: *mut u8, blocker_out: *mut u32,
                                       summary_out: *mut u32, hops_out: *mut u8, blocker_reason_out: *mut u8,
                                       policy_out: *mut u32) -> c_int;
+    pub fn fp_dev_rebalance_sweep(ctx: *mut fp_ctx, c: *const fp_containers, nodes: *const fp_nodes,
+                              assign: *const u32, victim_order: *const u32, n_var: u32, n_try: u32,
+                              max_moves: *const u32, strategy: u32, preferred_labels: u32, node_count: *const u32,
+                              domain: *const u32, max_skew: u32, relax_mask: *const u32, n_hops: u32,
+                              assign_out: *mut u32, hops_out: *mut u8, reason_out: *mut u8,
+                              summary_out: *mut u32) -> c_int;
     pub fn fp_dev_grow_sweep(ctx: *mut fp_ctx, c: *const fp_containers, reason: *const u8, reason_mask: u32,
                              n_cand: u32, t_cpu: *const u32, t_mem: *const u32, t_labels: *const u32,
                              t_max: *const u32, max_new: u32, summary_out: *mut u32, assign_out: *mut u32) -> c_int;

@@ -238,6 +238,47 @@ impl Planner {
         Ok((out, hops, state, blocker, why, rows, prows))
     }
 
+    /// Rebalance sweep (SPEC.md 2.19, fleetplace.h `fp_rebalance_sweep`): variant v visits the containers of
+    /// `victim_order[v * n_try ..][.. n_try]` (`ffi::FP_NONE` entries are skipped) and lifts every one whose node
+    /// lies in a heavy domain (eligible, count - min > `max_skew`) off its node, to place it as the only container
+    /// of a `fp_place_policy_fallback` call; a rejected attempt leaves the state as it was.  `max_moves`: the move
+    /// budget per variant (None or `ffi::FP_NONE` = unlimited); `node_count` None means derived from `assign`.
+    /// Returns per variant (the final node, the hop of the move and the reason of a rejected last attempt per
+    /// container, and its row of `ffi::FP_REBAL_WORDS` words).
+    #[allow(clippy::too_many_arguments, clippy::type_complexity)]
+    pub fn rebalance_sweep(&mut self, c: &Containers, nodes: &Nodes, assign: &[u32], victim_order: &[u32], n_try: u32,
+                           max_moves: Option<&[u32]>, strategy: u32, preferred_labels: u32,
+                           node_count: Option<&[u32]>, domain: Option<&[u32]>, max_skew: u32, relax_mask: &[u32])
+                           -> Result<(Vec<u32>, Vec<u8>, Vec<u8>, Vec<[u32; ffi::FP_REBAL_WORDS]>), PlanError> {
+        let (n, nn) = (c.cpu_m.len(), nodes.cpu_free.len());
+        let n_var = if n_try == 0 { 0 } else { victim_order.len() / n_try as usize };
+        if !c.all_len(n) || !nodes.all_len(nn) || assign.len() != n || victim_order.len() != n_var * n_try as usize
+            || n_var > u32::MAX as usize || max_moves.map_or(false, |m| m.len() != n_var)
+            || node_count.map_or(false, |k| k.len() != nn) || domain.map_or(false, |d| d.len() != nn)
+            || relax_mask.len() > ffi::FP_FALLBACK_MAX_HOPS as usize {
+            return Err(PlanError(ffi::FP_EINVAL));
+        }
+        let cs = ffi::fp_containers { n: n as u32, cpu_m: c.cpu_m.as_ptr(), mem_mib: c.mem_mib.as_ptr(),
+                                      req_labels: c.req_labels.as_ptr(), conflict: c.conflict.as_ptr() };
+        // the sweep reads the node table only: the mutable pointers of fp_nodes are never written through
+        let ns = ffi::fp_nodes { n: nn as u32, cpu_free: nodes.cpu_free.as_ptr() as *mut u32,
+                                 mem_free: nodes.mem_free.as_ptr() as *mut u32, labels: nodes.labels.as_ptr(),
+                                 conflict_used: nodes.conflict_used.as_ptr() as *mut u32,
+                                 schedulable: nodes.schedulable.as_ptr() };
+        let (mut out, mut hops, mut why) = (vec![0u32; n_var * n], vec![0u8; n_var * n], vec![0u8; n_var * n]);
+        let mut rows = vec![[0u32; ffi::FP_REBAL_WORDS]; n_var];
+        check(unsafe {
+            ffi::fp_rebalance_sweep(self.ctx, &cs, &ns, assign.as_ptr(), victim_order.as_ptr(), n_var as u32, n_try,
+                                    max_moves.map_or(std::ptr::null(), |m| m.as_ptr()), strategy, preferred_labels,
+                                    node_count.map_or(std::ptr::null(), |k| k.as_ptr()),
+                                    domain.map_or(std::ptr::null(), |d| d.as_ptr()), max_skew,
+                                    if relax_mask.is_empty() { std::ptr::null() } else { relax_mask.as_ptr() },
+                                    relax_mask.len() as u32, out.as_mut_ptr(), hops.as_mut_ptr(), why.as_mut_ptr(),
+                                    rows.as_mut_ptr() as *mut u32)
+        })?;
+        Ok((out, hops, why, rows))
+    }
+
     /// The drain sweep under the policy (SPEC.md 2.15, fleetplace.h `fp_drain_sweep_policy`): `drain_sweep` with
     /// every move held to the spread constraint (`domain` ids below `ffi::FP_SPREAD_MAX_DOMAINS` and `max_skew`;
     /// None or 0 = none) and the fallback chain (`relax_mask`: per hop the label bits it gives up, at most
