@@ -366,6 +366,18 @@ constexpr uint32_t SYS_MAX_G = 4;
 #ifndef FPP_BIGP_WAVES
 #define FPP_BIGP_WAVES 7
 #endif
+// FPP_BIGP_LAZY: no prescan in the no-mask kernel.  Every valid lane has the same candidate groups there,
+//   so group g's queue is what is left of the batch, and g is worth entering exactly when its corner holds
+//   a node: the corner ballot is taken where the walk reaches the group (fpp_groups_lazy below), and `cand`
+//   and the per-lane `nxt` go.  Placements in earlier groups touch other nodes, so a group's corner is the
+//   same taken before the walk or at the group: the same plans.  A batch with nothing left enters no further
+//   group: 1 tests `remaining` at every group; 2 closes the walk's corner instead (fpp_group_lazy_p), so
+//   that a group with an empty corner costs four instructions and one branch.  0: the prescan and
+//   fpp_groups, as in the u32 twin.  Config-4 FFD 9.55-9.62 (0) / 9.23-9.25 (1) / 8.98-9.16 ms (2)
+//   (profiles/r15_ab_l2.jsonl).
+#ifndef FPP_BIGP_LAZY
+#define FPP_BIGP_LAZY 2
+#endif
 constexpr uint32_t BIGP_WV = 7;  // the WV that names bigp in fp_pipe_tus.h
 constexpr bool is_bigp(uint32_t G, uint32_t BLK, uint32_t WV, bool PK) {
     return G == 12 && BLK == 64 && WV == BIGP_WV && PK;
@@ -507,6 +519,51 @@ __device__ __forceinline__ void fpp_groups(std::integer_sequence<uint32_t, gs...
             }
         }(),
         ...);
+}
+
+// One group of the lazy walk (fpp_groups_lazy below; the no-mask kernel, where every lane of the
+// batch has the same candidate groups): the group's corner is tested here, and its queue is `remaining`,
+// the lanes of the batch not yet placed (wave-uniform).  The serial loop and the used bits are
+// fpp_group_xp's and fpp_groups'.  CLOSE (FPP_BIGP_LAZY 2): when nothing remains the walk's corner qw
+// becomes PK_GUARD, a demand no record can take (a 0x8000 field always borrows), so every group above
+// reads as empty and an empty group costs the corner test alone; else (1) each group tests `remaining`.
+template <uint32_t g, bool CLOSE>
+__device__ __forceinline__ void fpp_group_lazy_p(uint64_t &remaining, uint32_t &asg, uint32_t &used, uint32_t &rw,
+                                                 uint32_t &rcu, uint32_t rlab, uint32_t cw, uint32_t req,
+                                                 uint32_t conf, uint32_t gb64, uint32_t &nchk, uint32_t &nhit,
+                                                 unsigned long long (&gst)[4], uint32_t &qw) {
+    if (!CLOSE && !remaining) return;
+    if (!__builtin_amdgcn_ballot_w64(pk_fits(rw, qw))) return;  // an empty corner: no container fits
+    uint64_t touched = 0;
+    const unsigned long long gc0 = STAT_GCLK();
+    fpp_refilter_loop_p(remaining, touched, asg, rw, rcu, rlab, cw, req, conf, gb64 + g * 64u, nchk, qw);
+    const uint64_t hit = remaining & __builtin_amdgcn_ballot_w64(asg != 0xFFFFFFFFu);
+#ifdef FP_PIPE_STATS
+    nhit += (uint32_t)__builtin_popcountll(hit);
+#else
+    (void)nhit;
+#endif
+    remaining = fpp_uniform64(remaining & ~hit);
+    if (CLOSE) qw = remaining ? qw : PK_GUARD;
+    const unsigned long long gc1 = STAT_GCLK();
+    if (STAT_FINE) { gst[0] += gc1 - gc0; gst[2] += 1; gst[3] += (uint32_t)__builtin_popcountll(touched); }
+    if (touched) used = fpp_lane_sel<true>(touched, used | (1u << g), used);
+    if (STAT_FINE) gst[1] += STAT_GCLK() - gc1;
+}
+
+// The group walk of the no-mask packed kernel (FPP_BIGP_LAZY): `remaining` (wave-uniform) is the batch's
+// lanes still to place.  An active group runs fpp_groups' serial loop and used-bit bookkeeping on
+// `remaining` as its queue; a batch with nothing left enters no further group.
+template <uint32_t G, uint32_t... gs, class Rec>
+__device__ __forceinline__ void fpp_groups_lazy(std::integer_sequence<uint32_t, gs...>, uint64_t &remaining,
+                                                uint32_t &asg, uint32_t &used, Rec &rcf, Rec &rcu, const Rec &rlab,
+                                                uint32_t req, uint32_t conf, uint32_t gb64, uint32_t &nchk,
+                                                uint32_t &nhit, unsigned long long (&gst)[4], uint32_t cw,
+                                                uint32_t qw) {
+    static_assert(G <= 32, "used bits of the lazy walk: one word");
+    (fpp_group_lazy_p<gs, FPP_BIGP_LAZY == 2>(remaining, asg, used, rcf[gs], rcu[gs], rlab[gs], cw, req, conf, gb64,
+                                              nchk, nhit, gst, qw),
+     ...);
 }
 
 // BLK: 1024 for multi-stage segments (W <= 16 waves, <= 128 VGPRs each); 64 for the one-wave
@@ -1009,9 +1066,11 @@ k_ffd_pipe(const PipeArgs a_arg) {
         // every mask load is issued before the first use (no per-group LDS round trip)
         const uint32_t oc = kc * 2, om = km * 2 + 1;
         constexpr bool prescan_skip = G > SYS_MAX_G;
+        // LZ: bigp's lazy walk (FPP_BIGP_LAZY): no prescan, each corner is tested where the walk reaches it
+        constexpr bool LZ = NM && FPP_BIGP_LAZY;
         GM cand = 0;
 #pragma unroll
-        for (uint32_t g = 0; g < G; ++g) {
+        for (uint32_t g = 0; g < (LZ ? 0u : G); ++g) {
             const uint64_t e = PK ? __builtin_amdgcn_ballot_w64(pk_fits(rcf[g], qw))
                                   : (__builtin_amdgcn_ballot_w64(rcf[g] >= qc) & __builtin_amdgcn_ballot_w64(rmf[g] >= qm));
             const uint64_t *mg = Mw + (size_t)g * K * 2;
@@ -1043,7 +1102,9 @@ k_ffd_pipe(const PipeArgs a_arg) {
             }
         }
         const bool zero = DB_EARLY ? zero_early : valid && (cpu | mem | req | conf) == 0u;
-        uint64_t todo = __builtin_amdgcn_ballot_w64(cand != 0 && !zero);
+        uint64_t todo;
+        if constexpr (LZ) todo = __builtin_amdgcn_ballot_w64(valid && !zero);  // every valid lane: the same candidates
+        else todo = __builtin_amdgcn_ballot_w64(cand != 0 && !zero);
         uint64_t placed = 0;
         uint32_t my_assign = FP_NONE;
         if (STAT_ON) {
@@ -1066,7 +1127,22 @@ k_ffd_pipe(const PipeArgs a_arg) {
         // g after exactly the earlier containers that reached g -- the sequential first
         // fit, bit for bit -- and every record access has a static register index (no
         // s_set_gpr_idx windows, no indexed copies).
-        {
+        if constexpr (LZ) {
+            // the same candidates for every lane: group g's queue is whatever of the batch is not yet placed
+            uint32_t nchk = 0, nhit = 0;
+            unsigned long long gst[4] = {0, 0, 0, 0};
+            if (prio == 1u && todo) __builtin_amdgcn_s_setprio(FP_PRIO_LEVEL);
+            if (todo) {
+                uint64_t remaining = todo;
+                fpp_groups_lazy<G>(std::make_integer_sequence<uint32_t, G>{}, remaining, my_assign, usedbits,
+                                   rcf, rcu, rlab, req, conf, __builtin_amdgcn_readfirstlane(gbase * 64u), nchk, nhit,
+                                   gst, cw, qw);
+                placed = todo & ~remaining;
+            }
+            if (prio == 1u && todo) __builtin_amdgcn_s_setprio(0);
+            if (STAT_ON) { st_checks += nchk; st_hits += nhit; }
+            if (STAT_FINE) { ck_gx += gst[0]; ck_gu += gst[1]; st_queues += (uint32_t)gst[2]; st_touched += (uint32_t)gst[3]; }
+        } else {
             uint32_t nxt = ((todo >> lane) & 1ull) ? (cand ? (uint32_t)__builtin_ctzll((uint64_t)cand) : G) : G;
             // the hand-scheduled loop of fp_pipe_asm.h, one asm block per (static) group;
             // one-group stages leave their bucket masks at the tile's start state (still

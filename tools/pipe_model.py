@@ -11,7 +11,10 @@ segment's lifetime (s_memtime from its start to the end of its stream).  With la
 the segments of a scenario run phase by phase, so
     model_ms = S x sum_b life_b / slots / clock
 and the busy share of a lifetime is the exact checks + prescans; the rest is input
-waits, forwarding and the per-batch bookkeeping.
+waits, forwarding and the per-batch bookkeeping.  (The packed 4096-scenario kernel tests
+each group's corner inside its group walk, FPP_BIGP_LAZY: there prescan_Mcycles holds
+only the batch corner, the pack and the next batch's request, and the corner tests are
+part of cand_Mcycles.  busy = prescan + cand either way.)
 config 3 (one scenario, one-group stages): every container walks the stages in FFD order
 until a node of the stage fits it.  Reported: container-stage visits, exact checks,
 placements and the summed busy cycles over the launch's cycles (the average number of
@@ -120,6 +123,8 @@ def main():
         checks, hits, visits = per(1), per(2), per(0)
         busy = per(9) + per(10)
         raw[leg] = {"geometry": g, "kernel_ms_diag_build": kms, "placed": placed,
+                    "note": "kernels with the lazy group walk (FPP_BIGP_LAZY): the per-group corner tests are in "
+                            "cand_Mcycles, not prescan_Mcycles",
                     "per_stage_slot": [{"visits": r[0] / S, "checks": r[1] / S, "hits": r[2] / S, "batches": r[3] / S,
                                         "input_Mcycles": r[8] / S / 1e6, "prescan_Mcycles": r[9] / S / 1e6,
                                         "cand_Mcycles": r[10] / S / 1e6, "fwd_Mcycles": r[11] / S / 1e6,
