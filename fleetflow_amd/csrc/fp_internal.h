@@ -341,8 +341,23 @@ struct fp_pipe_soa {
     // screen) and the sort's last phase wrote s_req, s_conf and the skip bits, so fp_pipe_launch runs neither
     uint32_t *summ = nullptr;
     bool payload_done = false;
+    // set by the fused sort's prepack mode: the per-scenario header [S][4] = {sc_c, sc_m, packs_s, 0}.  A
+    // scenario with packs_s = 1 has ONE demand row, s_w = packed (cpu, mem) | skip << 31, in its s_cpu row, and
+    // nothing in its s_mem / s_idx rows (fp_pipe_launch: k_unpack_rows, the prepacked-input kernel)
+    uint32_t *pkhdr = nullptr;
 };
 int fp_pipe_soa_take(fp_ctx *c, size_t SC, fp_pipe_soa *soa);
+// Prepack mode of the fused sort for S x C x N on this context: the launch will be the 4096-scenario pair
+// (big / its packed no-mask twin) and FP_OPT_PREPACK allows it.  The same test decides in fp_pipe_launch
+// which packed kernel runs, so the caller sets fp_pipe_soa::pkhdr exactly when this holds.
+bool fp_pipe_prepack(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N);
+// The shifts of packed (cpu, mem) records for the OR words of a value set, and whether the set packs
+// (fp_pipe_pk.h): k_ffd_pipe's rule for the batch, k_scen_sort's for a scenario
+__host__ __device__ static inline bool fp_pk_shifts(uint32_t orc, uint32_t orm, uint32_t *sc_c, uint32_t *sc_m) {
+    *sc_c = orc ? (uint32_t)__builtin_ctz(orc) : 0u;
+    *sc_m = orm ? (uint32_t)__builtin_ctz(orm) : 0u;
+    return (orc >> *sc_c) <= 0x7FFFu && (orm >> *sc_m) <= 0x7FFFu;
+}
 // 1 when the position word carries the bucket indices (bits 21-30)
 uint32_t fp_pipe_kpack(const fp_ctx *c, uint32_t C);
 // ready: the per-scenario LDS sort already wrote order, s_cpu, s_mem and s_idx (only the

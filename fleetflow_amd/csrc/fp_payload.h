@@ -27,7 +27,10 @@ constexpr uint32_t PL_SKIP = 0x80000000u;
 // PL_FIELD_CHUNK words: level leaves a CYCLE bit per position, conf is written as soon as its last chunk
 // has been picked and leaves the bit (conf & summ[1]) != 0, req joins the bits and is written with the
 // reason codes.  Per container 4 B of order (none in the fused sort) and 4 B per field are read, 8 B
-// written and s_idx touched where the bit is set.
+// written and the skip-bit row touched where the bit is set.
+// The skip-bit row (`s_skip` below) is s_idx -- or, for a scenario the fused sort's prepack mode wrote as one
+// packed demand row (fp_place.hip), that row s_w, whose bit 31 is a guard bit of the packed word and clear
+// by construction: the same bit, the same store / barrier / agent-scope load order.
 constexpr uint32_t PL_ROWS = 2 * PL_H;
 constexpr uint32_t PL_FIELD_CHUNK = 36 * 1024;  // words of one field: 144 KB of LDS
 constexpr size_t PL_FIELD_LDS_BYTES = (size_t)PL_FIELD_CHUNK * 4;
@@ -95,13 +98,13 @@ __device__ __forceinline__ void pl_indices(uint32_t C, const uint32_t *ord, cons
 // The whole gather for one scenario (blockIdx.x): its summ words, the indices, then the level, conf and req
 // passes and the stores.  pl_lds: PL_FIELD_LDS_BYTES of LDS.  SAME_WG = false: the indices come from `order`,
 // which an earlier kernel wrote (k_payload_lds).  SAME_WG = true (the fused sort): from X when from_x (uniform
-// in the workgroup), else from `order`; the row, and the s_idx words the skip bit is ORed into, were stored by
+// in the workgroup), else from `order`; the row, and the words of s_skip (s_idx or s_w, above) the skip bit is ORed into, were stored by
 // other waves of this workgroup (drained before a barrier, see pl_indices) and are read at agent scope.
 template <bool SAME_WG>
 __device__ __forceinline__ void pl_by_field(uint32_t *pl_lds, uint32_t C, const uint32_t *order, const uint16_t *X,
                                             bool from_x, const uint32_t *req, const uint32_t *conf,
                                             const uint32_t *level, const uint32_t *summ, uint32_t *s_req,
-                                            uint32_t *s_conf, uint32_t *s_idx) {
+                                            uint32_t *s_conf, uint32_t *s_skip) {
     const uint32_t t = threadIdx.x;
     const size_t cb = (size_t)blockIdx.x * C;
     const uint32_t sm0 = summ ? summ[(size_t)blockIdx.x * 4] : 0xFFFFFFFFu;
@@ -146,7 +149,7 @@ __device__ __forceinline__ void pl_by_field(uint32_t *pl_lds, uint32_t C, const 
     pl_pick_field(pl_lds, req + cb, C, o, v);
     uint32_t tr = t, Cr = C;
     asm volatile("" : "+v"(tr), "+s"(Cr));
-    uint32_t *const d_req = s_req + cb, *const d_idx = s_idx + cb;
+    uint32_t *const d_req = s_req + cb, *const d_idx = s_skip + cb;
 #pragma unroll
     for (uint32_t j = 0; j < PL_ROWS; ++j) {
         const uint32_t p = tr + PL_THREADS * j;

@@ -135,8 +135,13 @@ struct PipeArgs {
     // (containers and schedulable nodes; k_scen_sort / k_ffd_keys / k_node_summary), and the mode:
     // 0 = the u32 kernel alone; 1 / 2 = the u32 / packed kernel of a pair launched back to back,
     // each running the batch only when the values do not / do pack (the other one returns)
-    uint32_t *rng;  // [3]: [2] = the kernel that ran (1 u32, 2 packed; fp_ctx_place_path)
+    uint32_t *rng;  // [4]: [2] = the kernel that ran (1 u32, 2 packed, 3 packed with prepacked input;
+                    // fp_ctx_place_path), [3] = scenarios k_unpack_rows repaired
     uint32_t pk_mode;
+    // prepacked demand rows (k_scen_sort's prepack mode, fp_place.hip): [S][4] per scenario {sc_c, sc_m,
+    // packs_s}; the row s_cpu then holds s_w = packed (cpu, mem) | skip << 31 for a scenario with packs_s = 1.
+    // Read by the prepacked-input kernel (PW) alone; null when the sort wrote the legacy rows
+    const uint32_t *pkhdr;
 };
 
 // Control words (heads, tails, counts, abort flags) are read by every lane at one address: the
@@ -378,6 +383,21 @@ constexpr uint32_t SYS_MAX_G = 4;
 #ifndef FPP_BIGP_LAZY
 #define FPP_BIGP_LAZY 2
 #endif
+// FPP_PREPACK: the fused sort may write one packed demand row per scenario (k_scen_sort's prepack mode,
+//   fp_place.hip) where the pair big / bigp will run; 0: never, the three legacy rows
+//   and today's bigp, line for line (FP_OPT_PREPACK = 0 is the same choice per context).
+// FPP_PREPACK_FFD: 1: the prepacked-input form of bigp (bigpw: PW below, fp_pipe_tus.h PK = 2) reads the
+//   row; 0: the sort still writes it, k_unpack_rows turns every such scenario back into the legacy rows
+//   and bigp reads those (the A/B that attributes the gain to the sort and to the FFD kernel).
+#ifndef FPP_PREPACK
+#define FPP_PREPACK 1
+#endif
+#ifndef FPP_PREPACK_FFD
+#define FPP_PREPACK_FFD 1
+#endif
+// the row has no bucket bits and the prepacked-input kernel was written for the lazy walk and the early
+// double buffer: a build without them keeps the legacy rows
+constexpr bool PREPACK_OK = FPP_PREPACK && FPP_BIGP_NOMASK && FPP_BIGP_LAZY != 0 && FPP_LOOKAHEAD == 3;
 constexpr uint32_t BIGP_WV = 7;  // the WV that names bigp in fp_pipe_tus.h
 constexpr bool is_bigp(uint32_t G, uint32_t BLK, uint32_t WV, bool PK) {
     return G == 12 && BLK == 64 && WV == BIGP_WV && PK;
@@ -598,13 +618,22 @@ constexpr uint32_t WIDE_WAVES = 3, WIDE12_WAVES = 5;
 // FFD 15.62 -> 15.06 ms, config 3 64.3 -> 63.6 ms; r03aa/r03ab).  Measured slower and removed in
 // round 4: per-group capacity bounds in place of the corner ballots (15.73 vs 15.08
 // ms, r03af), req / conf of link input loaded after the prescan (15.45 vs 15.08 ms, r03ac).
-template <uint32_t G, uint32_t BLK, uint32_t WV = 0, bool PK = false>
+// PW: the prepacked-input form of bigp (FPP_PREPACK above).  The scenario's demands arrive as one row
+// s_w = packed (cpu, mem) | skip << 31 in place of s_cpu, s_mem and s_idx, packed by k_scen_sort with the
+// scenario's OWN shifts (its header row, PipeArgs::pkhdr), which also pack and unpack the node records.
+// Invariant (k_scen_sort states its side): a batch that packs by rng packs in every scenario -- a
+// scenario's OR words are the ones it ORs into rng, plus its nodes', so its bits are a subset of rng's, its
+// shifts are >= the batch's and its fields <= the batch's -- and packed arithmetic is exact under any
+// shifts that divide every value: the same plans.  A visit gathers three words (w, req, conf), segment 0
+// takes a container's position from its load index, and links carry plain positions.
+template <uint32_t G, uint32_t BLK, uint32_t WV = 0, bool PK = false, bool PW = false>
 __global__ __launch_bounds__(BLK, BLK == 64 ? (is_bigp(G, BLK, WV, PK) ? FPP_BIGP_WAVES
                                                 : WV   ? WV
                                                 : G == 12 ? WIDE12_WAVES
                                                           : WIDE_WAVES)
                                                : 1) void
 k_ffd_pipe(const PipeArgs a_arg) {
+    static_assert(!PW || is_bigp(G, BLK, WV, PK), "prepacked input: bigp alone (launched only when PREPACK_OK)");
     // the arguments are read through the kernarg segment (memory), not promoted to SGPRs for the
     // whole kernel: held in SGPRs they spilled into VGPR lanes (wide kernel: 781 v_readlane vs 296,
     // config-4 FFD 16.7 vs 15.2 ms; narrow kernel by value: config 3 65.9 vs 65.0 ms, r04o A/B)
@@ -645,7 +674,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
         const bool packs = (orc >> sc_c) <= PK_FIELD_MAX && (orm >> sc_m) <= PK_FIELD_MAX;
         if (packs != PK) return;  // uniform: the other kernel of the pair takes the batch
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && a.rng) a.rng[2] = PK ? 2u : 1u;  // fp_ctx_place_path
+    if (blockIdx.x == 0 && threadIdx.x == 0 && a.rng) a.rng[2] = PK ? (PW ? 3u : 2u) : 1u;  // fp_ctx_place_path
     for (uint32_t i = threadIdx.x; i < (W - 1) * 8 + 8; i += blockDim.x) CTL[i] = 0;
     __syncthreads();
     // Ticket order = start order.  Ticket t is round r = t / B, segment b = t % B, and
@@ -683,6 +712,12 @@ k_ffd_pipe(const PipeArgs a_arg) {
     if (tk == 0xFFFFFFFFu) return;  // uniform: every wave of the workgroup leaves
     const uint32_t b = tk % B, s = tk / B - b * a.lag;
     const size_t cb = (size_t)s * C, nb = (size_t)s * N;
+    if constexpr (PW) {
+        // the scenario's own shifts (k_scen_sort packed its row with them; packs_s = 1 by the invariant
+        // above, since the batch packs); the batch-level test and report above stay on rng
+        sc_c = __builtin_amdgcn_readfirstlane(a.pkhdr[(size_t)s * 4]);
+        sc_m = __builtin_amdgcn_readfirstlane(a.pkhdr[(size_t)s * 4 + 1]);
+    }
 
     // ---- stage the tile into LDS and build the bucket masks ----
     // lane k < 32 holds Tc[k], lane 32 + k holds Tm[k] (K == 32: one wave covers both)
@@ -793,6 +828,9 @@ k_ffd_pipe(const PipeArgs a_arg) {
     // nf_n is the next slot's count.  Only the 12-group kernels (bigp, w12p): the wider ones were not
     // measured
     constexpr bool DB = BLK == 64 && G == 12 && PK && FPP_LOOKAHEAD >= 3, DB_EARLY = DB && FPP_LOOKAHEAD == 3;
+    // the prepacked-input kernel is written for the early double buffer alone; a build without it never
+    // launches PW (PREPACK_OK: fp_pipe_prepack returns false there)
+    static_assert(!PW || !PREPACK_OK || DB_EARLY, "prepacked input needs the early double buffer");
     [[maybe_unused]] uint32_t nf_cpu = 0, nf_mem = 0, nf_req = 0, nf_conf = 0, nf_idx = 0, nf_n = 0;
     [[maybe_unused]] bool nf_ok = false;
     // DB_EARLY: the pair's next values, in flight across the group loop.  Loading them into the pair
@@ -819,15 +857,18 @@ k_ffd_pipe(const PipeArgs a_arg) {
             nf_ok = true;                                                                               \
         }                                                                                               \
         const size_t o_ = cb + off_;                                                                    \
-        nf_cpu = g_ld_w(a.s_cpu + o_);                                                                  \
-        nf_mem = g_ld_w(a.s_mem + o_);                                                                  \
+        nf_cpu = g_ld_w(a.s_cpu + o_); /* PW: the packed word s_w, and no mem / position rows */        \
+        if constexpr (!PW) nf_mem = g_ld_w(a.s_mem + o_);                                               \
         nf_req = g_ld_w(a.s_req + o_);                                                                  \
         nf_conf = g_ld_w(a.s_conf + o_);                                                                \
-        if (!g_in) nf_idx = g_ld_w(a.s_idx + o_);                                                       \
-        else if (!DB_EARLY) nf_idx = la_pos;                                                            \
+        if constexpr (!PW) { /* (PW: DB_EARLY, asserted above; segment 0 has no position row) */        \
+            if (!g_in) nf_idx = g_ld_w(a.s_idx + o_);                                                   \
+            else if (!DB_EARLY) nf_idx = la_pos;                                                        \
+        }                                                                                               \
         if (DB_EARLY && g_in) { /* two slots deep: the pair held slot itail's words, the next batch's */ \
             la_ok = itail + 1u < ihead_seen;                                                            \
-            const uint32_t *sn_ = la_ok ? gin_data + (size_t)GSLOT(itail + 1u) * LSLOT : a.s_idx + cb;  \
+            const uint32_t *sn_ = la_ok ? gin_data + (size_t)GSLOT(itail + 1u) * LSLOT                  \
+                                        : (PW ? a.s_cpu : a.s_idx) + cb;                                \
             la2_n = g_ld(sn_);                                                                          \
             la2_pos = g_ld(sn_ + (la_ok ? 64u + lane : 0u));                                            \
         }                                                                                               \
@@ -856,6 +897,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
         const unsigned long long tl_top = ck_a;  // timeline: the previous batch's end
         unsigned long long tl_avail = ck_a;      // timeline: this batch's input available
 #endif
+        // (PW: `cpu` holds the packed word s_w, skip bit included until segment 0 has read it; `mem` stays 0)
         uint32_t cpu = 0, mem = 0, req = 0, conf = 0, idx = 0;
         bool valid = false;
         if (g_in) {
@@ -916,7 +958,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
             if (DB && nf_ok) {  // lanes past the count hold position 0's fields: zero, as below
                 idx = valid ? pos : 0u;
                 cpu = valid ? nf_cpu : 0u;
-                mem = valid ? nf_mem : 0u;
+                if constexpr (!PW) mem = valid ? nf_mem : 0u;
                 req = valid ? nf_req : 0u;
                 conf = valid ? nf_conf : 0u;
             } else {
@@ -924,7 +966,7 @@ k_ffd_pipe(const PipeArgs a_arg) {
                     idx = pos;  // the packed s_idx word (position | buckets)
                     const uint32_t p = pos & pmask;
                     cpu = a.s_cpu[cb + p];
-                    mem = a.s_mem[cb + p];
+                    if constexpr (!PW) mem = a.s_mem[cb + p];
                     req = a.s_req[cb + p];
                     conf = a.s_conf[cb + p];
                 }
@@ -939,21 +981,23 @@ k_ffd_pipe(const PipeArgs a_arg) {
             valid = i < C;
             if (DB && nf_ok) {  // rows requested one batch early (clamped at C: zero past it, as below)
                 cpu = valid ? nf_cpu : 0u;
-                mem = valid ? nf_mem : 0u;
+                if constexpr (!PW) mem = valid ? nf_mem : 0u;
                 req = valid ? nf_req : 0u;
                 conf = valid ? nf_conf : 0u;
-                idx = valid ? nf_idx : 0u;
+                if constexpr (!PW) idx = valid ? nf_idx : 0u;
             } else {
                 if (valid) {
                     cpu = a.s_cpu[cb + i];
-                    mem = a.s_mem[cb + i];
+                    if constexpr (!PW) mem = a.s_mem[cb + i];
                     req = a.s_req[cb + i];
                     conf = a.s_conf[cb + i];
-                    idx = a.s_idx[cb + i];
+                    if constexpr (!PW) idx = a.s_idx[cb + i];
                 }
                 if constexpr (DB) __builtin_amdgcn_s_waitcnt(VMCNT0);  // as in the link branch
             }
-            const bool cyc = valid && (idx & CYC);
+            // PW: the position is the load index (row P holds FFD position P), the skip bit is s_w's bit 31
+            if constexpr (PW) idx = valid ? i : 0u;
+            const bool cyc = valid && ((PW ? cpu : idx) & CYC);
             if (cyc) {  // CYCLE member, or screened out by stage 2 (NOFIT): s_req holds the reason
                 const uint32_t j = idx & pmask;
                 a.assign[cb + j] = FP_NONE;
@@ -1051,11 +1095,23 @@ k_ffd_pipe(const PipeArgs a_arg) {
         // the valid lanes are a prefix holding the batch in FFD order (cpu non-increasing), so the
         // smallest cpu is the last valid lane's
         const uint64_t vm = __builtin_amdgcn_ballot_w64(valid);
-        const uint32_t qc = vm ? __builtin_amdgcn_readlane(cpu, 63 - __builtin_clzll(vm)) : 0xFFFFFFFFu;
-        const uint32_t qm = wave_min(valid ? mem : 0xFFFFFFFFu);
-        // packed demands (this batch's values are multiples of the shifts: exact)
-        const uint32_t cw = PK ? pk_pack(cpu, mem, sc_c, sc_m) : 0u;
-        const uint32_t qw = PK ? pk_pack(qc, qm, sc_c, sc_m) : 0u;
+        uint32_t qc, qm, cw, qw;
+        if constexpr (PW) {
+            // the demands arrive packed: a lane that is not (or no longer: segment 0's skipped containers) valid
+            // holds 0, so the skip bit is gone before any use.  The corner from the packed words: the high
+            // field of the last valid lane is the batch's smallest cpu, a wave minimum of the low field its
+            // smallest mem; without a valid lane, a demand no record can take (nothing reads it: no todo)
+            cw = valid ? cpu : 0u;
+            qc = qm = 0u;
+            const uint32_t ql = wave_min(valid ? cw & 0xFFFFu : 0xFFFFFFFFu);
+            qw = vm ? (__builtin_amdgcn_readlane(cw, 63 - __builtin_clzll(vm)) & 0xFFFF0000u) | ql : PK_GUARD;
+        } else {
+            qc = vm ? __builtin_amdgcn_readlane(cpu, 63 - __builtin_clzll(vm)) : 0xFFFFFFFFu;
+            qm = wave_min(valid ? mem : 0xFFFFFFFFu);
+            // packed demands (this batch's values are multiples of the shifts: exact)
+            cw = PK ? pk_pack(cpu, mem, sc_c, sc_m) : 0u;
+            qw = PK ? pk_pack(qc, qm, sc_c, sc_m) : 0u;
+        }
         // cpu and mem are dead from here on in a packed kernel (the all-zero test is taken first): the
         // next batch is requested into registers that stay live across the prescan and the group loop
         [[maybe_unused]] bool zero_early = false;
@@ -1480,6 +1536,12 @@ __global__ __launch_bounds__(256) void k_node_summary(uint32_t N, const uint32_t
         if (RANGE) {
             fp_or_new_bits(&rng[0], oc);
             fp_or_new_bits(&rng[1], om);
+            // ... and per scenario, in the free words of its row: the sort's prepack mode (fp_place.hip) packs a
+            // scenario's demands with shifts from its own OR words, these two among them
+            if (SUMM) {
+                summ[(size_t)blockIdx.x * 4 + 2] = oc;
+                summ[(size_t)blockIdx.x * 4 + 3] = om;
+            }
         }
     }
 }
@@ -1722,6 +1784,44 @@ __global__ __launch_bounds__(1024) void k_payload_lds(uint32_t C, const uint32_t
 }
 #endif  // FPP_PAYLOAD_BY_FIELD
 
+// The repair pass of the sort's prepack mode (fp_place.hip), between the sort and the FFD pair, one workgroup
+// per scenario.  A scenario whose values pack got ONE demand row, s_w = packed (cpu, mem) | skip << 31 in its
+// s_cpu row, for the prepacked-input kernel (k_ffd_pipe's PW).  That kernel runs only when the whole batch
+// packs by rng; when it does not (a single scenario out of range is enough) the u32 twin takes the batch, and
+// this pass first turns every prepacked scenario back into the legacy rows: s_cpu, s_mem, and the position
+// word with the bucket bits as the sort writes them and the skip bit from s_w's bit 31, every access
+// coalesced.  In every other case a workgroup returns at once.  `all` (the FPP_PREPACK_FFD = 0 build, whose
+// packed kernel reads the legacy rows too): unpack whether or not the batch packs.
+__global__ __launch_bounds__(1024) void k_unpack_rows(uint32_t C, uint32_t kpack, uint32_t all,
+                                                      const uint32_t *__restrict__ hdr, uint32_t *rng,
+                                                      const uint32_t *__restrict__ thr, uint32_t *__restrict__ s_cpu,
+                                                      uint32_t *__restrict__ s_mem, uint32_t *__restrict__ s_idx) {
+    const uint32_t s = blockIdx.x;
+    if (hdr[(size_t)s * 4 + 2] == 0u) return;  // (uniform) the sort wrote the legacy rows
+    uint32_t bc, bm;
+    if (!all && fp_pk_shifts(rng[0], rng[1], &bc, &bm)) return;  // (uniform) the batch packs: the row is read as it is
+    const uint32_t sc_c = hdr[(size_t)s * 4], sc_m = hdr[(size_t)s * 4 + 1];
+    if (threadIdx.x == 0) atomicAdd(&rng[3], 1u);  // scenarios repaired (fp_ctx_place_path out[3])
+    __shared__ uint32_t T[2 * K];
+    if (threadIdx.x < 2 * K) T[threadIdx.x] = kpack ? thr[threadIdx.x] : 0u;
+    __syncthreads();
+    auto bucket = [](const uint32_t *t, uint32_t v) {  // largest k with T[k] <= v (k_gather_sorted's)
+        uint32_t k = 0;
+#pragma unroll
+        for (uint32_t step = K / 2; step; step >>= 1) k += t[k + step] <= v ? step : 0u;
+        return k;
+    };
+    const size_t cb = (size_t)s * C;
+    for (uint32_t P = threadIdx.x; P < C; P += blockDim.x) {
+        const uint32_t w = s_cpu[cb + P];
+        const uint32_t cv = pk_cpu(w & ~CYC, sc_c), mv = pk_mem(w, sc_m);
+        const uint32_t kb = kpack ? (bucket(T, cv) << 21) | (bucket(T + K, mv) << 26) : 0u;
+        s_cpu[cb + P] = cv;
+        s_mem[cb + P] = mv;
+        s_idx[cb + P] = P | kb | (w & CYC);
+    }
+}
+
 // assign/reason from FFD (sorted) order back to container order, per scenario and per
 // range of container indices held in LDS: every read and write is coalesced.  The
 // pipeline's stores hit the sorted arrays at positions that advance together, so its
@@ -1782,12 +1882,13 @@ size_t lds_bytes(uint32_t W, uint32_t G, uint32_t R) {
 size_t lds_bytes_bigp(uint32_t R) { return FPP_BIGP_NOMASK ? 8 * 4 : lds_bytes(1, 12, R); }
 
 // G is a template parameter (records are register arrays); one instantiation per G
-template <uint32_t G, uint32_t BLK = 1024, uint32_t WV = 0, bool PK = false>
+template <uint32_t G, uint32_t BLK = 1024, uint32_t WV = 0, bool PK = false, bool PW = false>
 static int launch_g(hipStream_t st, unsigned grid, unsigned block, size_t lds, const PipeArgs &a) {
     if (block > BLK) return FP_EINVAL;
-    FP_HIP(hipFuncSetAttribute((const void *)k_ffd_pipe<G, BLK, WV, PK>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (PW && !a.pkhdr) return FP_EINVAL;
+    FP_HIP(hipFuncSetAttribute((const void *)k_ffd_pipe<G, BLK, WV, PK, PW>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds));
-    k_ffd_pipe<G, BLK, WV, PK><<<grid, block, lds, st>>>(a);
+    k_ffd_pipe<G, BLK, WV, PK, PW><<<grid, block, lds, st>>>(a);
     return FP_OK;
 }
 
@@ -1797,7 +1898,7 @@ typedef int (*launch_fn)(hipStream_t, unsigned, unsigned, size_t, const PipeArgs
 // the Makefile's FFD_TUS: each under its own LLVM machine scheduler) and is reached through its
 // launcher; without (the one-TU diagnostics build) they are instantiated here.
 struct TuKernel {
-    uint32_t G, BLK, WV, PK;
+    uint32_t G, BLK, WV, PK;  // PK as fp_pipe_tus.h lists it: 0 u32, 1 packed, 2 packed with prepacked input (PW)
     launch_fn launch;
     const void *(*kernel)();
 };
@@ -1819,7 +1920,8 @@ namespace fpp {
      ::fpp_tu_kernel_##name},
 #else
 #define FPP_TU_ENTRY(name, G, BLK, WV, PK) \
-    {G, BLK, WV, PK, launch_g<G, BLK, WV, (bool)PK>, [] { return (const void *)k_ffd_pipe<G, BLK, WV, (bool)PK>; }},
+    {G, BLK, WV, PK, launch_g<G, BLK, WV, (PK) != 0, (PK) == 2>,                          \
+     [] { return (const void *)k_ffd_pipe<G, BLK, WV, (PK) != 0, (PK) == 2>; }},
 #endif
 static const TuKernel kTu[] = {FPP_TUS(FPP_TU_ENTRY)};
 #undef FPP_TU_ENTRY
@@ -1829,9 +1931,9 @@ constexpr bool in_tu(uint32_t G, uint32_t BLK, uint32_t WV) {
     return false FPP_TUS(FPP_TU_IS);
 #undef FPP_TU_IS
 }
-static const TuKernel *tu_find(uint32_t G, uint32_t BLK, uint32_t WV, bool PK) {
+static const TuKernel *tu_find(uint32_t G, uint32_t BLK, uint32_t WV, bool PK, bool PW = false) {
     for (const TuKernel &k : kTu)
-        if (k.G == G && k.BLK == BLK && k.WV == WV && (k.PK != 0) == PK) return &k;
+        if (k.G == G && k.BLK == BLK && k.WV == WV && k.PK == (PK ? (PW ? 2u : 1u) : 0u)) return &k;
     return nullptr;
 }
 template <uint32_t G, uint32_t BLK = 1024, uint32_t WV = 0>
@@ -1870,12 +1972,12 @@ static inline bool wide12_big(uint32_t S, uint32_t W, uint32_t G) { return W == 
 // The kernel of a geometry (PK: the packed one, if compiled; else null).  big: the 4096-scenario
 // 12-group kernels (fp_pipe_launch takes them only with unbounded links): six waves per SIMD for the u32
 // one, seven for its packed twin, which runs on an LDS size of its own (lds_bytes_bigp).
-static void pipe_kernel(uint32_t G, uint32_t W, bool big, bool PK, launch_fn *l, const void **k) {
+static void pipe_kernel(uint32_t G, uint32_t W, bool big, bool PK, launch_fn *l, const void **k, bool PW = false) {
     const bool wide = wide_g(W, G);
     const uint32_t BLK = wide ? 64u : 1024u, WV = big ? (PK ? BIGP_WV : WIDE12_BIG_WAVES) : 0u;
     *l = nullptr;
     *k = nullptr;
-    if (const TuKernel *t = tu_find(G, BLK, WV, PK)) {
+    if (const TuKernel *t = tu_find(G, BLK, WV, PK, PW)) {
         *l = t->launch;
         *k = t->kernel();
         return;
@@ -1900,11 +2002,11 @@ static void pipe_kernel(uint32_t G, uint32_t W, bool big, bool PK, launch_fn *l,
 #define FPP_TU_CAT2(a, b) a##b
 #define FPP_TU_CAT(a, b) FPP_TU_CAT2(a, b)
 int FPP_TU_CAT(fpp_tu_launch_, FPP_TU_NAME)(hipStream_t st, unsigned grid, unsigned block, size_t lds, const void *args) {
-    return fpp::launch_g<FPP_TU_G, FPP_TU_BLK, FPP_TU_WV, (bool)FPP_TU_PK>(st, grid, block, lds,
-                                                                          *static_cast<const fpp::PipeArgs *>(args));
+    return fpp::launch_g<FPP_TU_G, FPP_TU_BLK, FPP_TU_WV, FPP_TU_PK != 0, FPP_TU_PK == 2>(
+        st, grid, block, lds, *static_cast<const fpp::PipeArgs *>(args));
 }
 const void *FPP_TU_CAT(fpp_tu_kernel_, FPP_TU_NAME)() {
-    return (const void *)fpp::k_ffd_pipe<FPP_TU_G, FPP_TU_BLK, FPP_TU_WV, (bool)FPP_TU_PK>;
+    return (const void *)fpp::k_ffd_pipe<FPP_TU_G, FPP_TU_BLK, FPP_TU_WV, FPP_TU_PK != 0, FPP_TU_PK == 2>;
 }
 #endif
 
@@ -2113,8 +2215,20 @@ size_t fp_pipe_ws_bytes(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N) {
     PipeGeom g;
     if (!pipe_geom(c, S, C, N, &g)) return 0;
     const size_t SC = (size_t)S * C, nlinks = (size_t)S * (g.B - 1);
+    // (the last two terms: the screen's summary rows, the prepack header, and a 256-B round-up per take)
     return 5 * SC * 4 + SC * 5 + 256 + nlinks * LCTL * 4 + (size_t)S * g.B * 8 + 8 + nlinks * g.slots * 2 * 64 * 4 +
-           (size_t)S * 16 + 11 * 256;
+           2 * (size_t)S * 16 + 12 * 256;
+}
+
+bool fp_pipe_prepack(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N) {
+    if (!PREPACK_OK || fp_opt(c, FP_OPT_PREPACK, 1) == 0 || fp_opt(c, FP_OPT_PACKED, 1) == 0) return false;
+    PipeGeom g;
+    if (!pipe_geom(c, S, C, N, &g)) return false;
+    if (!wide12_big(S, g.W, g.G) || g.bounded) return false;  // fp_pipe_launch's `big`
+    launch_fn l;
+    const void *k;
+    pipe_kernel(g.G, g.W, true, true, &l, &k, FPP_PREPACK_FFD != 0);
+    return l != nullptr;
 }
 
 uint32_t fp_pipe_kpack(const fp_ctx *c, uint32_t C) {
@@ -2194,11 +2308,15 @@ int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_
     // the packed pair (fp_pipe_pk.h): the batch's node values join the containers' OR (rng, from the sort)
     launch_fn u32fn = nullptr, pkfn = nullptr;
     const bool big = wide12_big(S, W, G) && !geo.bounded;  // (idle flushes of global links need bounded)
+    // the sort's prepack mode wrote packed demand rows (fp_pipe_prepack held): the packed kernel of the pair is
+    // the prepacked-input one, behind the repair pass
+    const uint32_t *pkhdr = ready ? ready->pkhdr : nullptr;
+    if (pkhdr && !(big && rng && ready->payload_done)) return FP_EINVAL;
     {
         const void *k_;
         pipe_kernel(G, W, big, false, &u32fn, &k_);
-        if (rng && fp_opt(c, FP_OPT_PACKED, 1) != 0) pipe_kernel(G, W, big, true, &pkfn, &k_);
-        if (!u32fn) return FP_EOVERFLOW;
+        if (rng && fp_opt(c, FP_OPT_PACKED, 1) != 0) pipe_kernel(G, W, big, true, &pkfn, &k_, pkhdr && FPP_PREPACK_FFD);
+        if (!u32fn || (pkhdr && !pkfn)) return FP_EOVERFLOW;
     }
     // stage-2 screen (k_node_summary); the fused sort (fp_place.hip) ran it ahead of itself and the payload
     // with it: `ready` then carries summ
@@ -2239,7 +2357,12 @@ int fp_pipe_launch(fp_ctx *c, uint32_t S, uint32_t C, uint32_t N, uint32_t scen_
                 b->conflict, b->level, summ, s_cpu, s_mem, s_req, s_conf, s_idx);
         FP_HIP(hipGetLastError());
     }
+    if (pkhdr) {  // always launched in prepack mode; a workgroup with nothing to repair returns at once
+        k_unpack_rows<<<S, 1024, 0, st>>>(C, kpack, FPP_PREPACK_FFD ? 0u : 1u, pkhdr, rng, thr, s_cpu, s_mem, s_idx);
+        FP_HIP(hipGetLastError());
+    }
     PipeArgs a;
+    a.pkhdr = pkhdr;
     a.C = C; a.N = N; a.scen_base = scen_base; a.W = W; a.G = G; a.R = R;
     a.B = B; a.slots = slots; a.bounded = geo.bounded; a.ticket = ctl; a.gabort = ctl + 32; a.ghead = ctl + 64;
     a.gdata = gdata;

@@ -4,6 +4,8 @@
 //   big / bigp  the 4096-scenario kernels (one-wave 12-group segments): u32 at six waves per SIMD; packed
 //               at seven and without bucket masks (fp_pipe.hip FPP_BIGP_NOMASK; WV = 7 names it,
 //               FPP_BIGP_WAVES sets the waves it is compiled for)
+//   bigpw       bigp reading prepacked demand rows (PK = 2: packed records and the template's PW; the sort's
+//               prepack mode, fp_place.hip): one word s_w per container instead of cpu, mem and position
 //   w12 / w12p  one-wave 12-group segments at five waves per SIMD (2048-scenario loads, bounded rings)
 //   m8  / m8p   2-stage segments of 8 groups (1024-scenario loads)
 //   m10 / m10p  4-stage segments of 10 groups (512-scenario loads)
@@ -16,6 +18,7 @@
 #define FPP_TUS(X)            \
     X(big, 12, 64, 6, 0)      \
     X(bigp, 12, 64, 7, 1)     \
+    X(bigpw, 12, 64, 7, 2)    \
     X(w12, 12, 64, 0, 0)      \
     X(w12p, 12, 64, 0, 1)     \
     X(m8, 8, 1024, 0, 0)      \

@@ -251,7 +251,32 @@ struct ScenSortArgs {
     // and the rest of the sorted SoA
     const uint32_t *req, *conf, *level, *summ;
     uint32_t *s_req, *s_conf;
+    // Prepack mode (the fused kernel, host-chosen: fp_pipe_prepack; null: off): [S][4] per scenario
+    // {sc_c, sc_m, packs_s, 0}.  The workgroup forms its own OR words -- exactly the two it ORs into rng, plus
+    // its scenario's node words summ[s][2..3] (k_node_summary; summ is not null in this mode) -- and derives
+    // the shifts and packs_s by the rule k_ffd_pipe applies to rng (fp_pk_shifts).  packs_s = 1: the scenario's
+    // demands go out as ONE row, s_w = (cpu >> sc_c) << 16 | mem >> sc_m in the s_cpu row, phase P ORs the skip
+    // bit into its bit 31 (a guard bit of the packed word, clear by construction), and s_mem / s_idx are not
+    // written; else the three legacy rows.
+    // Invariant: if the batch packs by rng, every scenario has packs_s = 1 -- its bits are a subset of rng's,
+    // so its shifts are >= the batch's and its fields <= the batch's -- and packed arithmetic is exact under
+    // any shifts that divide every value of the scenario: the plans do not depend on which shifts packed a row.
+    uint32_t *pkhdr;
 };
+
+// Prepack mode's decision for one scenario from its OR words (the same in every lane of the workgroup: taken
+// into scalar registers, the callers' loops branch on the result)
+__device__ __forceinline__ bool ss_prepack(const ScenSortArgs &a, uint32_t oc, uint32_t om, uint32_t &sc_c,
+                                           uint32_t &sc_m) {
+    oc = __builtin_amdgcn_readfirstlane(oc | a.summ[(size_t)blockIdx.x * 4 + 2]);
+    om = __builtin_amdgcn_readfirstlane(om | a.summ[(size_t)blockIdx.x * 4 + 3]);
+    const bool packs = fp_pk_shifts(oc, om, &sc_c, &sc_m);
+    if (threadIdx.x == 0) {
+        uint32_t *h = a.pkhdr + (size_t)blockIdx.x * 4;
+        h[0] = sc_c; h[1] = sc_m; h[2] = packs ? 1u : 0u; h[3] = 0u;
+    }
+    return packs;
+}
 
 // the u16 digit rows are also counted, zeroed and scanned through 32/64-bit views: these
 // types may alias the u16 entries (else type-based alias analysis may reorder them)
@@ -344,6 +369,10 @@ __device__ __forceinline__ void ss_offsets(uint16_t *WH, uint32_t *HS, uint32_t 
 // scenario's `order` row when k is odd (pass 0 starts from the identity), so pass 7 leaves it in
 // `order`; a pass reads the row back through agent-scope loads (other waves of the workgroup wrote
 // it in the pass before).  Then the sorted fields as the fast path writes them.
+// It has no value tables: the scenario's OR words (for rng, and for prepack mode's format decision, which has
+// to be made before the first sorted field is written) are accumulated in the counting passes 0 (mem) and 4
+// (cpu), each of which reads every container's value once, and left in HS[0] (cpu) and HS[1] (mem).  The
+// sorted fields follow in ss_generic_fields.
 __device__ void ss_generic(const ScenSortArgs &a, uint16_t *X, uint16_t *WH, uint32_t *HS, uint32_t *HB,
                            size_t cb, uint32_t C) {
     const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -353,6 +382,7 @@ __device__ void ss_generic(const ScenSortArgs &a, uint16_t *X, uint16_t *WH, uin
     uint16_t *myrow = WH + w * SS_DIG;
     uint32_t *ord = a.order + cb;
     const uint32_t *cpu = a.cpu + cb, *mem = a.mem + cb;
+    uint32_t oc = 0, om = 0;  // the scenario's OR words
     for (uint32_t k = 0; k < 8; ++k) {
         const uint32_t *key = k < 4 ? mem : cpu;
         const uint32_t sh = 8u * (k & 3u);
@@ -363,7 +393,12 @@ __device__ void ss_generic(const ScenSortArgs &a, uint16_t *X, uint16_t *WH, uin
         };
         for (uint32_t i = t; i < SS_WAVES * SS_DIG / 2; i += blockDim.x) reinterpret_cast<ss_u32a *>(WH)[i] = 0u;
         __syncthreads();
-        for (uint32_t p = s0 + lane; p < s1; p += 64) ss_inc16(myrow, ((~key[src(p)]) >> sh) & 0xFFu);
+        for (uint32_t p = s0 + lane; p < s1; p += 64) {
+            const uint32_t v = key[src(p)];  // (src is a permutation: the slices cover every container once)
+            om |= k == 0 ? v : 0u;
+            oc |= k == 4 ? v : 0u;
+            ss_inc16(myrow, ((~v) >> sh) & 0xFFu);
+        }
         __syncthreads();
         ss_offsets(WH, HS, HB, t, lane, w);
         for (uint32_t p0 = s0; p0 < s1; p0 += 64) {
@@ -384,21 +419,11 @@ __device__ void ss_generic(const ScenSortArgs &a, uint16_t *X, uint16_t *WH, uin
         }
         __syncthreads();
     }
-    uint32_t oc = 0, om = 0;  // the batch's OR words (k_scen_sort)
-    for (uint32_t P = t; P < C; P += blockDim.x) {
-        const uint32_t j = __hip_atomic_load(&ord[P], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t cv = cpu[j], mv = mem[j];
-        a.s_cpu[cb + P] = cv;
-        a.s_mem[cb + P] = mv;
-        a.s_idx[cb + P] = P | (a.kpack ? (ss_bucket(a.T, cv) << 21) | (ss_bucket(a.T + FP_BUCKETS, mv) << 26) : 0u);
-        oc |= cv;
-        om |= mv;
-    }
     for (int o = 32; o > 0; o >>= 1) {
         oc |= (uint32_t)__shfl_xor((int)oc, o);
         om |= (uint32_t)__shfl_xor((int)om, o);
     }
-    __syncthreads();  // HS is free: every wave is past the last pass
+    // (HS is free: every wave is past the last pass' barrier)
     if (t < 2) HS[t] = 0u;
     __syncthreads();
     if (lane == 0) {
@@ -406,9 +431,28 @@ __device__ void ss_generic(const ScenSortArgs &a, uint16_t *X, uint16_t *WH, uin
         atomicOr(&HS[1], om);
     }
     __syncthreads();
-    if (t == 0) {
+    if (t == 0) {  // the batch's OR words (k_scen_sort)
         fp_or_new_bits(&a.rng[0], HS[0]);
         fp_or_new_bits(&a.rng[1], HS[1]);
+    }
+}
+
+// ... and its sorted fields, from the `order` row pass 7 left (other waves wrote it: agent-scope loads, behind
+// ss_generic's last barrier): the legacy rows, or the one packed row (pw, with the scenario's shifts)
+__device__ __forceinline__ void ss_generic_fields(const ScenSortArgs &a, size_t cb, uint32_t C, bool pw,
+                                                  uint32_t sc_c, uint32_t sc_m) {
+    const uint32_t t = threadIdx.x;
+    const uint32_t *ord = a.order + cb, *cpu = a.cpu + cb, *mem = a.mem + cb;
+    for (uint32_t P = t; P < C; P += blockDim.x) {
+        const uint32_t j = __hip_atomic_load(&ord[P], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t cv = cpu[j], mv = mem[j];
+        if (pw) {
+            a.s_cpu[cb + P] = ((cv >> sc_c) << 16) | (mv >> sc_m);  // s_w
+        } else {
+            a.s_cpu[cb + P] = cv;
+            a.s_mem[cb + P] = mv;
+            a.s_idx[cb + P] = P | (a.kpack ? (ss_bucket(a.T, cv) << 21) | (ss_bucket(a.T + FP_BUCKETS, mv) << 26) : 0u);
+        }
     }
 }
 
@@ -486,6 +530,7 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
     uint16_t *myrow = WH + w * SS_DIG;
     uint32_t dc = 0, dm = 0, hbits = 0, lbits = 0;
     uint32_t dvp[SS_CHUNKS / 2];
+    bool pw = false;  // prepack mode: this scenario goes out as one packed row (uniform in the workgroup)
     unsigned long long ck1 = 0;
     // the scenario's rows as buffer resources: range-checked loads (0 past C) without branches
     const __amdgpu_buffer_rsrc_t rc_cpu = __builtin_amdgcn_make_buffer_rsrc((void *)cpu, (short)0, (int)(4 * C), 0x00020000);
@@ -594,6 +639,9 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
             __syncthreads();
             if (!elig) {  // more than 256 distinct values in a dimension, or a value >= 2^18 (uniform)
                 ss_generic(a, X, WH, HS, HB, cb, C);
+                uint32_t gsc_c = 0, gsc_m = 0;  // prepack mode: the same format decision, from ss_generic's OR words
+                if (FUSED && a.pkhdr) pw = ss_prepack(a, HS[0], HS[1], gsc_c, gsc_m);
+                ss_generic_fields(a, cb, C, pw, gsc_c, gsc_m);
                 return 2u;
             }
             if (t < SS_DIG) {
@@ -677,6 +725,20 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
         __syncthreads();
         const unsigned long long ck3 = SS_CLK();
         uint32_t big = 0;
+        // ---- prepack mode (ScenSortArgs::pkhdr): the scenario's format, decided before B writes anything.
+        // Every wave forms the same OR words from the value tables, the ones wave 0 ORs into rng after B
+        // (2 x <= 4 LDS words per lane; no barrier, no table of its own), thread 0 writes the header ----
+        uint32_t psc_c = 0, psc_m = 0;
+        if (FUSED && a.pkhdr) {
+            uint32_t oc = 0, om = 0;
+            for (uint32_t i = lane; i < dc; i += 64) oc |= CV[i];
+            for (uint32_t i = lane; i < dm; i += 64) om |= MV[i];
+            for (int o = 32; o > 0; o >>= 1) {
+                oc |= (uint32_t)__shfl_xor((int)oc, o);
+                om |= (uint32_t)__shfl_xor((int)om, o);
+            }
+            pw = ss_prepack(a, oc, om, psc_c, psc_m);
+        }
 
         // ---- B: each hd bucket sorted by ld by one wave and written out ----
         while (true) {
@@ -693,6 +755,7 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             const uint32_t cv = CV[d];
             const uint32_t kbc = a.kpack ? (uint32_t)CB[d] << 21 : 0u;
+            const uint32_t cvw = (cv >> psc_c) << 16;  // pw: the bucket's half of s_w
             if (hi - lo <= 64 * SS_REG) {
                 // the bucket in registers: count, scan, reorder X[lo, hi) in place, then write the
                 // bucket's window of every output array coalesced
@@ -719,12 +782,20 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
                     }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                for (uint32_t P = lo + lane; P < hi; P += 64) {
-                    const uint32_t j = X[P], l = LD[j];
-                    a.order[cb + P] = j;
-                    a.s_cpu[cb + P] = cv;
-                    a.s_mem[cb + P] = MV[l];
-                    a.s_idx[cb + P] = P | kbc | (a.kpack ? (uint32_t)MB[l] << 26 : 0u);
+                if (pw) {  // order and s_w alone (8 B per container instead of 16)
+                    for (uint32_t P = lo + lane; P < hi; P += 64) {
+                        const uint32_t j = X[P], l = LD[j];
+                        a.order[cb + P] = j;
+                        a.s_cpu[cb + P] = cvw | (MV[l] >> psc_m);
+                    }
+                } else {
+                    for (uint32_t P = lo + lane; P < hi; P += 64) {
+                        const uint32_t j = X[P], l = LD[j];
+                        a.order[cb + P] = j;
+                        a.s_cpu[cb + P] = cv;
+                        a.s_mem[cb + P] = MV[l];
+                        a.s_idx[cb + P] = P | kbc | (a.kpack ? (uint32_t)MB[l] << 26 : 0u);
+                    }
                 }
             } else {  // a large bucket: the same stable order, scattered straight to HBM
                 if (FUSED && lane == 0) NEXT[3] = 1u;  // X keeps the bucket in hd order only: P reads `order`
@@ -744,9 +815,13 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
                         if ((m & lt) == 0) myrow[l] = (uint16_t)(off + __popcll(m));
                         const uint32_t P = off + (uint32_t)__popcll(m & lt);
                         a.order[cb + P] = j;
-                        a.s_cpu[cb + P] = cv;
-                        a.s_mem[cb + P] = MV[l];
-                        a.s_idx[cb + P] = P | kbc | (a.kpack ? (uint32_t)MB[l] << 26 : 0u);
+                        if (pw) {
+                            a.s_cpu[cb + P] = cvw | (MV[l] >> psc_m);
+                        } else {
+                            a.s_cpu[cb + P] = cv;
+                            a.s_mem[cb + P] = MV[l];
+                            a.s_idx[cb + P] = P | kbc | (a.kpack ? (uint32_t)MB[l] << 26 : 0u);
+                        }
                     }
                 }
             }
@@ -800,8 +875,11 @@ __global__ __launch_bounds__(1024) void k_scen_sort(const ScenSortArgs a) {
         const unsigned long long ckp = SS_CLK();
         const bool from_x = rr != 2u && __builtin_amdgcn_readfirstlane((int)NEXT[3]) == 0;  // uniform
         // (the first chunk load begins with a barrier: every thread has read X, NEXT and the tables by then)
+        // (a prepacked scenario: the skip bit goes into bit 31 of s_w, the s_cpu row, where it went into the
+        // position word's bit 31 -- the same store / barrier / agent-scope load order; s_req keeps the reason)
+        static_assert(fpl::PL_SKIP == 1u << 31, "the skip bit of s_w");
         fpl::pl_by_field<true>(reinterpret_cast<uint32_t *>(ssm), C, a.order, X, from_x, a.req, a.conf, a.level, a.summ,
-                               a.s_req, a.s_conf, a.s_idx);
+                               a.s_req, a.s_conf, pw ? a.s_cpu : a.s_idx);
 #ifdef FP_PIPE_STATS
         __syncthreads();
         if (t == 0) atomicAdd(&g_sort_stats[8], SS_CLK() - ckp);
@@ -990,6 +1068,7 @@ int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b) {
         sa.scnt = rcnt;
         sa.rng = rcnt + CN_ORC;
         sa.simg = simg;
+        sa.pkhdr = nullptr;
         k_sort_image<<<1, 1024, 0, st>>>(rbm, rpre, rval, rcnt, thr, sa.kpack, simg);
         FP_HIP(hipGetLastError());
         // One kernel for sort and payload (FP_OPT_SORT_FUSED = 0: two, as before), wherever k_payload_lds would
@@ -1001,6 +1080,12 @@ int fp_dev_place_batch_impl(fp_ctx *c, const fp_batch *b) {
             soa.payload_done = true;
             sa.req = b->req_labels; sa.conf = b->conflict; sa.level = b->level; sa.summ = soa.summ;
             sa.s_req = soa.s_req; sa.s_conf = soa.s_conf;
+            // prepack mode: where the 4096-scenario pair will run and the node words exist (the screen's rows)
+            if (soa.summ && fp_pipe_prepack(c, S, C, N)) {
+                soa.pkhdr = (uint32_t *)fp_ws_take(c, (size_t)S * 16);
+                if (!soa.pkhdr) return FP_ENOMEM;
+                sa.pkhdr = soa.pkhdr;
+            }
             if (lds < fpl::PL_FIELD_LDS_BYTES) lds = fpl::PL_FIELD_LDS_BYTES;
             static_assert(fpl::PL_FIELD_LDS_BYTES <= SS_LDS_CAP, "the chunk buffer fits the sort's LDS");
             FP_HIP(hipFuncSetAttribute((const void *)k_scen_sort<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1032,7 +1117,12 @@ extern "C" int fp_ctx_place_path(fp_ctx *c, uint32_t *out3) {
     if (!c->last_rng) return FP_OK;
     FP_HIP(hipSetDevice(c->device));
     FP_HIP(hipStreamSynchronize(c->stream));
-    FP_HIP(hipMemcpy(out3, c->last_rng, 12, hipMemcpyDeviceToHost));
+    uint32_t w[4];  // the OR words, the kernel that ran, scenarios k_unpack_rows repaired (CN_ORC .. CN_WORDS - 1)
+    static_assert(CN_ORC + 4 == CN_WORDS, "last_rng holds four words");
+    FP_HIP(hipMemcpy(w, c->last_rng, 16, hipMemcpyDeviceToHost));
+    out3[0] = w[0];
+    out3[1] = w[1];
+    out3[2] = (w[2] == 1u && w[3] != 0u) ? 4u : w[2];
     return FP_OK;
 }
 

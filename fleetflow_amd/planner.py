@@ -335,10 +335,14 @@ class Planner:
 
     def place_path(self) -> dict:
         """The FFD kernel the last placement ran (fp_ctx_place_path; waits for the stream):
-        {"or_cpu", "or_mem", "packed"} -- packed is True for the packed (cpu, mem) records."""
+        {"or_cpu", "or_mem", "packed"} -- packed is True for the packed (cpu, mem) records; prepacked when
+        they were fed by prepacked demand rows (FP_OPT_PREPACK); repaired when the u32 kernel ran on rows the
+        repair pass unpacked."""
         out = (ct.c_uint32 * 3)()
         check(self._L.fp_ctx_place_path(self._ctx, out), "fp_ctx_place_path")
-        return {"or_cpu": int(out[0]), "or_mem": int(out[1]), "packed": int(out[2]) == 2, "ran": int(out[2]) != 0}
+        k = int(out[2])
+        return {"or_cpu": int(out[0]), "or_mem": int(out[1]), "packed": k in (2, 3), "ran": k != 0,
+                "prepacked": k == 3, "repaired": k == 4}
 
     def kernel_stats(self, kernel_id: int):
         ms = ct.c_double()

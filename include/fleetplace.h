@@ -179,7 +179,9 @@ int fp_ctx_profile(fp_ctx *ctx, int enable);
 int fp_ctx_kernel_stats(fp_ctx *ctx, int kernel_id, double *total_ms, uint64_t *launches);
 /* The FFD kernel the last placement call on this context ran (waits for the stream): out[0] / out[1]
  * = the OR of every cpu / mem value of its batch (containers and schedulable nodes), out[2] = 1 for
- * the u32 records, 2 for the packed (cpu, mem) records (FP_OPT_PACKED), 0 if nothing ran.  All zero
+ * the u32 records, 2 for the packed (cpu, mem) records (FP_OPT_PACKED), 3 for the packed records fed by
+ * prepacked demand rows (FP_OPT_PREPACK), 4 for the u32 records after the repair pass turned prepacked rows
+ * back into cpu / mem / position rows (a batch that does not pack as a whole), 0 if nothing ran.  All zero
  * also when a later call on the context has reused the workspace. */
 int fp_ctx_place_path(fp_ctx *ctx, uint32_t *out3);
 
@@ -221,7 +223,10 @@ enum fp_option {
                                  batch's values fit them (decided on the device, fp_pipe_pk.h)  */
     FP_OPT_SORT_FUSED = 23,   /* 0 = the per-scenario sort and the LDS-chunked payload as two kernels; auto = one
                                  kernel (the payload is the sort's last phase), wherever both would run */
-    FP_OPT_COUNT = 24
+    FP_OPT_PREPACK = 24,      /* 0 = the fused sort always writes the cpu / mem / position rows; auto = one packed
+                                 (cpu, mem) demand row per scenario whose values pack, wherever the packed
+                                 4096-scenario kernel may run (decided on the device; plans are the same) */
+    FP_OPT_COUNT = 25
 };
 int fp_ctx_set_option(fp_ctx *ctx, int option, int64_t value);
 int fp_ctx_get_option(fp_ctx *ctx, int option, int64_t *value);

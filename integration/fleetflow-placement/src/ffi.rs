@@ -154,6 +154,7 @@ pub const FP_OPT_PIPE_PRIO: c_int = 20;
 pub const FP_OPT_INDEG_BIN: c_int = 21;
 pub const FP_OPT_PACKED: c_int = 22;
 pub const FP_OPT_SORT_FUSED: c_int = 23;
+pub const FP_OPT_PREPACK: c_int = 24;
 pub const FP_GEOM_GROUPS: usize = 0;
 pub const FP_GEOM_STAGES: usize = 1;
 pub const FP_GEOM_SEGMENTS: usize = 2;
