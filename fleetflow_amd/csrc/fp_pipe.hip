@@ -556,7 +556,13 @@ __device__ __forceinline__ void fpp_group_lazy_p(uint64_t &remaining, uint32_t &
     if (!__builtin_amdgcn_ballot_w64(pk_fits(rw, qw))) return;  // an empty corner: no container fits
     uint64_t touched = 0;
     const unsigned long long gc0 = STAT_GCLK();
+#if FPP_BIGP_RETEST == 2 && !STAT_FINE  // (the fine diagnostics count the passes in _pm's C++ frame)
+    fpp_refilter_loop_pa(remaining, touched, asg, rw, rcu, rlab, cw, req, conf, gb64 + g * 64u, nchk, qw);
+#elif FPP_BIGP_RETEST
+    fpp_refilter_loop_pm(remaining, touched, asg, rw, rcu, rlab, cw, req, conf, gb64 + g * 64u, nchk, qw);
+#else
     fpp_refilter_loop_p(remaining, touched, asg, rw, rcu, rlab, cw, req, conf, gb64 + g * 64u, nchk, qw);
+#endif
     const uint64_t hit = remaining & __builtin_amdgcn_ballot_w64(asg != 0xFFFFFFFFu);
 #ifdef FP_PIPE_STATS
     nhit += (uint32_t)__builtin_popcountll(hit);
@@ -2532,6 +2538,17 @@ extern "C" int fp_debug_sys_stats(unsigned long long *out, int reset) {
     }
     return FP_OK;
 }
+#ifdef FP_PIPE_STATS_FINE
+extern "C" int fp_debug_retest_stats(unsigned long long *out, int reset) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_retest_stats), sizeof(unsigned long long) * 4) != hipSuccess)
+        return FP_EDEVICE;
+    if (reset) {
+        static const unsigned long long zero[4] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_retest_stats), zero, sizeof(zero)) != hipSuccess) return FP_EDEVICE;
+    }
+    return FP_OK;
+}
+#endif
 #endif
 
 extern "C" int fp_debug_pipe_stats(unsigned long long *out, int reset) {

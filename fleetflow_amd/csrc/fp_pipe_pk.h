@@ -42,11 +42,8 @@ __device__ __forceinline__ bool pk_fits(uint32_t wn, uint32_t wk) { return ((wn 
 // d = rw - kw, z = (d & G) | (kr & rlab) | (kx & rcu), ONE v_cmp, then the exec-masked placement
 // rw = d, rcu |= kx (22 instructions per container against 26).  SCC for STOP's select comes from
 // the s_and that sets exec (= hit).
-#define FPP_GXP_BODY(SEL, TEST)                                                             \
-    "s_cmp_eq_u64 %[q], 0\n\t"                                                             \
-    "s_cbranch_scc1 .Lfgxp_end%=\n\t"                                                      \
-    "s_mov_b64 %[esv], exec\n"                                                             \
-    ".Lfgxp_loop%=:\n\t"                                                                   \
+// one check of the serial loop: the queue's lowest lane against every node, and its placement
+#define FPP_GXP_CHECK(SEL)                                                                  \
     "s_ff1_i32_b64 %[t], %[q]\n\t"                                                         \
     "v_readlane_b32 %[kw], %[cw], %[t]\n\t"                                                \
     "v_readlane_b32 %[kr], %[req], %[t]\n\t"                                               \
@@ -68,7 +65,13 @@ __device__ __forceinline__ bool pk_fits(uint32_t wn, uint32_t wk) { return ((wn 
     "s_or_b32 %[nv], %[gbg], %[l]\n\t"         /* FP_NONE on a miss */                     \
     "s_lshl_b64 exec, 1, %[t]\n\t"                                                         \
     "v_mov_b32_e32 %[asg], %[nv]\n\t"                                                      \
-    "s_mov_b64 exec, %[esv]\n\t"                                                           \
+    "s_mov_b64 exec, %[esv]\n\t"
+#define FPP_GXP_BODY(SEL, TEST)                                                             \
+    "s_cmp_eq_u64 %[q], 0\n\t"                                                             \
+    "s_cbranch_scc1 .Lfgxp_end%=\n\t"                                                      \
+    "s_mov_b64 %[esv], exec\n"                                                             \
+    ".Lfgxp_loop%=:\n\t"                                                                   \
+    FPP_GXP_CHECK(SEL)                                                                     \
     "s_cmp_lg_u64 " TEST ", 0\n\t"                                                         \
     "s_cbranch_scc1 .Lfgxp_loop%=\n"                                                       \
     ".Lfgxp_end%=:"
@@ -94,8 +97,28 @@ __device__ __forceinline__ void fpp_asm_group_xp(uint64_t &q, uint64_t &touched,
     touched = fpp_uniform64(touched);
     nchk = (uint32_t)__builtin_amdgcn_readfirstlane((int)nchk);
 }
-#undef FPP_GXP_BODY
-#undef FPP_GXP_OPERANDS
+
+#if defined(FP_PIPE_STATS) && defined(FP_PIPE_STATS_FINE)
+// re-test diagnostics (FP_PIPE_STATS_FINE builds, tools/pipe_stats.py; summed over every kernel that runs
+// fpp_refilter_loop_p / _pm): [0] re-test passes (a first miss, the corner within REFILTER_MAX)
+// [1] corner nodes those passes walk [2] passes with an empty corner [3] corners above REFILTER_MAX
+__device__ unsigned long long g_retest_stats[4];
+__device__ __forceinline__ void fpp_retest_stat(uint64_t e) {
+    const uint32_t n = (uint32_t)__builtin_popcountll(e);
+    if (__lane_id() == 0) {
+        if (n <= REFILTER_MAX) {
+            atomicAdd(&g_retest_stats[0], 1ull);
+            atomicAdd(&g_retest_stats[1], (unsigned long long)n);
+            if (!n) atomicAdd(&g_retest_stats[2], 1ull);
+        } else {
+            atomicAdd(&g_retest_stats[3], 1ull);
+        }
+    }
+}
+#define FPP_RETEST_STAT(e) fpp_retest_stat(e)
+#else
+#define FPP_RETEST_STAT(e) ((void)0)
+#endif
 
 // fpp_refilter_loop on packed records (qw = the batch corner, packed)
 __device__ __forceinline__ void fpp_refilter_loop_p(uint64_t q, uint64_t &touched, uint32_t &asg, uint32_t &rw,
@@ -105,6 +128,7 @@ __device__ __forceinline__ void fpp_refilter_loop_p(uint64_t q, uint64_t &touche
     while (q) {
         uint64_t e = __builtin_amdgcn_ballot_w64(pk_fits(rw, qw));
         uint64_t fit = 0;
+        FPP_RETEST_STAT(e);
         if (__builtin_popcountll(e) <= REFILTER_MAX) {
             bool ok = false;
             while (e) {
@@ -126,6 +150,139 @@ __device__ __forceinline__ void fpp_refilter_loop_p(uint64_t q, uint64_t &touche
         fpp_asm_group_xp<true>(q, touched, asg, rw, rcu, rlab, cw, req, conf, gbg, nchk);
     }
 }
+
+// FPP_BIGP_RETEST: how the lazy walk of bigp / bigpw (fp_pipe.hip fpp_group_lazy_p) re-tests a queue after
+//   a miss.  0: fpp_refilter_loop_p, the kernels as before line for line; 1: fpp_refilter_loop_pm, the node
+//   loop alone in asm; 2: fpp_refilter_loop_pa, the whole loop in one asm block.  The A/B is in DESIGN.md 7
+//   round 14, the code of each in profiles/r17_bigp_regs.txt.
+#ifndef FPP_BIGP_RETEST
+#define FPP_BIGP_RETEST 2
+#endif
+
+// fpp_refilter_loop_p with the re-test over the corner's nodes in one asm block: the same outcomes (which
+// lanes a pass drops, the order of the checks, the plans).  Per corner node the test word
+//     z = ((nw - cw) & G) | (req & nlb) | (conf & ncu)          a lane fits the node <=> z == 0
+// goes into an UNSIGNED minimum over the nodes (a cpu borrow sets bit 31 of z: as a signed minimum a
+// failing node would hide a fitting one), and the minimum is compared with 0 once after the loop,
+// straight into a lane mask: 12 instructions per node against 19, and no bool carried in lane-mask pairs.
+// The accumulator starts at ~0, so an empty corner drops the whole queue.  The readlanes read rw, rlab
+// and rcu, which nothing inside the block writes; the lane select comes from an SALU instruction.
+__device__ __forceinline__ void fpp_refilter_loop_pm(uint64_t q, uint64_t &touched, uint32_t &asg, uint32_t &rw,
+                                                     uint32_t &rcu, uint32_t rlab, uint32_t cw, uint32_t req,
+                                                     uint32_t conf, uint32_t gbg, uint32_t &nchk, uint32_t qw) {
+    fpp_asm_group_xp<true>(q, touched, asg, rw, rcu, rlab, cw, req, conf, gbg, nchk);
+    const uint32_t gm = PK_GUARD;
+    while (q) {
+        uint64_t e = __builtin_amdgcn_ballot_w64(pk_fits(rw, qw));
+        uint64_t fit;
+        FPP_RETEST_STAT(e);
+        if (__builtin_popcountll(e) <= REFILTER_MAX) {
+            uint32_t zmin = 0xFFFFFFFFu, z, t, nw, nl, nu;
+            asm volatile(
+                "s_cmp_eq_u64 %[e], 0\n\t"
+                "s_cbranch_scc1 .Lfrm_end%=\n"
+                ".Lfrm_loop%=:\n\t"
+                "s_ff1_i32_b64 %[t], %[e]\n\t"
+                "v_readlane_b32 %[nw], %[rw], %[t]\n\t"
+                "v_readlane_b32 %[nl], %[rlab], %[t]\n\t"
+                "v_readlane_b32 %[nu], %[rcu], %[t]\n\t"
+                "s_bitset0_b64 %[e], %[t]\n\t"
+                "v_sub_u32_e32 %[z], %[nw], %[cw]\n\t"
+                "v_and_b32_e32 %[z], %[gm], %[z]\n\t"
+                "v_and_or_b32 %[z], %[nl], %[req], %[z]\n\t"
+                "v_and_or_b32 %[z], %[nu], %[conf], %[z]\n\t"
+                "v_min_u32_e32 %[zmin], %[z], %[zmin]\n\t"
+                "s_cmp_lg_u64 %[e], 0\n\t"
+                "s_cbranch_scc1 .Lfrm_loop%=\n"
+                ".Lfrm_end%=:\n\t"
+                "v_cmp_eq_u32_e64 %[fit], 0, %[zmin]\n\t"
+                "s_and_b64 %[fit], %[q], %[fit]"
+                : [e] "+s"(e), [zmin] "+v"(zmin), [fit] "=&s"(fit), [z] "=&v"(z), [t] "=&s"(t), [nw] "=&s"(nw),
+                  [nl] "=&s"(nl), [nu] "=&s"(nu)
+                : [q] "s"(q), [rw] "v"(rw), [rlab] "v"(rlab), [rcu] "v"(rcu), [cw] "v"(cw), [req] "v"(req),
+                  [conf] "v"(conf), [gm] "s"(gm)
+                : "scc");
+            fit = fpp_uniform64(fit);
+        } else {
+            fit = q;
+        }
+        if (fit == q) {
+            fpp_asm_group_xp<false>(q, touched, asg, rw, rcu, rlab, cw, req, conf, gbg, nchk);
+            break;
+        }
+        q = fit;
+        fpp_asm_group_xp<true>(q, touched, asg, rw, rcu, rlab, cw, req, conf, gbg, nchk);
+    }
+}
+
+// fpp_refilter_loop_pm as ONE asm block (FPP_BIGP_RETEST 2): the STOP loop, the corner ballot, the node
+// loop and the plain loop with the branches between them, so that the compiler adds nothing around the
+// three loops (lane masks turned into VCC and back, copies of rw / rcu / asg on every edge between the
+// blocks).  The same checks in the same order.  An empty corner, and a pass that keeps no lane, leave at
+// once: the STOP loop on an empty queue was a no-op.  m1 / m2, kw / kr / kx, t0 and d are free between
+// two checks and serve the node loop (the corner's mask, its node's words, the minimum and z).
+__device__ __forceinline__ void fpp_refilter_loop_pa(uint64_t q, uint64_t &touched, uint32_t &asg, uint32_t &rw,
+                                                     uint32_t &rcu, uint32_t rlab, uint32_t cw, uint32_t req,
+                                                     uint32_t conf, uint32_t gbg, uint32_t &nchk, uint32_t qw) {
+    uint32_t t, kw, kr, kx, l, nv, t0, d;
+    uint64_t m1, m2, esv, qx;
+    const uint32_t gm = PK_GUARD;
+    asm volatile(
+        "s_cmp_eq_u64 %[q], 0\n\t"
+        "s_cbranch_scc1 .Lfrt_end%=\n\t"
+        "s_mov_b64 %[esv], exec\n"
+        ".Lfrt_stop%=:\n\t"                          // the STOP loop: q is not empty here
+        FPP_GXP_CHECK("s_cselect_b64 %[qx], %[q], 0\n\t")
+        "s_cmp_lg_u64 %[qx], 0\n\t"
+        "s_cbranch_scc1 .Lfrt_stop%=\n\t"
+        "s_cmp_eq_u64 %[q], 0\n\t"                  // a miss left lanes behind it?
+        "s_cbranch_scc1 .Lfrt_end%=\n\t"
+        "v_subrev_u32_e32 %[d], %[qw], %[rw]\n\t"   // the corner's nodes now
+        "v_and_b32_e32 %[d], %[gm], %[d]\n\t"
+        "v_cmp_eq_u32_e64 %[m1], 0, %[d]\n\t"
+        "s_bcnt1_i32_b64 %[t], %[m1]\n\t"           // SCC = the corner holds a node
+        "s_cbranch_scc0 .Lfrt_end%=\n\t"            // empty: the whole queue is dropped
+        "s_cmp_gt_u32 %[t], %[rmax]\n\t"
+        "s_cbranch_scc1 .Lfrt_plain%=\n\t"
+        "v_mov_b32_e32 %[t0], -1\n"
+        ".Lfrt_node%=:\n\t"
+        "s_ff1_i32_b64 %[t], %[m1]\n\t"
+        "v_readlane_b32 %[kw], %[rw], %[t]\n\t"
+        "v_readlane_b32 %[kr], %[rlab], %[t]\n\t"
+        "v_readlane_b32 %[kx], %[rcu], %[t]\n\t"
+        "s_bitset0_b64 %[m1], %[t]\n\t"
+        "v_sub_u32_e32 %[d], %[kw], %[cw]\n\t"
+        "v_and_b32_e32 %[d], %[gm], %[d]\n\t"
+        "v_and_or_b32 %[d], %[kr], %[req], %[d]\n\t"
+        "v_and_or_b32 %[d], %[kx], %[conf], %[d]\n\t"
+        "v_min_u32_e32 %[t0], %[d], %[t0]\n\t"      // unsigned: a cpu borrow is bit 31 of z
+        "s_cmp_lg_u64 %[m1], 0\n\t"
+        "s_cbranch_scc1 .Lfrt_node%=\n\t"
+        "v_cmp_eq_u32_e64 %[m2], 0, %[t0]\n\t"
+        "s_and_b64 %[m2], %[q], %[m2]\n\t"          // the lanes some node takes; SCC = any
+        "s_cbranch_scc0 .Lfrt_end%=\n\t"
+        "s_cmp_eq_u64 %[m2], %[q]\n\t"              // nothing dropped: the plain loop
+        "s_cbranch_scc1 .Lfrt_plain%=\n\t"
+        "s_mov_b64 %[q], %[m2]\n\t"
+        "s_branch .Lfrt_stop%=\n"
+        ".Lfrt_plain%=:\n\t"
+        FPP_GXP_CHECK("")
+        "s_cmp_lg_u64 %[q], 0\n\t"
+        "s_cbranch_scc1 .Lfrt_plain%=\n"
+        ".Lfrt_end%=:"
+        : [q] "+s"(q), [touched] "+s"(touched), [asg] "+v"(asg), [rw] "+v"(rw), [rcu] "+v"(rcu), [nchk] "+s"(nchk),
+          [t] "=&s"(t), [kw] "=&s"(kw), [kr] "=&s"(kr), [kx] "=&s"(kx), [l] "=&s"(l), [nv] "=&s"(nv),
+          [m1] "=&s"(m1), [m2] "=&s"(m2), [esv] "=&s"(esv), [qx] "=&s"(qx), [t0] "=&v"(t0), [d] "=&v"(d)
+        : [rlab] "v"(rlab), [cw] "v"(cw), [req] "v"(req), [conf] "v"(conf), [gbg] "s"(gbg), [gm] "s"(gm),
+          [qw] "s"(qw), [rmax] "i"(REFILTER_MAX)
+        : "scc", "memory");
+    touched = fpp_uniform64(touched);
+    nchk = (uint32_t)__builtin_amdgcn_readfirstlane((int)nchk);
+}
+
+#undef FPP_GXP_CHECK
+#undef FPP_GXP_BODY
+#undef FPP_GXP_OPERANDS
 
 // fpp_group_x on packed records (same epilogue)
 template <uint32_t g, uint32_t G, bool IB = false>

@@ -31,11 +31,17 @@ def main():
     f = L.fp_debug_pipe_stats
     f.argtypes = [ct.POINTER(ct.c_ulonglong), ct.c_int]
     buf = (ct.c_ulonglong * 256)()
+    # FP_PIPE_STATS_FINE builds: the re-test after a first miss (fp_pipe_pk.h g_retest_stats)
+    r, rb = getattr(L, "fp_debug_retest_stats", None), (ct.c_ulonglong * 4)()
+    if r is not None:
+        r.argtypes = [ct.POINTER(ct.c_ulonglong), ct.c_int]
     p.profile(True)
     for rep in range(2):
         db.restore_nodes(pristine)
         torch.cuda.synchronize()
         f(buf, 1)
+        if r is not None:
+            r(rb, 1)
         t0 = time.perf_counter()
         p.dev_place_batch(db)
         p.sync()
@@ -60,6 +66,12 @@ def main():
         print(f"{w:5d} {f(v[8]):18.2f} {f(v[9]):8.2f} {f(v[10]):10.2f} {f(v[11]):5.2f} {f(v[12]):9.2f} {f(v[13]):6.2f}"
               f"   | {v[10]/max(v[1],1):8.0f}   in cand_loop: checks {f(v[6]):6.2f} mask upkeep {f(v[7]):6.2f}"
               f"  queues/scen {v[14]/S:7.0f} touched/scen {v[15]/S:7.0f}")
+    if r is not None:
+        r(rb, 0)
+        queues = sum(buf[w * 16 + 14] for w in range(16))
+        print(f"re-test per scenario: queues {queues/S:.0f}  passes {rb[0]/S:.0f}  corner nodes {rb[1]/S:.0f}  "
+              f"empty-corner passes {rb[2]/S:.0f}  big-corner exits {rb[3]/S:.1f}  "
+              f"(passes x 25 + nodes x 19 = {(rb[0]*25 + rb[1]*19)/S:.0f} instructions)")
 
 
 
